@@ -10,7 +10,11 @@ inside a step; the only collectives are the barrier, the MAX of the elapsed time
 `python bench.py --gpus N` launches itself under torch.distributed.run when it is not already running under it.
 
 Rank 0 prints ONE JSON line.  `value` is measured with the library's DEFAULT arithmetic, which is fp32-class
-(f16x3 split products, see `dtype`); extra objects:
+(f16x3 split products, see `dtype`).  A plain run sets up, warms up, times the K steps and prints the line (`ms_per_step`,
+`per_rank_ms`, `ms_per_step_device`, `step_ms_min_med_max`, `ranks`, `config`); `kernels`, the roofline objects, the
+extra legs, `first_steps_ms` and `cpu_baseline` are measured only with `--full` (each part still subject to its --no-*
+switch).  `--dump-outputs DIR` writes the logits of the last timed step as DIR/logits.npy (float32; other ranks:
+logits_rank<r>.npy) - inputs and weights are seeded, so two builds can be compared output for output.  Extra objects:
   roofline       dominant kernel of the step: ALGORITHMIC flops (or bytes) / hipEvent time / the dense peak of the
                  data type its MFMAs are issued in; `issued_*` = the matrix-core flops actually issued (3x for f16x3).
                  The hipEvent times come from a second, instrumented pass of the same K steps right behind the timed
@@ -377,7 +381,9 @@ def cpu_baseline(cfg, sd, N, map_w, budget_s=30.0):
 
 
 def relaunch_under_torchrun(n):
-    """`python bench.py --gpus N` outside torch.distributed.run: start N ranks of this script on this node."""
+    """`python bench.py --gpus N` outside torch.distributed.run: start N ranks of this script on this node (in a child
+    process; this one exits with its status)."""
+    import subprocess
     s = socket.socket()
     s.bind(("127.0.0.1", 0))
     port = s.getsockname()[1]
@@ -385,7 +391,7 @@ def relaunch_under_torchrun(n):
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n),
            "--master-addr", "127.0.0.1", "--master-port", str(port), os.path.abspath(__file__)] + sys.argv[1:]
-    os.execv(sys.executable, cmd)
+    raise SystemExit(subprocess.call(cmd))
 
 
 def main():
@@ -403,6 +409,11 @@ def main():
                          "collectives (sum of ones, barrier, gather of the elapsed times) go over gloo.  Exercises bench.py's own "
                          "rank logic (ranks_seen, per_rank_ms, MAX over ranks); its value is NOT a scaling measurement and the "
                          "line says so (config.rehearsal)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: per-kernel times and rooflines, the cold first steps, "
+                         "the extra legs and the CPU baseline (each still subject to its --no-* switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the logits of the last timed step to DIR/logits.npy (float32)")
     args = ap.parse_args()
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
@@ -457,9 +468,10 @@ def main():
             dist.barrier()
         torch.cuda.synchronize(dev)
 
-    def run_leg(x, S, steps, warmup, timing, net=net, repeats=1):
+    def run_leg(x, S, steps, warmup, timing, net=net, repeats=1, keep_out=False):
         """`warmup` untimed steps, then EXACTLY `steps` timed ones between barrier + synchronize on both sides.
         Returns (MAX over ranks of the elapsed seconds, per-tag kernel times of THIS rank, every rank's own elapsed ms).
+        keep_out: a copy of the last timed step's logits, taken behind the timed region, in run_leg.out.
         repeats > 1 (the EXTRA legs only, never the headline): the timed region is run that often and the fastest one reported -
         the GPU boxes show a sporadic 60-90 ms device stall every few seconds (tools/exp/stall_probe2.py: not tied to the model,
         the step or the collector), which triples a 20-step region of a 1 ms workload when it lands inside it."""
@@ -492,6 +504,8 @@ def main():
                 ev1.record()
                 barrier()
                 el = time.perf_counter() - t0
+                if keep_out:
+                    run_leg.out = out.detach().clone()
                 if elapsed is None or el < elapsed:
                     elapsed = el
                     run_leg.device_ms = ev0.elapsed_time(ev1) / steps
@@ -604,7 +618,7 @@ def main():
     S = comm_gso(B, N, map_w, seed=4242 + rank).to(dev)       # float32, as the dataloader hands it over
     # the profiling hooks run on EVERY rank or on none (a MAX over ranks of differently instrumented processes would
     # measure the instrumentation); rank 0's table is the one reported
-    timing = not args.no_kernel_timing
+    timing = args.full and not args.no_kernel_timing
     # The device has been IDLE while the CPU-baseline leg ran (tens of seconds): its clocks take ~10 steps (25 ms) to come back
     # (tools/ramp_probe.py, profiles/r05g/ramp_probe.txt: per-step device times 3.14, 3.00, 2.80, 2.64, 2.56 ms .. then 2.37-2.39
     # steady; behind matrix work 2.75, 2.46, 2.40, 2.39 ..).  With the driver's `--warmup 5 --steps 20` the timed region used to
@@ -613,27 +627,40 @@ def main():
     # steps, on every rank: ~150 ms of matrix work that is not a step - W and K are untouched, the timed region is steady state.
     # What a COLD caller sees: two untimed steps take the one-off work (weight packs, the calibration
     # pass), the device then idles for two seconds, and the next five steps are timed one by one (synchronised each: +~20 us of
-    # host latency per step).  Not part of `value`; the pre-heat below and the W warm-up steps come after it.
+    # host latency per step).  Not part of `value`; the pre-heat below and the W warm-up steps come after it.  A plain run
+    # (no --full) takes the two set-up steps only.
     first_steps_ms = []
     with torch.no_grad():
         for _ in range(2):
             net.addGSO(S)
             net(x)
         torch.cuda.synchronize(dev)
-        time.sleep(2.0)
-        for _ in range(5):
-            t0_ = time.perf_counter()
-            net.addGSO(S)
-            net(x)
-            torch.cuda.synchronize(dev)
-            first_steps_ms.append(round((time.perf_counter() - t0_) * 1e3, 4))
+        if args.full:
+            time.sleep(2.0)
+            for _ in range(5):
+                t0_ = time.perf_counter()
+                net.addGSO(S)
+                net(x)
+                torch.cuda.synchronize(dev)
+                first_steps_ms.append(round((time.perf_counter() - t0_) * 1e3, 4))
     sus_pre = None
     try:
         sus_pre = sustained_mfma_tflops(lib, dev, reps=15, ms=10)
         sus_pre = (sus_pre, sustained_mfma_tflops.clock_mhz, sustained_mfma_tflops.per_clk)
     except Exception:
         pass
-    elapsed, kern, per_rank_ms = run_leg(x, S, args.steps, args.warmup, timing)
+    elapsed, kern, per_rank_ms = run_leg(x, S, args.steps, args.warmup, timing, keep_out=bool(args.dump_outputs))
+    if args.dump_outputs:
+        # what a caller of the timed step receives: the logits (the synthetic S holds no NaN for addGSO to scrub); float32, at most
+        # 64 MB over all ranks (a fixed, seeded sample of the rows beyond that)
+        import numpy as np
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        logits = run_leg.out.float().cpu().numpy()
+        cap_rows = max(1, (64 << 20) // world // max(1, logits[:1].nbytes))
+        if logits.shape[0] > cap_rows:
+            logits = logits[np.sort(np.random.default_rng(0).choice(logits.shape[0], cap_rows, replace=False))]
+        np.save(os.path.join(args.dump_outputs, "logits.npy" if rank == 0 else "logits_rank%d.npy" % rank), logits)
+        del run_leg.out
     instr_ms = getattr(run_leg, "instrumented_ms", 0.0)
     dev_ms = getattr(run_leg, "device_ms", 0.0)      # hipEvent pair around the K timed steps on the launch stream (this rank)
     step_ms = getattr(run_leg, "step_ms", None)      # [min, median, max] device time of a timed step (events between the steps)
@@ -672,8 +699,9 @@ def main():
                           "global_batch": B * world, "agents": N, "parallelism": "instance-sharded x%d" % world,
                           "preheat": "in front of the W warm-up steps: gc.collect + freeze, and ~150 ms of registers-only MFMA work "
                                      "(the roofline.sustained_* measurement) so that the timed region starts at the clocks the "
-                                     "chip holds under load; a cold caller's first steps: first_steps_ms"},
-               "first_steps_ms": first_steps_ms}
+                                     "chip holds under load; a cold caller's first steps: first_steps_ms (--full)"}}
+        if args.full:
+            res["first_steps_ms"] = first_steps_ms
         if args.share_gpu:
             res["config"]["rehearsal"] = ("--share-gpu: %d ranks drive ONE device over gloo - the launch / rank logic of the "
                                           "N > 1 run, not a scaling measurement" % world)
@@ -718,7 +746,7 @@ def main():
                                     "same %d steps right behind the timed region (the pairs cost 2-3 %% of a step: the timed "
                                     "region runs without them)" % args.steps)
     # ---- extra legs (N=1 only; never `value`) -----------------------------------------------------------------------------
-    if world == 1 and rank == 0 and not args.no_extra_legs and args.workload == "c3" and not args.batch:
+    if args.full and world == 1 and rank == 0 and not args.no_extra_legs and args.workload == "c3" and not args.batch:
         esteps, ewarm = max(5, min(args.steps, 20)), 3
         # (a) the north-star shape: N=100, batch 1024, default arithmetic
         Bn = 1024
@@ -997,7 +1025,7 @@ def main():
                                   "N10_device": _g(res, "latency_b1", "N10", "device_back_to_back_us"),
                                   "N100_device": _g(res, "latency_b1", "N100", "device_back_to_back_us")}}
     # ---- the CPU baseline: the pinned oracle on this box's host cores, behind every GPU leg (nothing of it is inside a timed region)
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if args.full and rank == 0 and world == 1 and not args.no_cpu_baseline:
         torch.cuda.synchronize(dev)
         try:
             cpu = cpu_baseline(cfg, {k: v.detach().cpu() for k, v in net.state_dict().items()}, N, map_w)

@@ -7,6 +7,7 @@ import socket
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 import torch
 
@@ -114,7 +115,7 @@ def _one_json_line(out):
 def test_bench_runs_as_the_driver_launches_it(gpu_device):
     """`python bench.py --gpus 1 ...` and the torch.distributed.run form the driver uses for N > 1 (here with one rank:
     RCCL is initialised, ranks_seen comes from an all_reduce of ones) both print exactly one JSON line and exit 0."""
-    common = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "8", "--no-cpu-baseline"]
+    common = ["--gpus", "1", "--steps", "2", "--warmup", "1", "--batch", "8", "--no-cpu-baseline", "--full"]
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
@@ -129,6 +130,31 @@ def test_bench_runs_as_the_driver_launches_it(gpu_device):
     assert r.returncode == 0, r.stderr[-2000:]
     d = _one_json_line(r.stdout)
     assert d["n_gpus"] == 1 and d["ranks_seen"] == 1 and d["value"] > 0
+
+
+def test_bench_plain_run_and_output_dump(gpu_device, tmp_path):
+    """A plain `bench.py` run (no --full) times exactly --steps steps and prints the headline keys only; --dump-outputs
+    writes the last timed step's logits, and two runs with the same arguments write the same inputs' logits."""
+    env = dict(os.environ)
+    for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
+        env.pop(k, None)
+    dumps = []
+    for i in range(2):
+        out_dir = tmp_path / ("run%d" % i)
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1",
+                            "--batch", "8", "--dump-outputs", str(out_dir)], capture_output=True, text=True, env=env, timeout=600)
+        assert r.returncode == 0, r.stderr[-2000:]
+        d = _one_json_line(r.stdout)
+        assert d["steps"] == 3 and d["ms_per_step"] > 0 and d["value"] > 0 and d["higher_is_better"] is True
+        for k in ("metric", "unit", "dtype"):
+            assert d[k]
+        for k in ("kernels", "roofline", "cpu_baseline", "first_steps_ms", "north_star_b1024"):
+            assert k not in d, k
+        assert sorted(p.name for p in out_dir.iterdir()) == ["logits.npy"]
+        a = np.load(out_dir / "logits.npy")
+        assert a.dtype == np.float32 and a.shape == (8 * 100, 5) and np.isfinite(a).all()
+        dumps.append(a)
+    assert np.array_equal(dumps[0], dumps[1])
 
 
 def test_bench_eight_ranks_rehearsed_on_one_gpu(gpu_device):

@@ -4,7 +4,7 @@
 for rep in 1 2; do
   for w in ${WORKLOADS:-c3}; do
   for e in "$@"; do
-    env $e python bench.py --workload $w --no-cpu-baseline --no-extra-legs --steps 30 --warmup 5 2>/dev/null | python -c "
+    env $e python bench.py --full --workload $w --no-cpu-baseline --no-extra-legs --steps 30 --warmup 5 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=d['kernels']

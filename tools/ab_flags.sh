@@ -7,7 +7,7 @@ SRC=${SRC:-block_fused.hip}
 IFS="|" read -ra VARS <<< "|${FLAG_LIST}|x"; unset "VARS[${#VARS[@]}-1]"; VARS+=("")
 for F in "${VARS[@]}"; do
   bash tools/build_variant.sh ab $SRC "$F" > /dev/null 2>&1 || { echo "build failed: $F"; continue; }
-  MAGAT_LIB_PATH=magat_pathplanning_amd/lib/libmagat_hip_ab.so python bench.py --no-cpu-baseline --no-extra-legs --steps 30 --warmup 5 2>/dev/null | python -c "
+  MAGAT_LIB_PATH=magat_pathplanning_amd/lib/libmagat_hip_ab.so python bench.py --full --no-cpu-baseline --no-extra-legs --steps 30 --warmup 5 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.readline())
 ks = [k for k in d['kernels'] if any(s in k for s in '''${KERNELS:-layer}'''.split('|'))]

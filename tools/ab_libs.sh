@@ -4,7 +4,7 @@ ENVS=$1; shift
 for rep in 1 2; do
   for n in "$@"; do
     L=$PWD/magat_pathplanning_amd/lib/libmagat_hip${n:+_$n}.so
-    env $ENVS MAGAT_LIB_PATH=$L python bench.py --no-cpu-baseline --no-extra-legs --steps 30 --warmup 5 2>/dev/null | python -c "
+    env $ENVS MAGAT_LIB_PATH=$L python bench.py --full --no-cpu-baseline --no-extra-legs --steps 30 --warmup 5 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=d['kernels']

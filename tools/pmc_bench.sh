@@ -3,7 +3,7 @@
 # Usage: tools/pmc_bench.sh <tag> "<CTR1 CTR2 ...>" ["<second pass>"...]
 R=$PWD; TAG=$1; shift; OUT=$R/gpurun_out/pmcb_$TAG; mkdir -p $OUT; cd /tmp; export TMPDIR=/tmp
 i=0
-for P in "$@"; do i=$((i+1)); rocprofv3 --pmc $P --kernel-trace --output-format csv -d $OUT/p$i -o b -- python $R/bench.py --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-timing > $OUT/p$i.log 2>&1; done
+for P in "$@"; do i=$((i+1)); rocprofv3 --pmc $P --kernel-trace --output-format csv -d $OUT/p$i -o b -- python $R/bench.py --full --steps 2 --warmup 1 --no-cpu-baseline --no-kernel-timing > $OUT/p$i.log 2>&1; done
 cd $R
 python - <<PY
 import csv, glob, collections
