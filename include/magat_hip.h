@@ -105,6 +105,17 @@ int magat_reset_option(const char* name);   /* back to the value the process sta
  *    (= reference output (B,PF|F,N) transposed, i.e. already in the (B*N, features) layout
  *    actionsMLP consumes, …bottleneck.py:331).  ldy = row stride of Y in floats (>= width),
  *    so Y may be a column block of a wider skip-concat buffer.
+ * Alignment (every graph-layer entry point: magat_gat_forward_{packed,planned,tail,dense}_f32, magat_gat_forward_csr_{f32,bf16},
+ *    magat_gat_forward_csc_{f32,bf16,bf16_f32out}, magat_gnn_forward_csr_f32): X must start on a 16-byte boundary - otherwise
+ *    MAGAT_ERR_UNSUPPORTED before anything is launched (its rows are read in 16-byte pieces).  ldy must be a multiple of 4
+ *    (MAGAT_ERR_BAD_SHAPE).  Y may start anywhere a float (bf16: an element) may, a column block at an odd column offset
+ *    included - with two exceptions, each answered with MAGAT_ERR_UNSUPPORTED before anything is launched:
+ *    (1) dense entries, 128 features on 106 .. 128 agents (beyond the two-launch form's tiles, only the one-launch kernel
+ *        covers them): Y on a 16-byte boundary (the *_csr_* / *_csc_* entry points take that shape at any Y);
+ *    (2) magat_gat_forward_csc_bf16 and magat_gat_forward_csc_bf16_f32out in their fused form (option CSR_FUSED, on by
+ *        default; KeyQuery, K = 2, G = F = 128, concat, P in {1, 2, 4}): Y and bias on a 16-byte boundary, and ldy a multiple
+ *        of 8 for bf16 rows (4 for float32 rows).  magat_gat_forward_csr_bf16 takes that shape at any Y.
+ *    Nothing outside the result block of Y is written.
  * A_opt [B,P,N,N] attention (aij of graphML.py:4650) or NULL (not materialised).
  * Supported: G,F in {16,32,64,128,256}, 1 <= N <= 128 (dense mask path), K >= 1, P >= 1.
  */

@@ -485,18 +485,22 @@ static int enc_run_resnet(const magat_encoder_desc* d, const float* x, float* fe
       if (inguard) {
         lg.x = x + (size_t)m0 * 3 * H * W; lg.pack = pk; lg.off = d->off; lg.book = reinterpret_cast<int*>(range_flag);
       }
-      if (lat)
+      // (lat_all skipped the stem launch above: buf[0] / buf[1] hold nothing, so only block_lat - which runs the stem itself -
+      //  may follow.  Its conditions are lat's and head_done's, checked here so that a later edit cannot split them silently)
+      if (lat_all && !(lat && head_done)) return MAGAT_ERR_UNSUPPORTED;
+      if (lat) {
         rc = magat_block_lat(buf[1], buf[0], pk + d->chain_off, sp ? sp + 928 : pk + d->off[5], sp ? sp + 960 : pk + d->off[7],
                              sp ? sp + 1024 : pk + d->off[9], buf[2], pk + d->chain3_off, sp ? sp + 1088 : pk + d->off[11],
                              sp ? sp + 1216 : pk + d->off[13], mm, reinterpret_cast<int*>(range_flag), st,
                              sp ? sp + 1344 : nullptr, head_gl ? 1 : 0, head_done ? &lh : nullptr, inguard ? &lg : nullptr,
                              (lat_all && head_done) ? &ls : nullptr);
-      if (lat && rc == MAGAT_OK && inguard) *self_guarded = true;
-      else
-      rc = magat_block_full(buf[1], buf[0], pk + d->chain_off, sp ? sp + 928 : pk + d->off[5], sp ? sp + 960 : pk + d->off[7],
-                            sp ? sp + 1024 : pk + d->off[9], buf[2], pk + d->chain3_off, sp ? sp + 1088 : pk + d->off[11],
-                            sp ? sp + 1216 : pk + d->off[13], mm, reinterpret_cast<int*>(range_flag), st, sp ? sp + 1344 : nullptr,
-                            head_gl ? 1 : 0);
+        if (rc != MAGAT_OK) return rc;
+        if (inguard) *self_guarded = true;
+      } else
+        rc = magat_block_full(buf[1], buf[0], pk + d->chain_off, sp ? sp + 928 : pk + d->off[5], sp ? sp + 960 : pk + d->off[7],
+                              sp ? sp + 1024 : pk + d->off[9], buf[2], pk + d->chain3_off, sp ? sp + 1088 : pk + d->off[11],
+                              sp ? sp + 1216 : pk + d->off[13], mm, reinterpret_cast<int*>(range_flag), st, sp ? sp + 1344 : nullptr,
+                              head_gl ? 1 : 0);
       if (rc != MAGAT_OK) return rc;
       cur = 2; hin = Ho; win = Wo; lstart = 3; pooled_in = true;
     } else if (fused1 && d->chain_off > 0 && Ho == 6 && Wo == 6 && nblocks >= 2 && magat_opt(MAGAT_OPT_BLOCK_FUSED)) {

@@ -909,6 +909,9 @@ int csr_forward(const ST* X, const int* rowptr, const int* colidx, long long nnz
   if ((size_t)(2 * N + 2) * sizeof(int) > 64 * 1024) return MAGAT_ERR_UNSUPPORTED;   // transpose LDS (N <= 8190)
   const int width = concat ? P * F : F;
   if (ldy < width || (ldy & 3)) return MAGAT_ERR_BAD_SHAPE;
+  // X rows are read in 16-byte pieces (the maps GEMMs, the range guard's float32 re-run, the fused bf16 kernels): an X that is
+  // not on a 16-byte boundary is refused before anything is launched (magat_hip.h, "Alignment")
+  if (reinterpret_cast<uintptr_t>(X) & 15) return MAGAT_ERR_UNSUPPORTED;
   const bool have_csc = pre_cscptr && pre_cscsrc && pre_cscpos;     // made by magat_gso_csr_build (once per GSO)
   const WsLayout w = ws_layout(B, N, nnz, G, F, K, P, mode, concat, sizeof(ST), have_csc);
   if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255) || workspace_bytes < w.total)
@@ -930,7 +933,9 @@ int csr_forward(const ST* X, const int* rowptr, const int* colidx, long long nnz
                                                 packed + magat_gat_csr_fused_offset(L.NC, G), bias, Y, ldy, y_f32,
                                                 reinterpret_cast<float*>(ws + w.att), att_opt,
                                                 reinterpret_cast<int*>(ws + w.order), B, N, P, st);
-    // (MAGAT_ERR_UNSUPPORTED: result rows / bias not 16-byte aligned)
+    // (MAGAT_ERR_UNSUPPORTED before any launch: result rows / bias not 16-byte aligned, ldy not a multiple of 8 bf16 / 4 float32
+    //  elements - magat_hip.h "Alignment" (2); the workspace the caller sized for this form holds no maps, so there is no
+    //  fall-through to the unfused kernels)
   }
   int rc = csr_maps_gemm<ST>(X, packed, Z, B * N, G, L, stream, reinterpret_cast<int32_t*>(ws + w.status));
   if (rc != MAGAT_OK) return rc;

@@ -1387,6 +1387,10 @@ static int gat_forward_impl(const float* X, const void* S, int s_is_f64, const f
   if (G != F || !supported_width(G) || N > 128) return MAGAT_ERR_UNSUPPORTED;
   const int width = concat ? P * F : F;
   if (ldy < width || (ldy & 3)) return MAGAT_ERR_BAD_SHAPE;
+  // X rows are read in 16-byte pieces by every form (gat_small / gat_mid, the maps GEMMs and the range guard's float32 re-run
+  // behind gat_mfma and the two-launch form): an X that is not on a 16-byte boundary is refused before anything is launched
+  // (magat_hip.h, "Alignment")
+  if (reinterpret_cast<uintptr_t>(X) & 15) return MAGAT_ERR_UNSUPPORTED;
   if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255) ||
       workspace_bytes < magat_gat_workspace_bytes(B, N, G, F, K, P, mode, concat))
     return MAGAT_ERR_WORKSPACE;
@@ -1396,7 +1400,7 @@ static int gat_forward_impl(const float* X, const void* S, int s_is_f64, const f
   // as the range guard's float32 re-run; no attention tensor there (the CSR kernels serve such requests)
   const bool slim = lds > 160 * 1024;
   if (slim && !(G == 128 && F == 128 && mode == MAGAT_MODE_KEYQUERY && !A_opt && gat_one_launch(N, G, F, K, mode, concat) &&
-                (reinterpret_cast<uintptr_t>(Y) & 15) == 0 && (reinterpret_cast<uintptr_t>(X) & 15) == 0))
+                (reinterpret_cast<uintptr_t>(Y) & 15) == 0))
     return MAGAT_ERR_UNSUPPORTED;
   hipStream_t st = static_cast<hipStream_t>(stream);
 
@@ -1426,10 +1430,9 @@ static int gat_forward_impl(const float* X, const void* S, int s_is_f64, const f
   // One launch of matrix-core products (gat_mfma.hip) when the shape allows; with the range guard on, the two-launch float32
   // form below follows in the same stream, every launch of it predicated on the flag the fused kernel raises.
   bool rerun_only = false;
-  // (the one-launch kernel stores Y in 16-byte pieces: a column block at an odd offset of a wider buffer takes the two-launch form)
-  // ... and the small-graph kernel loads X rows as 16-byte pieces)
-  if (!A_opt && gat_one_launch(N, G, F, K, mode, concat) && (reinterpret_cast<uintptr_t>(Y) & 15) == 0 &&
-      (G == 128 || (reinterpret_cast<uintptr_t>(X) & 15) == 0)) {
+  // (the one-launch kernels store Y in 16-byte pieces: a column block at an odd offset of a wider buffer takes the two-launch
+  //  form - or, beyond its tiles, is refused above)
+  if (!A_opt && gat_one_launch(N, G, F, K, mode, concat) && (reinterpret_cast<uintptr_t>(Y) & 15) == 0) {
     const bool guard = magat_opt(MAGAT_OPT_RANGE_GUARD) != 0;
     const unsigned* masks = nullptr;
     const float* frag = packed + magat_gat_frag_offset(L.NC, G);
@@ -1450,8 +1453,7 @@ static int gat_forward_impl(const float* X, const void* S, int s_is_f64, const f
     if (rc != MAGAT_OK || !guard) return rc;
     rerun_only = true;
     p.run_if = status;
-    if (mode == MAGAT_MODE_KEYQUERY && (G == 32 || G == 64 || G == 128) && (long long)B * P <= GAT_RERUN_SMALL_UNITS &&
-        (reinterpret_cast<uintptr_t>(X) & 15) == 0) {
+    if (mode == MAGAT_MODE_KEYQUERY && (G == 32 || G == 64 || G == 128) && (long long)B * P <= GAT_RERUN_SMALL_UNITS) {
       // few instances: the whole float32 form as ONE predicated launch (final rows straight into Y, the guard's bookkeeping too)
       p.B = B; p.b0 = 0; p.Ymean = Y; p.ldym = ldy; p.book = reinterpret_cast<int*>(status);
       size_t slds = sizeof(float) * ((size_t)N * (G + 1) + (size_t)N * (N | 1));

@@ -476,7 +476,10 @@ int launch_mid(const GatMidParams& p, int concat, int slot, int slot_hs, hipStre
   if (hs) {
     const void* fh = concat ? reinterpret_cast<const void*>(&gat_mid_kernel<F, KT, NT, true, true, XR>)
                             : reinterpret_cast<const void*>(&gat_mid_kernel<F, KT, NT, false, true, XR>);
-    if (magat_ensure_dyn_lds(fh, slot_hs + (concat ? 0 : 1), lds) != MAGAT_OK) return MAGAT_ERR_LAUNCH;
+    if (magat_ensure_dyn_lds(fh, slot_hs + (concat ? 0 : 1), lds) != MAGAT_OK) {
+      magat_prof_end(pid, st);
+      return MAGAT_ERR_LAUNCH;
+    }
     const unsigned g = (unsigned)(p.B * p.P);
     if (concat) hipLaunchKernelGGL((gat_mid_kernel<F, KT, NT, true, true, XR>), dim3(g), dim3(64 * NT), lds, st, p);
     else {

@@ -301,6 +301,8 @@ def gat_forward_rows(X, S, layer, out=None, want_attention=False, csr=None):
     concat = 1 if layer.concatenate else 0
     width = P * F if concat else F
     X = X.contiguous()
+    if X.data_ptr() % 16:
+        X = X.clone()       # (every graph-layer entry point, dense or CSR, needs X on a 16-byte boundary: magat_hip.h "Alignment")
     bf16 = X.dtype == torch.bfloat16           # bf16 storage: always the CSR kernels (the LDS kernel is fp32-only)
     if X.dtype != torch.float32 and not bf16:
         X = X.float()

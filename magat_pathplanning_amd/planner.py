@@ -17,6 +17,7 @@ float32 matrix-core kernels); BatchNorm / ReLU / pooling and the MLPs train thro
 """
 import ctypes
 import hashlib
+import itertools
 import operator
 import os
 import types
@@ -58,6 +59,7 @@ from .train_cnn import convlayers_forward  # noqa: E402
 
 _DATA_PTR = torch.Tensor.data_ptr
 _VERSION = operator.attrgetter("_version")
+_chain = itertools.chain.from_iterable
 # Registration epoch: bumped whenever ANY module of the process registers a parameter, buffer or submodule (torch's global
 # registration hooks; `m.weight = nn.Parameter(..)` and `seq[0] = nn.Linear(..)` go through them) - what tells _weights_key that
 # its cached tensor list may no longer be the module tree's.  Without the hooks (an older torch) the list is re-derived per call.
@@ -181,7 +183,7 @@ class DecentralPlannerGATNet(nn.Module):
             self.actionsMLP = nn.Sequential(nn.Linear(width, numAction))
         self.apply(weights_init)
         self._rt = _Runtime()
-        self._flat, self._flat_age, self._flat_epoch = None, 0, -1     # cached tensor list of _weights_key
+        self._flat, self._seen, self._dicts, self._flat_age, self._flat_epoch = None, None, None, 0, -1     # cached lists of _weights_key
         # agent count the batch-size-dependent kernel forms are chosen on (0: each call's own); set around a shard's forward by
         # distributed.sharded_forward (magat_encoder_desc.form_agents)
         self.form_agents = 0
@@ -198,12 +200,13 @@ class DecentralPlannerGATNet(nn.Module):
         st["_rt"] = None
         st["S"] = None
         st["_flat"] = None
+        st["_dicts"] = st["_seen"] = None
         return st
 
     def __setstate__(self, st):
         super().__setstate__(st)
         self._rt = _Runtime()
-        self._flat, self._flat_age, self._flat_epoch = None, 0, -1
+        self._flat, self._seen, self._dicts, self._flat_age, self._flat_epoch = None, None, None, 0, -1
         self.__dict__.setdefault("_cal", None)       # (modules pickled before the calibration record existed)
         self.__dict__.setdefault("step_plan", True)
 
@@ -312,54 +315,60 @@ class DecentralPlannerGATNet(nn.Module):
         return self.actionsMLP(shared)
 
     # ------------------------------------------------------------------ inference path (HIP)
-    def _walk_tensors(self):
-        """Every parameter and buffer of the module tree, in a fixed walk order (an iterative walk over the module dicts:
-        nn.Module.parameters() / buffers() are recursive generators with a memo set, several times slower)."""
-        flat = []
+    def _walk_dicts(self):
+        """The non-empty _parameters and _buffers dicts of every module of the tree, in a fixed walk order (an iterative walk
+        over the module dicts: nn.Module.parameters() / buffers() are recursive generators with a memo set, several times
+        slower)."""
+        dicts = []
         stack = [self]
         while stack:
             m = stack.pop()
-            for t in m._parameters.values():
-                if t is not None:
-                    flat.append(t)
-            for t in m._buffers.values():
-                if t is not None:
-                    flat.append(t)
+            if m._parameters:
+                dicts.append(m._parameters)
+            if m._buffers:
+                dicts.append(m._buffers)
             for c in m._modules.values():
                 if c is not None:
                     stack.append(c)
-        return flat
+        return dicts
 
     def _weights_key(self, dev):
         """(device, addresses, versions) of every parameter and buffer of the module tree: what the folded / packed weights of
         the HIP path were made from.  It sits on the critical path of the closed-loop step (nothing can be launched before
-        it), so the tensors are visited through a cached flat list with two C-level maps (6 us instead of 18 for the ~70
-        tensors of the reference's model).  Changes under any of: load_state_dict / optimizer steps / in-place updates
-        (version), .to() / .data assignment (address), a replaced Parameter / buffer / submodule anywhere in the tree (the
-        registration epoch above: the list is re-derived).  The list is also re-derived on _apply() / load_state_dict()
-        (overridden below), after unpickling and on every 64th call (the backstop for surgery on the module dicts themselves:
-        `del m._parameters[..]`; `invalidate_weights()` makes the next forward see that at once)."""
-        flat = self._flat
+        it), so the tensors are read out of a cached list of the modules' _parameters / _buffers dicts with C-level maps.
+        Changes under any of: load_state_dict / optimizer steps / in-place updates (version), .to() / .data assignment
+        (address), a replaced Parameter / buffer anywhere in the tree - also one written straight into a module's dict, or
+        swapped by a submodule's own conversion under torch.__future__.set_overwrite_module_params_on_conversion: the dicts'
+        values are compared by identity with the cached tensor list on every call, and a new object has a new address (the
+        cached list keeps the old one alive until then).  The dict list is re-derived when a module registers a parameter,
+        buffer or submodule (the registration epoch above), on _apply() / load_state_dict() (overridden below), after
+        unpickling and on every 64th call (the backstop for surgery on the module dicts themselves - an entry added to a dict
+        that was empty, `del m._modules[..]`; `invalidate_weights()` makes the next forward see that at once)."""
         self._flat_age += 1
-        if flat is None or self._flat_epoch != _REG_EPOCH[0] or (self._flat_age & 63) == 0 or not _REG_HOOKED:
-            walked = self._walk_tensors()
+        if (self._dicts is None or self._flat_epoch != _REG_EPOCH[0] or (self._flat_age & 63) == 0 or
+                not _REG_HOOKED):
+            self._dicts = self._walk_dicts()
             self._flat_epoch = _REG_EPOCH[0]
-            if flat is None or len(walked) != len(flat) or any(a is not b for a, b in zip(walked, flat)):
-                flat = self._flat = walked
+        vals = tuple(_chain(map(dict.values, self._dicts)))
+        seen = self._seen
+        if seen is None or len(vals) != len(seen) or not all(map(operator.is_, vals, seen)):
+            self._seen = vals
+            self._flat = [t for t in vals if t is not None]
+        flat = self._flat
         return (dev, tuple(map(_DATA_PTR, flat)), tuple(map(_VERSION, flat)))
 
     def invalidate_weights(self):
         """Forget the cached tensor list and the folded weights: the next forward re-derives everything from the module tree."""
-        self._flat = None
+        self._flat = self._seen = self._dicts = None
         if self._rt is not None:
             self._rt.key = None
 
     def _apply(self, fn, *a, **kw):
-        self._flat = None
+        self._flat = self._seen = self._dicts = None
         return super()._apply(fn, *a, **kw)
 
     def load_state_dict(self, *a, **kw):
-        self._flat = None
+        self._flat = self._seen = self._dicts = None
         return super().load_state_dict(*a, **kw)
 
     def _refresh(self, dev):
@@ -662,6 +671,8 @@ class DecentralPlannerGATNet(nn.Module):
         try:
             stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
             rc = lib.magat_encoder_forward_f32(pl.desc_ref, ctypes.c_void_p(x.data_ptr()), *pl.enc_tail, stream)
+            if rc == -3:        # MAGAT_ERR_WORKSPACE: an option that sizes the encoder's workspace (LAT_AGENTS, ENC_CHUNK) changed
+                return None     # since the plan was built - the general path resizes it
             if rc:
                 nat.check(rc, "magat_encoder_forward_f32")
             layer.addGSO(S)
@@ -670,8 +681,9 @@ class DecentralPlannerGATNet(nn.Module):
             pl.act.out = out.data_ptr()
             rc = lib.magat_gat_forward_tail_f32(pl.gat_head, ctypes.c_void_p(S.data_ptr()), 1 if S.dtype == torch.float64 else 0,
                                                 *pl.gat_tail, pl.act_ref, pl.tail_done_ref, stream)
-            if rc == -2:        # MAGAT_ERR_UNSUPPORTED: a library option that decides the layer's route (GAT_MFMA, GAT_WIDE_FROM)
-                return None     # changed since the plan was built - the caller drops the plan and takes the general path
+            if rc in (-2, -3):  # MAGAT_ERR_UNSUPPORTED / _WORKSPACE: a library option that decides the layer's route (GAT_MFMA,
+                return None     # GAT_WIDE_FROM) or sizes its workspace (GAT_CHUNK_MB) changed since the plan was built - the caller
+                                # drops the plan and takes the general path, whose whole re-run (encoder included) is the result
             if rc:
                 nat.check(rc, "magat_gat_forward_tail_f32")
             layer.aij = None
@@ -849,7 +861,7 @@ class DecentralPlannerNet(DecentralPlannerGATNet):
             self.actionsMLP = nn.Sequential(nn.Linear(nif, numAction))
         self.apply(weights_init)
         self._rt = _Runtime()
-        self._flat, self._flat_age, self._flat_epoch = None, 0, -1
+        self._flat, self._seen, self._dicts, self._flat_age, self._flat_epoch = None, None, None, 0, -1
         self.step_plan = True
         self.form_agents = 0
         self._cal = None

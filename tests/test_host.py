@@ -377,3 +377,66 @@ def test_fragment_major_head_pack_holds_the_row_major_planes():
                     want = planes[pl][(32 * ct + (lane & 31)).view(64, 1), (k0 + 8 * (lane >> 5)).view(64, 1) + torch.arange(8).view(1, 8)]
                     assert torch.equal(blk[ct, s_, pl], want)
 
+
+
+def _swap_net():
+    import torch
+    from magat_pathplanning_amd import DecentralPlannerGATNet
+    from magat_pathplanning_amd.synthetic import make_config
+    cfg = make_config(num_agents=10, nGraphFilterTaps=2, nAttentionHeads=2, device="cpu")
+    return DecentralPlannerGATNet(cfg).eval(), torch.device("cpu")
+
+
+def test_weights_key_sees_a_parameter_replaced_in_the_module_dict():
+    """A Parameter written straight into a submodule's _parameters (no registration hook fires) changes the key at once: the
+    packed / folded weights of the HIP path are never reused for it."""
+    import torch
+    net, dev = _swap_net()
+    k0 = net._weights_key(dev)
+    assert net._weights_key(dev) == k0
+    lin = net.actionsMLP[0]
+    lin._parameters["weight"] = torch.nn.Parameter(lin.weight.detach() + 1)
+    assert net._weights_key(dev) != k0
+
+
+def test_weights_key_sees_a_submodule_conversion_that_overwrites_parameters():
+    """torch.__future__.set_overwrite_module_params_on_conversion(True): a SUBMODULE's .double().float() replaces its Parameter
+    objects without passing through the planner's own _apply - the key changes at once."""
+    import torch
+    net, dev = _swap_net()
+    k0 = net._weights_key(dev)
+    prev = torch.__future__.get_overwrite_module_params_on_conversion()
+    torch.__future__.set_overwrite_module_params_on_conversion(True)
+    try:
+        net.compressMLP.double().float()
+    finally:
+        torch.__future__.set_overwrite_module_params_on_conversion(prev)
+    assert net._weights_key(dev) != k0
+
+
+def test_header_states_the_alignment_rule_of_every_graph_layer_entry():
+    """Every graph-layer entry point the ABI tests drive (tests/test_gpu_abi_contract.py) is named in the header's alignment
+    paragraph, which states the X rule, the ldy rule, the column-block rule and its one exception."""
+    import re
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    text = open(os.path.join(root, "include", "magat_hip.h")).read()
+    m = re.search(r"\* Alignment \(every graph-layer entry point: (.*?)\*/", text, flags=re.S)
+    assert m, "magat_hip.h: no 'Alignment' paragraph in the graph layer section"
+    para = " ".join(line.strip(" *") for line in m.group(1).splitlines())
+    names = set()
+    for stem, alts, suffix in re.findall(r"(magat_\w+?_)\{([\w,]+)\}(\w*)", para):
+        names.update(stem + a + suffix for a in alts.split(","))
+    names.update(re.findall(r"magat_\w+_f32\b", para))
+    for entry in ("magat_gat_forward_packed_f32", "magat_gat_forward_planned_f32", "magat_gat_forward_tail_f32",
+                  "magat_gat_forward_dense_f32", "magat_gat_forward_csr_f32", "magat_gat_forward_csr_bf16",
+                  "magat_gat_forward_csc_f32", "magat_gat_forward_csc_bf16", "magat_gat_forward_csc_bf16_f32out",
+                  "magat_gnn_forward_csr_f32"):
+        assert entry in names, entry
+        assert re.search(r"\b%s\s*\(" % entry, text), entry          # (and it is declared)
+    for rule in ("16-byte boundary", "MAGAT_ERR_UNSUPPORTED", "ldy must be a multiple of 4", "odd column offset",
+                 "before anything is launched", "two exceptions", "106 .. 128 agents",
+                 # the fused bf16 CSC form (gat_csr_fused.hip) and the rules tests/test_gpu_abi_contract.py asserts for it
+                 "magat_gat_forward_csc_bf16 and magat_gat_forward_csc_bf16_f32out in their fused form", "CSR_FUSED",
+                 "KeyQuery, K = 2, G = F = 128, concat, P in {1, 2, 4}", "Y and bias on a 16-byte boundary",
+                 "ldy a multiple of 8 for bf16 rows (4 for float32 rows)", "magat_gat_forward_csr_bf16 takes that shape at any Y"):
+        assert rule in para, rule
