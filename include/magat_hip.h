@@ -106,7 +106,7 @@ int magat_reset_option(const char* name);   /* back to the value the process sta
  *    actionsMLP consumes, …bottleneck.py:331).  ldy = row stride of Y in floats (>= width),
  *    so Y may be a column block of a wider skip-concat buffer.
  * Alignment (every graph-layer entry point: magat_gat_forward_{packed,planned,tail,dense}_f32, magat_gat_forward_csr_{f32,bf16},
- *    magat_gat_forward_csc_{f32,bf16,bf16_f32out}, magat_gnn_forward_csr_f32): X must start on a 16-byte boundary - otherwise
+ *    magat_gat_forward_csc_{f32,bf16,bf16_f32out}, magat_gnn_forward_csr_f32, magat_gnn_forward_dense_f32): X must start on a 16-byte boundary - otherwise
  *    MAGAT_ERR_UNSUPPORTED before anything is launched (its rows are read in 16-byte pieces).  ldy must be a multiple of 4
  *    (MAGAT_ERR_BAD_SHAPE).  Y may start anywhere a float (bf16: an element) may, a column block at an odd column offset
  *    included - with two exceptions, each answered with MAGAT_ERR_UNSUPPORTED before anything is launched:
@@ -174,6 +174,20 @@ int magat_gat_forward_csr_f32(const float* X, const int* rowptr, const int* coli
 int magat_gnn_forward_csr_f32(const float* X, const int* rowptr, const int* colidx, const float* vals, long long nnz,
                               const float* packed, const float* bias, float* Y, int ldy, void* workspace,
                               size_t workspace_bytes, int B, int N, int G, int F, int K, void* stream);
+/* GraphFilterBatch.forward on a DENSE GSO in one launch (gnn_dense.hip; profiling tag MAGAT_TAG_GNN_DENSE, form
+ * MAGAT_FORM_GNN_DENSE): the graph layer of the bottleneck GNN planners, with their ReLU fused (relu != 0).
+ *   Y[b,n,f] = act(bias[f] + sum_k sum_g (x S^k)[g,n] h[f,0,k,g])   (graphML.py:5485-5579; x @ S.float() as :5562)
+ * X [B*Nin][ldx] float32 rows (the encoder's compressMLP output).  S [B][N][N] float32 or float64 (s_is_f64), exactly as
+ * addGSO left it; a float64 entry is rounded to float32 to nearest even.  S is a plain dense operand: every entry is
+ * multiplied in, zeros included, so a NaN entry propagates as through the reference's matmul (no edge rule, no scrub).
+ * weight: the RAW taps (F,1,K,G) float32 contiguous (no packing, no workspace); bias [F] or NULL.
+ * Nin <= N agents: rows Nin..N-1 of the signal are the reference's zero padding (graphML.py:5675-5680) and only the Nin
+ * rows of each instance are written (Y [B*Nin][ldy]).  Arithmetic: true float32 FMA chains in the Horner form on F-wide rows,
+ * acc = U_{K-1}; acc = S^T acc + U_k (U_k = X H_k^T), one workgroup per (instance, 16 | 32-column slice of F).
+ * Supported: 1 <= N <= 128, G, F in {16, 32, 64, 128} (G != F allowed), 1 <= K <= 8; any other shape returns
+ * MAGAT_ERR_UNSUPPORTED before anything is launched (the caller then takes magat_gnn_forward_csr_f32). */
+int magat_gnn_forward_dense_f32(const float* X, int ldx, const void* S, int s_is_f64, const float* weight, const float* bias,
+                                float* Y, int ldy, int B, int N, int Nin, int G, int F, int K, int relu, void* stream);
 /* bf16-STORAGE variant (BASELINE config 5: "1000 agents, CSR, bf16"; SURVEY.md 8(b) `..._csr_{f32,bf16}`): X, the hoisted
  * maps Z, the hop intermediates and Y are bf16 in HBM (raw uint16 bit patterns, RNE), all arithmetic accumulates in
  * fp32 (bf16 MFMA for the maps GEMM with the RNE-bf16 plane of the packed weights; fp32 scores / softmax / gathers),
@@ -633,7 +647,8 @@ int magat_encoder_forward_f32(const magat_encoder_desc* desc_host, const float* 
 #define MAGAT_TAG_BLOCK3 22       /* layer3 + ReLU + 2x2 pool in one launch (block_fused.hip) */
 #define MAGAT_TAG_BLOCK_FULL 23   /* layer1.conv2 -> layer2 -> layer3 -> pool in one launch (block_fused.hip) */
 #define MAGAT_TAG_CONV_WGRAD 24   /* weight gradient of a convolution (conv_train.hip; training) */
-#define MAGAT_PROF_TAGS 25
+#define MAGAT_TAG_GNN_DENSE 25    /* GraphFilterBatch on a dense GSO in one launch (gnn_dense.hip) */
+#define MAGAT_PROF_TAGS 26
 int magat_gat_set_debug_buffer(long long* dev_buf); /* [grid][8] int64 phase timestamps of gat_dense_kernel; NULL = off */
 int magat_profile_reserve(int spans);   /* pre-create event pairs (keeps hipEventCreate out of a timed region) */
 int magat_profile_enable(int on);
@@ -667,7 +682,8 @@ int magat_mfma_sustained_f16_ex(double* tflops, double* clock_mhz, double* per_c
 #define MAGAT_FORM_GUARD_LAT 12   /* ... and the encoder's range guard inside the same launch (no predicated launches behind it) */
 #define MAGAT_FORM_STEM_LAT 13    /* ... and the stem + layer1.conv1 in front: the whole encoder of a few-agent call is ONE launch */
 #define MAGAT_FORM_ACTIONS_TAIL 14 /* the action head inside the graph layer's predicated re-run launch (magat_gat_forward_tail_f32) */
-#define MAGAT_FORMS 15
+#define MAGAT_FORM_GNN_DENSE 15   /* the GNN graph filter as one dense launch (magat_gnn_forward_dense_f32) */
+#define MAGAT_FORMS 16
 long long magat_form_count(int id);
 int magat_form_reset(void);
 

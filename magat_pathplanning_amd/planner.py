@@ -953,3 +953,180 @@ class DecentralPlannerNet(DecentralPlannerGATNet):
             if not self.no_relu:
                 rows = torch.relu_(rows)
             return self._run_actions(rt, feat, comp, rows, rows, M, dev, stream)
+
+
+_BOTTLENECK_GNN_FILES = {
+    "BottomNeck_only": "only",                    # graphs/models/decentralplanner_bottleneck.py
+    "BottomNeck_skipConcat": "skipConcat",        # ..._bottleneck_SkipConcat.py
+    "BottomNeck_skipConcatGNN": "skipConcatGNN",  # ..._bottleneck_SkipConcatGNN.py
+    "BottomNeck_skipAddGNN": "skipAddGNN",        # ..._bottleneck_SkipAddGNN.py
+}
+
+
+class DecentralPlannerBottleneckNet(DecentralPlannerNet):
+    """Drop-in for the `DecentralPlannerNet` class of the reference's bottleneck GNN files
+    graphs/models/decentralplanner_bottleneck{,_SkipConcat,_SkipConcatGNN,_SkipAddGNN}.py, selected by config.bottleneckMode
+    exactly like agents/decentralplannerlocal_OnlineExpert.py:63-80 selects the file (decentralplanner.py, the fall-back
+    there, is DecentralPlannerNet).  The per-agent CNN (every CNN_mode the files accept; config.use_dilated is not read), a
+    compressMLP to config.bottleneckFeature + ReLU, ONE GraphFilterBatch(bf, bf, K) followed by a ReLU that nothing switches
+    off (GFL.0 / GFL.1), and the action MLP on the graph layer's rows - or on [CNN feature map | rows] (skipConcat) or
+    [compressMLP output | rows] (skipConcatGNN).  addGSO aliases the caller's tensor; only BottomNeck_only scrubs NaN.
+
+    Inference (eval / no_grad, device tensors): the HIP encoder, the graph layer + its ReLU as ONE launch of the dense
+    kernel (magat_gnn_forward_dense_f32, N <= 128) and the action head with the skip source as a second K segment - no host
+    synchronisation after the first call with a given set of weights, so the step can be captured in a CUDA graph.  Larger
+    graphs (or a shape the dense kernel refuses) take GraphFilterBatch's CSR route.  Training: the same differentiable path
+    as DecentralPlannerNet (_GnnTrainFunction, convlayers_forward) with the skip concatenation in torch."""
+
+    def __init__(self, config):
+        nn.Module.__init__(self)
+        from .graphml import GraphFilterBatch
+        mode_name = getattr(config, "bottleneckMode", None)
+        if mode_name not in _BOTTLENECK_GNN_FILES:
+            raise ValueError("DecentralPlannerBottleneckNet reproduces the bottleneck GNN files (bottleneckMode in %s); "
+                             "bottleneckMode %r selects graphs/models/decentralplanner.py: use DecentralPlannerNet"
+                             % (sorted(_BOTTLENECK_GNN_FILES), mode_name))
+        self.config = config
+        self.S = None
+        self.numAgents = config.num_agents
+        self.dilated_version = 0
+        self.skip = _BOTTLENECK_GNN_FILES[mode_name]
+        inW = inH = config.FOV + 2
+        numAction = 5
+        bf = config.bottleneckFeature
+        mode = config.CNN_mode
+        self.cnn_mode = mode
+        if mode in ("ResNetSlim_withMLP", "ResNetLarge_withMLP"):
+            body = ResNetSlim() if "Slim" in mode else ResNet()
+            self.ConvLayers = nn.Sequential(body, nn.Dropout(0.2), nn.Flatten(),
+                                            nn.Linear(1152, config.numInputFeatures, bias=True))
+            numFeatureMap = config.numInputFeatures
+        elif mode in ("ResNetSlim", "ResNetLarge"):
+            body = ResNetSlim() if "Slim" in mode else ResNet()
+            self.ConvLayers = nn.Sequential(body, nn.Dropout(0.2))
+            numFeatureMap = 1152
+        else:
+            chans = [3, 32, 32, 64, 64, 128]
+            layers, w, h = [], inW, inH
+            for l in range(5):
+                layers += [nn.Conv2d(chans[l], chans[l + 1], 3, 1, 1, bias=True), nn.BatchNorm2d(chans[l + 1]),
+                           nn.ReLU(inplace=True)]
+                if l % 2 == 0:
+                    layers.append(nn.MaxPool2d(kernel_size=2))
+                    w, h = (w - 2) // 2 + 1, (h - 2) // 2 + 1
+            self.ConvLayers = nn.Sequential(*layers)
+            numFeatureMap = chans[-1] * w * h
+            self.cnn_mode = "Default"
+        self.numFeatureMap = numFeatureMap
+        self.compressMLP = nn.Sequential(nn.Linear(numFeatureMap, bf, bias=True), nn.ReLU(inplace=True))
+        self.numFeatures2Share = bf
+        self.L = 1
+        self.F = [bf, bf]
+        self.K = [config.nGraphFilterTaps]
+        self.E = 1
+        self.bias = True
+        self.GFL = nn.Sequential(GraphFilterBatch(bf, bf, self.K[0], self.E, self.bias), nn.ReLU(inplace=True))
+        self.no_relu = False
+        self.gat_width = bf
+        width = bf + {"skipConcat": numFeatureMap, "skipConcatGNN": bf}.get(self.skip, 0)
+        if config.use_dropout:
+            self.actionsMLP = nn.Sequential(nn.Linear(width, config.numInputFeatures), nn.ReLU(inplace=True),
+                                            nn.Dropout(p=0.2), nn.Linear(config.numInputFeatures, numAction),
+                                            nn.Dropout(p=0.2))
+        else:
+            self.actionsMLP = nn.Sequential(nn.Linear(width, numAction))
+        self.apply(weights_init)
+        self._rt = _Runtime()
+        self._flat, self._seen, self._dicts, self._flat_age, self._flat_epoch = None, None, None, 0, -1
+        self.step_plan = True
+        self.form_agents = 0
+        self._cal = None
+
+    def addGSO(self, S):
+        """decentralplanner_bottleneck*.py:262-278: aliases the caller's tensor; NaN scrubbed in place by
+        decentralplanner_bottleneck.py (BottomNeck_only) alone; dist_GSO_one / full_GSO in every file."""
+        assert len(S.shape) == 3
+        scrub = self.skip == "only"
+        gso_mode = {"dist_GSO_one": 1, "full_GSO": 2}.get(self.config.GSO_mode, 0)
+        if S.is_cuda and S.is_contiguous() and S.dtype in (torch.float32, torch.float64) and gso_mode != 2:
+            if (scrub or gso_mode) and S.numel() > 0:
+                with torch.cuda.device(S.device):
+                    nat.check(nat.lib().magat_gso_prepare(nat.ptr(S), 1 if S.dtype == torch.float64 else 0, S.numel(),
+                                                          1 if scrub else 0, gso_mode, nat.current_stream(S.device)),
+                              "magat_gso_prepare")
+            self.S = S.unsqueeze(1)
+            return
+        self.S = S.unsqueeze(1)
+        if scrub:
+            self.S[torch.isnan(self.S)] = 0
+        if gso_mode == 1:
+            self.S[self.S > 0] = 1
+        elif gso_mode == 2:
+            self.S = torch.ones_like(self.S).to(self.config.device)
+
+    def _check_forward(self):
+        if self.skip == "skipAddGNN":
+            # the reference builds this model, but its forward calls torch.cat(compressfeature, sharedFeature_stack) -
+            # a tensor where torch.cat wants a sequence - and raises (decentralplanner_bottleneck_SkipAddGNN.py:311)
+            raise TypeError("BottomNeck_skipAddGNN: the reference's forward raises at "
+                            "decentralplanner_bottleneck_SkipAddGNN.py:311 (torch.cat(compressfeature, sharedFeature_stack): "
+                            "cat() expects a sequence of tensors); construction and load_state_dict work, forward does not")
+
+    def forward(self, inputTensor):
+        self._check_forward()
+        return super().forward(inputTensor)
+
+    def _forward_autograd(self, x, B, N):
+        feat = convlayers_forward(self.ConvLayers, x)       # (ResNet trunks: HIP convolution kernels, train_cnn.py)
+        feat = feat.view(feat.size(0), -1)
+        comp = self.compressMLP(feat)
+        xg = comp.reshape(B, N, self.numFeatures2Share).permute(0, 2, 1)
+        self.GFL[0].addGSO(self.S)
+        shared = self.GFL(xg)
+        shared = shared.permute(0, 2, 1).reshape(B * N, shared.shape[1])
+        if self.skip == "skipConcat":
+            shared = torch.cat((feat, shared), dim=1)
+        elif self.skip == "skipConcatGNN":
+            shared = torch.cat((comp, shared), dim=1)
+        return self.actionsMLP(shared)
+
+    @torch.no_grad()
+    def _forward_hip(self, x, B, N):
+        if not x.is_cuda:
+            raise nat.MagatNativeError("inference runs on the HIP path only; config.device=%r is not a GPU "
+                                       "(no CPU fallback)" % (self.config.device,))
+        dev = x.device
+        M = B * N
+        rt = self._refresh(dev)
+        x = x.contiguous().float()
+        G = self.numFeatures2Share
+        layer = self.GFL[0]
+        with torch.cuda.device(dev):
+            stream = nat.current_stream(dev)
+            feat, comp = self._run_encoder(rt, x, M, dev, stream)
+            S = self.S
+            Ns = S.shape[-1]
+            if S.shape[0] != B or Ns < N:
+                raise RuntimeError("DecentralPlannerBottleneckNet: GSO of shape %s does not match a batch of %d instances x "
+                                   "%d agents" % (tuple(S.shape), B, N))
+            rows = self._buf("gat", (M, self.gat_width), dev)
+            S3 = S.reshape(B, Ns, Ns)
+            if S3.device != dev or S3.dtype not in (torch.float32, torch.float64) or not S3.is_contiguous():
+                S3 = S3.to(dev, torch.float32 if S3.dtype not in (torch.float32, torch.float64) else S3.dtype).contiguous()
+            w = layer.weight.detach().to(dev, torch.float32).contiguous()
+            b = None if layer.bias is None else layer.bias.detach().to(dev, torch.float32).contiguous()
+            # graph layer + its ReLU (GFL.1) in one launch: no CSR structure, no host round trip
+            rc = nat.lib().magat_gnn_forward_dense_f32(nat.ptr(comp), comp.stride(0), nat.ptr(S3),
+                                                       1 if S3.dtype == torch.float64 else 0, nat.ptr(w), nat.ptr(b),
+                                                       nat.ptr(rows), rows.stride(0), B, Ns, N, G, layer.F, layer.K, 1, stream)
+            if rc == -2:
+                # MAGAT_ERR_UNSUPPORTED (N > 128, or a width / tap count the dense kernel does not cover): GraphFilterBatch's
+                # CSR route; the layer's own forward zero-pads the signal to the GSO's size and trims its output
+                layer.addGSO(S)
+                xg = comp.view(B, N, G).permute(0, 2, 1)
+                y = layer._forward_hip(xg)[0] if Ns == N else layer(xg)
+                rows = torch.relu_(y.permute(0, 2, 1).reshape(M, self.gat_width))
+            else:
+                nat.check(rc, "magat_gnn_forward_dense_f32")
+                layer.addGSO(S)
+            return self._run_actions(rt, feat, comp, rows, rows, M, dev, stream)
