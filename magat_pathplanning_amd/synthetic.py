@@ -31,7 +31,7 @@ def fov_states(B, N, seed=1337, fov=9):
 
 
 def calibration_states(fov=9, agents=2048, seed=0):
-    """The CANONICAL calibration batch of the split arithmetic's activation scales (planner._calibrate): `agents` state
+    """The CANONICAL calibration batch of the split arithmetic's activation scales (planner._ensure_calibrated): `agents` state
     tensors (agents, 3, fov+2, fov+2) that depend on nothing but (fov, agents, seed) - every process that holds the same
     weights measures the same layer magnitudes from it, whatever batch or shard it is given first.  Same three binary
     channels as fov_states (obstacles / goal / neighbouring agents, AgentState.toInputTensor 'Project_G':
