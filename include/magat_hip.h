@@ -248,6 +248,35 @@ int magat_sim_connect_radius(const int32_t* pos, double comm_radius, double* rad
 int magat_sim_fov_states(const uint8_t* map, int map_batched, int H, int W, const int32_t* pos, const int32_t* goal,
                          float* x, int FOV, int B, int N, void* stream);
 
+/* magat_sim_guided_states: AgentState.toInputTensor for the A*-guided encodings (dataloader/statetransformer_Guidance.py:
+ *   241-495; config.guidance = LocalG_S|SD, GlobalG_S|SD, SemiLG_S|SD), bit-exact: same arguments and output layout as
+ *   magat_sim_fov_states, channel 1 = the cells of the reference's A* path (offlineExpert/a_star.py:75-189, reproduced step
+ *   for step: 4-connected, moves up / left / down / right, Manhattan heuristic, pop = lexicographic minimum of (f, g, row,
+ *   col), a cell is closed when pushed and keeps its first pusher as parent; no path = the start cell alone).
+ *     mode MAGAT_GUIDE_LOCAL:  search inside the agent's own (FOV+2)^2 window (free border ring); channel 1 also holds the
+ *       (projected) goal cell.  dynamic_obstacles = 0 ('_S'): the other agents are no obstacles AND channel 2 is all zero,
+ *       as in the reference; 1 ('_SD'): agents in the window block, channel 2 as magat_sim_fov_states.
+ *     mode MAGAT_GUIDE_GLOBAL: search on the whole map padded by FOV/2 obstacle cells and a free one-cell ring; the agents
+ *       inside this agent's FOV block when dynamic_obstacles; a goal cell of value 1 is cleared; channel 1 = the path cells
+ *       that fall into the agent's window.
+ *     mode MAGAT_GUIDE_SEMI:   as GLOBAL on the map the agent has seen so far: agent_view [B][N][H+2(FOV/2)][W+2(FOV/2)]
+ *       uint8, caller-owned, zero at the start of an episode, updated IN PLACE (the current FOV crop is written before the
+ *       search); agents in the FOV always block (dynamic_obstacles is not read).  agent_view is NULL for the other modes.
+ *   One launch, one wavefront per agent, open list / closed bits / parents in LDS (sized for every cell of the canvas: the
+ *   open list cannot overflow), no workspace, no host synchronisation.  Limits, answered with MAGAT_ERR_UNSUPPORTED before
+ *   anything is launched: odd FOV, 3 <= FOV <= 29; GLOBAL / SEMI: H + 2(FOV/2) + 2 <= 64 and W + 2(FOV/2) + 2 <= 64 (FOV 9:
+ *   maps up to 54 x 54); LOCAL: any map.  The whole path is drawn (the reference raises IndexError beyond its
+ *   max_localPath cells).  An agent whose position or goal lies outside the map (no such case in the reference) is not
+ *   searched: its channel 1 holds the goal marker alone (LOCAL) or nothing.
+ *   Profiling tag 26 ("sim_guided"), form counter 16 - numbered in the library, MAGAT_PROF_TAGS / MAGAT_FORMS below are
+ *   unchanged. */
+#define MAGAT_GUIDE_LOCAL 1
+#define MAGAT_GUIDE_GLOBAL 2
+#define MAGAT_GUIDE_SEMI 3
+int magat_sim_guided_states(const uint8_t* map, int map_batched, int H, int W, const int32_t* pos, const int32_t* goal,
+                            float* x, int FOV, int B, int N, int mode, int dynamic_obstacles, uint8_t* agent_view,
+                            void* stream);
+
 /* magat_sim_move: multiRobotSimNew.move + check_collision (utils/new_simulator.py:334-454, 471-520),
  *   batched: action key = argmax of the 5 logits (convectToActionKey_softmax :863-869; or given keys `actions_in`), proposed
  *   move (up 0, left 1, down 2, right 3, stop 4), shielding in the reference's order - out of the arena, face-to-face

@@ -2,5 +2,7 @@
 DecentralPlannerGATNet / GraphFilterBatchAttentional).  See DESIGN.md and INTEGRATION.md."""
 from .graphml import GraphFilterBatch, GraphFilterBatchAttentional, GraphFilterBatchAttentional_Origin  # noqa: F401
 from .planner import DecentralPlannerBottleneckNet, DecentralPlannerGATNet, DecentralPlannerNet  # noqa: F401
+from .simulator import GUIDANCE_MODES, BatchedEpisode, batched_fov_states, batched_gso, new_agent_view  # noqa: F401
 
-__all__ = ["DecentralPlannerGATNet", "DecentralPlannerNet", "DecentralPlannerBottleneckNet", "GraphFilterBatchAttentional", "GraphFilterBatchAttentional_Origin", "GraphFilterBatch"]
+__all__ = ["DecentralPlannerGATNet", "DecentralPlannerNet", "DecentralPlannerBottleneckNet", "GraphFilterBatchAttentional", "GraphFilterBatchAttentional_Origin", "GraphFilterBatch",
+           "BatchedEpisode", "batched_fov_states", "batched_gso", "new_agent_view", "GUIDANCE_MODES"]

@@ -9,13 +9,14 @@ step, in numpy on the host right before the model call -
 
     S = batched_gso(pos, config.commR)                   # (B,N,N), what model.addGSO() takes
     x = batched_fov_states(obstacle_map, pos, goal, 9)   # (B,N,3,11,11), what model.forward() takes
+    x = batched_fov_states(obstacle_map, pos, goal, 9, guidance="GlobalG_SD")      # config.guidance: the A*-guided encodings
 
 and the step behind it (multiRobotSimNew.move, :471-549) with the episode state on the device:
 
     ep = BatchedEpisode(obstacle_map, pos, goal, maxstep, comm_radius=config.commR, action_select='exp_multinorm')
     S = ep.gso(); x = ep.states(); done = ep.step(logits)        # radius grown at step 0 like the reference
 
-HIP only (csrc/sim_frontend.hip): CPU tensors raise MagatNativeError."""
+HIP only (csrc/sim_frontend.hip, csrc/sim_guidance.hip): CPU tensors raise MagatNativeError."""
 import torch
 
 from . import _native as nat
@@ -76,9 +77,34 @@ def batched_gso(pos, comm_radius, symmetric_norm=False, normalize=True, dtype=to
     return (S, lam) if return_lambda else S
 
 
-def batched_fov_states(obstacle_map, pos, goal, FOV=9):
+# config.guidance -> (MAGAT_GUIDE_* mode, dynamic obstacles); 'Project_G' is magat_sim_fov_states
+GUIDANCE_MODES = {"Project_G": None,
+                  "LocalG_S": (nat.GUIDE_LOCAL, 0), "LocalG_SD": (nat.GUIDE_LOCAL, 1),
+                  "GlobalG_S": (nat.GUIDE_GLOBAL, 0), "GlobalG_SD": (nat.GUIDE_GLOBAL, 1),
+                  "SemiLG_S": (nat.GUIDE_SEMI, 0), "SemiLG_SD": (nat.GUIDE_SEMI, 1)}
+
+
+def new_agent_view(B, N, H, W, FOV=9, device="cuda"):
+    """The per-agent map memory of guidance 'SemiLG_*' at the start of an episode (AgentState.setmap: all unknown = free):
+    (B, N, H + 2 (FOV // 2), W + 2 (FOV // 2)) uint8 zeros.  batched_fov_states updates it in place."""
+    half = int(FOV) // 2
+    return torch.zeros(B, N, H + 2 * half, W + 2 * half, dtype=torch.uint8, device=device)
+
+
+def batched_fov_states(obstacle_map, pos, goal, FOV=9, guidance="Project_G", agent_view=None):
     """obstacle_map (H,W) or (B,H,W) uint8/bool device tensor (non-zero = obstacle), pos / goal (B,N,2) integer
-    (row, col) -> x (B,N,3,FOV+2,FOV+2) float32, identical to stacking AgentState.toInputTensor over the instances."""
+    (row, col) -> x (B,N,3,FOV+2,FOV+2) float32, identical to stacking AgentState.toInputTensor over the instances.
+
+    guidance = config.guidance of the reference: 'Project_G' (default: channel 1 is the goal or its projection onto the window's
+    border), or the A*-guided encodings whose channel 1 is the reference's A* path, cell for cell (csrc/sim_guidance.hip, one
+    launch): 'LocalG_S' / 'LocalG_SD' search the agent's own window, 'GlobalG_S' / 'GlobalG_SD' the whole padded map,
+    'SemiLG_S' / 'SemiLG_SD' the map the agent has seen so far - `agent_view` (new_agent_view(...)), a caller-owned uint8
+    tensor (B, N, H + 2 (FOV // 2), W + 2 (FOV // 2)) that the call updates IN PLACE.  '_SD' counts the agents inside the FOV
+    as obstacles.  GlobalG / SemiLG take maps up to 54 x 54 at FOV 9 (a 64 x 64 search canvas; larger maps raise
+    MagatNativeError, nothing is launched).  The whole path is drawn: the reference itself raises IndexError once a path is longer
+    than its max_localPath (4 (FOV + 2) cells for LocalG, rows + columns of the padded map otherwise)."""
+    if guidance not in GUIDANCE_MODES:
+        raise ValueError("guidance must be one of %s, got %r" % (sorted(GUIDANCE_MODES), guidance))
     pos, goal = _dev_i32(pos, "pos"), _dev_i32(goal, "goal")
     if not isinstance(obstacle_map, torch.Tensor) or not obstacle_map.is_cuda:
         raise nat.MagatNativeError("obstacle_map must be a device tensor (no CPU fallback)")
@@ -88,11 +114,26 @@ def batched_fov_states(obstacle_map, pos, goal, FOV=9):
     batched = m.dim() == 3
     assert m.dim() in (2, 3) and (not batched or m.shape[0] == B)
     H, W = m.shape[-2], m.shape[-1]
+    guided = GUIDANCE_MODES[guidance]
+    if guided is not None and guided[0] == nat.GUIDE_SEMI:
+        half = int(FOV) // 2
+        if agent_view is None:
+            raise ValueError("guidance %r needs agent_view (new_agent_view(B, N, H, W, FOV))" % guidance)
+        if (not isinstance(agent_view, torch.Tensor) or not agent_view.is_cuda or agent_view.dtype != torch.uint8
+                or not agent_view.is_contiguous() or tuple(agent_view.shape) != (B, N, H + 2 * half, W + 2 * half)):
+            raise nat.MagatNativeError("agent_view must be a contiguous uint8 device tensor of shape %s (it is updated in "
+                                       "place)" % ((B, N, H + 2 * half, W + 2 * half),))
     x = torch.empty(B, N, 3, FOV + 2, FOV + 2, dtype=torch.float32, device=pos.device)
     with torch.cuda.device(pos.device):
-        nat.check(nat.lib().magat_sim_fov_states(nat.ptr(m), 1 if batched else 0, H, W, nat.ptr(pos), nat.ptr(goal),
-                                                 nat.ptr(x), FOV, B, N, nat.current_stream(pos.device)),
-                  "magat_sim_fov_states")
+        if guided is None:
+            nat.check(nat.lib().magat_sim_fov_states(nat.ptr(m), 1 if batched else 0, H, W, nat.ptr(pos), nat.ptr(goal),
+                                                     nat.ptr(x), FOV, B, N, nat.current_stream(pos.device)),
+                      "magat_sim_fov_states")
+        else:
+            nat.check(nat.lib().magat_sim_guided_states(nat.ptr(m), 1 if batched else 0, H, W, nat.ptr(pos), nat.ptr(goal),
+                                                        nat.ptr(x), FOV, B, N, guided[0], guided[1],
+                                                        nat.ptr(agent_view) if guided[0] == nat.GUIDE_SEMI else None,
+                                                        nat.current_stream(pos.device)), "magat_sim_guided_states")
     return x
 
 
@@ -138,9 +179,11 @@ class BatchedEpisode:
     torch.Generator; seeded runs repeat exactly) - one float64 uniform per agent and step, inverse CDF on the device."""
 
     def __init__(self, obstacle_map, pos, goal, maxstep, comm_radius, action_select="soft_max", symmetric_norm=False,
-                 FOV=9, generator=None):
+                 FOV=9, generator=None, guidance="Project_G"):
         if action_select not in POLICIES:
             raise ValueError("action_select must be one of %s" % sorted(POLICIES))
+        if guidance not in GUIDANCE_MODES:
+            raise ValueError("guidance must be one of %s, got %r" % (sorted(GUIDANCE_MODES), guidance))
         self.pos = _dev_i32(pos, "pos").clone()
         self.goal = _dev_i32(goal, "goal")
         if not isinstance(obstacle_map, torch.Tensor) or not obstacle_map.is_cuda:
@@ -153,6 +196,12 @@ class BatchedEpisode:
         self.maxstep = int(maxstep)
         self.comm_radius, self.symmetric_norm, self.FOV = float(comm_radius), bool(symmetric_norm), int(FOV)
         self.generator = generator
+        self.guidance = guidance
+        # 'SemiLG_*': what every agent has seen so far, empty at the start of the episode (AgentState.setmap, once per episode in
+        # multiRobotSimNew.setup) and owned by the episode
+        self.agent_view = None
+        if guidance.startswith("SemiLG"):
+            self.agent_view = new_agent_view(B, N, self.map.shape[-2], self.map.shape[-1], self.FOV, dev)
         self.currentstep = 0
         self.radii = None
         self.reach_goal = torch.zeros(B, N, dtype=torch.uint8, device=dev)
@@ -178,7 +227,7 @@ class BatchedEpisode:
         return batched_gso(self.pos, self.radii, symmetric_norm=self.symmetric_norm, dtype=dtype)
 
     def states(self):
-        return batched_fov_states(self.map, self.pos, self.goal, self.FOV)
+        return batched_fov_states(self.map, self.pos, self.goal, self.FOV, self.guidance, self.agent_view)
 
     def step(self, logits=None, actions=None, uniforms=None):
         """move(actionVec, currentstep) for every instance; returns `done` (B,) int32 = allReachGoal as the reference
