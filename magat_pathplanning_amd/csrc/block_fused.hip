@@ -127,11 +127,11 @@ __device__ __forceinline__ void epi_to_lds(char* lds, int out_off, const int (&t
       for (int e = 0; e < 2; ++e) {
         const int q = 2 * ks + e;
         // (one packed fma per pair - these epilogues run with the matrix pipe idle, where v_pk_fma_f32 issues like any other
-        //  vector instruction; ReLU is the lower clamp of split2)
+        //  vector instruction; ReLU is the lower clamp of f16x3_split_relu_max)
         const f32x2 v01 = __builtin_elementwise_fma(f32x2{acc[s][4 * q], acc[s][4 * q + 1]}, f32x2{scale, scale}, f32x2{bq[q][0], bq[q][1]});
         const f32x2 v23 = __builtin_elementwise_fma(f32x2{acc[s][4 * q + 2], acc[s][4 * q + 3]}, f32x2{scale, scale}, f32x2{bq[q][2], bq[q][3]});
-        split2(v01[0], v01[1], h1[2 * e], h2[2 * e], cl);
-        split2(v23[0], v23[1], h1[2 * e + 1], h2[2 * e + 1], cl);
+        f16x3_split_relu_max(v01[0], v01[1], h1[2 * e], h2[2 * e], cl);
+        f16x3_split_relu_max(v23[0], v23[1], h1[2 * e + 1], h2[2 * e + 1], cl);
       }
       char* o = lds + out_off + ((ct * 2 + ks) * 2 + fh) * BLK + pix * PIXB + agent * 16;
       *reinterpret_cast<u32x4*>(o) = u32x4{h1[0], h1[1], h1[2], h1[3]};
@@ -372,11 +372,11 @@ __device__ __forceinline__ void chain_stage4(const ChainParams& p, char* lds, in
       for (int e = 0; e < 2; ++e) {
         const int q = 2 * ks + e;
         // (one packed fma per pair - these epilogues run with the matrix pipe idle, where v_pk_fma_f32 issues like any other
-        //  vector instruction; ReLU is the lower clamp of split2)
+        //  vector instruction; ReLU is the lower clamp of f16x3_split_relu_max)
         const f32x2 v01 = __builtin_elementwise_fma(f32x2{acc[s][4 * q], acc[s][4 * q + 1]}, f32x2{scale, scale}, f32x2{bq[q][0], bq[q][1]});
         const f32x2 v23 = __builtin_elementwise_fma(f32x2{acc[s][4 * q + 2], acc[s][4 * q + 3]}, f32x2{scale, scale}, f32x2{bq[q][2], bq[q][3]});
-        split2(v01[0], v01[1], h1[2 * e], h2[2 * e], cl);
-        split2(v23[0], v23[1], h1[2 * e + 1], h2[2 * e + 1], cl);
+        f16x3_split_relu_max(v01[0], v01[1], h1[2 * e], h2[2 * e], cl);
+        f16x3_split_relu_max(v23[0], v23[1], h1[2 * e + 1], h2[2 * e + 1], cl);
       }
       const int chunk = (ct * 2 + ks) * 2 + fh;
       if (LAST) {

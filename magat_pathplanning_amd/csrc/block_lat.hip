@@ -84,34 +84,6 @@ __device__ __forceinline__ void ring_fill(WRing& w, const char* wbase, unsigned 
   }
 }
 
-// value pair -> its two f16 planes, remembering whether a value left +-65504: the instruction sequence of split_pair_f16
-// (conv_gemm_bf16x6.hip) - the float32 loaders of the long-K head and of compressMLP, whose planes this kernel reproduces
-__device__ __forceinline__ void split_pair_lat(float x, float y, unsigned& p1, unsigned& p2, bool& clamped) {
-  clamped |= !(__builtin_fabsf(x) <= 65504.f) | !(__builtin_fabsf(y) <= 65504.f);
-  x = __builtin_amdgcn_fmed3f(x, -65504.f, 65504.f);
-  y = __builtin_amdgcn_fmed3f(y, -65504.f, 65504.f);
-  const f16x2 h = __builtin_convertvector(f32x2{x, y}, f16x2);
-  p1 = __builtin_bit_cast(unsigned, h);
-  float rx, ry;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(rx) : "v"(p1), "v"(x));
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(ry) : "v"(p1), "v"(y));
-  const f16x2 r = __builtin_convertvector(f32x2{rx, ry}, f16x2);
-  p2 = __builtin_bit_cast(unsigned, r);
-}
-
-// signed value pair -> its two f16 planes: split2s of stem8.hip (the stem's state maps and weights)
-__device__ __forceinline__ void split2s_lat(float x, float y, unsigned& p1, unsigned& p2) {
-  x = __builtin_amdgcn_fmed3f(x, -65504.f, 65504.f);
-  y = __builtin_amdgcn_fmed3f(y, -65504.f, 65504.f);
-  const f16x2 h = __builtin_convertvector(f32x2{x, y}, f16x2);
-  p1 = __builtin_bit_cast(unsigned, h);
-  float rx, ry;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(rx) : "v"(p1), "v"(x));
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(ry) : "v"(p1), "v"(y));
-  const f16x2 r = __builtin_convertvector(f32x2{rx, ry}, f16x2);
-  p2 = __builtin_bit_cast(unsigned, r);
-}
-
 // K walk of a dense layer on ONE row of activations (the agent's): NSTEP k steps of 16, the activation operand of step s at
 // lds + abase + 32 s (second plane PS bytes behind) - every column of the 32-wide tile carries the same row -, this wave's
 // 32 output channels' weight fragments at wbase (1 KB per plane and step)
@@ -234,8 +206,8 @@ __device__ __forceinline__ void lat_stage(char* lds, const unsigned (&ab)[NT], c
         const int q = 2 * ks + e;
         const f32x2 v01 = __builtin_elementwise_fma(f32x2{acc[s][4 * q], acc[s][4 * q + 1]}, f32x2{scale, scale}, f32x2{bq[q][0], bq[q][1]});
         const f32x2 v23 = __builtin_elementwise_fma(f32x2{acc[s][4 * q + 2], acc[s][4 * q + 3]}, f32x2{scale, scale}, f32x2{bq[q][2], bq[q][3]});
-        split2(v01[0], v01[1], h1[2 * e], h2[2 * e], cl);
-        split2(v23[0], v23[1], h1[2 * e + 1], h2[2 * e + 1], cl);
+        f16x3_split_relu_max(v01[0], v01[1], h1[2 * e], h2[2 * e], cl);
+        f16x3_split_relu_max(v23[0], v23[1], h1[2 * e + 1], h2[2 * e + 1], cl);
       }
       // (no branch around the stores: the padding lanes of the second tile write to a slot no tap reads - with the stores under
       //  a condition the compiler sinks the whole walk into the conditional block)
@@ -466,7 +438,7 @@ __global__ __launch_bounds__(256, 1) void block_lat_kernel(const LatParams p) {
       }
       unsigned h1[4], h2[4];
 #pragma unroll
-      for (int e = 0; e < 4; ++e) split2s_lat(wv[2 * e], wv[2 * e + 1], h1[e], h2[e]);
+      for (int e = 0; e < 4; ++e) f16x3_split_clamp(wv[2 * e], wv[2 * e + 1], h1[e], h2[e]);
       wa[ty][0] = u32x4{h1[0], h1[1], h1[2], h1[3]};
       wa[ty][1] = u32x4{h2[0], h2[1], h2[2], h2[3]};
     }
@@ -479,8 +451,8 @@ __global__ __launch_bounds__(256, 1) void block_lat_kernel(const LatParams p) {
       // (range guard of the INPUT: a NaN / Inf / |x| > 65504 entry must not become a finite clamp)
       clamped |= !(__builtin_fabsf(v0) <= 65504.f) || !(__builtin_fabsf(v1) <= 65504.f) || !(__builtin_fabsf(v2) <= 65504.f);
       unsigned h01, l01, h2x, l2x;
-      split2s_lat(v0, v1, h01, l01);
-      split2s_lat(v2, 1.f, h2x, l2x);
+      f16x3_split_clamp(v0, v1, h01, l01);
+      f16x3_split_clamp(v2, 1.f, h2x, l2x);
       char* dst = lds + L_SIN + (y + 1) * S_ROWB + (x + 1) * 8;
       *reinterpret_cast<uint2*>(dst) = uint2{h01, h2x};
       *reinterpret_cast<uint2*>(dst + S_INPL) = uint2{l01, l2x};
@@ -520,8 +492,8 @@ __global__ __launch_bounds__(256, 1) void block_lat_kernel(const LatParams p) {
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
           const int q = 2 * ks + e;
-          split2(acc[4 * q], acc[4 * q + 1], h1[2 * e], h2[2 * e], cl);
-          split2(acc[4 * q + 2], acc[4 * q + 3], h1[2 * e + 1], h2[2 * e + 1], cl);
+          f16x3_split_relu_max(acc[4 * q], acc[4 * q + 1], h1[2 * e], h2[2 * e], cl);
+          f16x3_split_relu_max(acc[4 * q + 2], acc[4 * q + 3], h1[2 * e + 1], h2[2 * e + 1], cl);
         }
         *reinterpret_cast<u32x4*>(o + ks * 2 * S_BLK) = u32x4{h1[0], h1[1], h1[2], h1[3]};
         *reinterpret_cast<u32x4*>(o + ks * 2 * S_BLK + 4 * S_BLK) = u32x4{h2[0], h2[1], h2[2], h2[3]};
@@ -623,8 +595,8 @@ __global__ __launch_bounds__(256, 1) void block_lat_kernel(const LatParams p) {
           // it; operand order [32-channel slab = this wave][cell][k step][lane half][8 halves] in the dead X1 region
           bool cl = false;
           unsigned h1[2], h2[2];
-          split_pair_lat(v[0] * insc, v[1] * insc, h1[0], h2[0], cl);
-          split_pair_lat(v[2] * insc, v[3] * insc, h1[1], h2[1], cl);
+          f16x3_split_clamp_flag(v[0] * insc, v[1] * insc, h1[0], h2[0], cl);
+          f16x3_split_clamp_flag(v[2] * insc, v[3] * insc, h1[1], h2[1], cl);
           const unsigned o = (unsigned)(L_HP + ((wave * 9 + cellT[s]) * 2 + (qd >> 1)) * 32 + (qd & 1) * 16 + fh * 8);
           if (owner) {
             *reinterpret_cast<uint2*>(lds + o) = uint2{h1[0], h1[1]};
@@ -659,8 +631,8 @@ __global__ __launch_bounds__(256, 1) void block_lat_kernel(const LatParams p) {
         // compressMLP's activation planes from the very values stored (x its activation scale), operand order
         // [k step = 2 wave + q / 2][lane half = q % 2][4 fh + c] in the dead X2 region
         unsigned h1[2], h2[2];
-        split_pair_lat(v[0] * insc2, v[1] * insc2, h1[0], h2[0], cl);
-        split_pair_lat(v[2] * insc2, v[3] * insc2, h1[1], h2[1], cl);
+        f16x3_split_clamp_flag(v[0] * insc2, v[1] * insc2, h1[0], h2[0], cl);
+        f16x3_split_clamp_flag(v[2] * insc2, v[3] * insc2, h1[1], h2[1], cl);
         const unsigned o = (unsigned)(L_CP + (2 * wave + (q >> 1)) * 32 + (q & 1) * 16 + fh * 8);
         if (fr == 0) {
           *reinterpret_cast<uint2*>(lds + o) = uint2{h1[0], h1[1]};

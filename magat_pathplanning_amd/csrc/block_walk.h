@@ -1,12 +1,8 @@
 // Shared pieces of the eight-agent-group kernels (block_fused.hip: the BasicBlock chain kernels; stem8.hip: stem +
-// layer1.conv1): LDS map geometry, row tiles by tap-validity class, the plane split, and walk4 - the four-wave K walk.
+// layer1.conv1): LDS map geometry, row tiles by tap-validity class, and walk4 - the four-wave K walk.
 // Included inside each file's anonymous namespace.
 #pragma once
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
+#include "f16x3.h"
 
 constexpr int AG = 8;                       // agents per workgroup
 constexpr int NPIX = 36, ZPIX = 36;         // 6 x 6 map; pixel slot 36 = zeros
@@ -48,28 +44,7 @@ __device__ constexpr int WT32[8][3] = {{T_I0, -1, -1}, {T_I2, -1, -1}, {T_C, -1,
 __device__ constexpr int WG64[4][3] = {{T_I0, T_I1, -1}, {T_I2, T_I3, -1}, {T_C, T_ET, -1}, {T_EB, T_EL, T_ER}};
 
 
-// barrier for LDS hand-overs only: __syncthreads() carries s_waitcnt vmcnt(0) in its release fence and would wait for every
-// global load in flight (weight prefetches, the next group's input)
-#define L3_LDS_SYNC() do { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); } while (0)
-
-// value pair -> its two f16 planes; ReLU and the f16 range clamp are the same v_med3.  `vmax` keeps the running maximum of the
-// UNclamped values (one v_max3 per pair; the caller compares it with 65504 once per tile for the range guard).
-__device__ __forceinline__ void split2(float x, float y, unsigned& p1, unsigned& p2, float& vmax) {
-  vmax = fmaxf(fmaxf(vmax, x), y);
-  x = __builtin_amdgcn_fmed3f(x, 0.f, 65504.f);
-  y = __builtin_amdgcn_fmed3f(y, 0.f, 65504.f);
-  const f16x2 h = __builtin_convertvector(f32x2{x, y}, f16x2);
-  p1 = __builtin_bit_cast(unsigned, h);
-  // residual x - hi: one mixed-precision fma per value (fma(hi, -1, x), exact; the f16 operand read from its half of the
-  // packed register) instead of two conversions and a packed subtract.  (v_fma_mixlo_f16 / v_fma_mixhi_f16 - the same fma
-  // with the conversion folded in, two instructions per pair instead of three - was measured in round 4: chain kernel 1900 ->
-  // 1904 us, stem 165 -> 169 us same-box: not cheaper.)
-  float rx, ry;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(rx) : "v"(p1), "v"(x));
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(ry) : "v"(p1), "v"(y));
-  const f16x2 r = __builtin_convertvector(f32x2{rx, ry}, f16x2);
-  p2 = __builtin_bit_cast(unsigned, r);
-}
+#define L3_LDS_SYNC() MAGAT_LDS_SYNC()      // (f16x3.h)
 
 
 struct W4Item { signed char tp, ks, s, first; };           // tp = 9: the residual 1x1 segment over in2
@@ -141,7 +116,7 @@ struct GeoStem {
 #ifdef MAGAT_W4_NOPIN
 #define W4_PIN() do { } while (0)
 #else
-#define W4_PIN() __builtin_amdgcn_sched_barrier(0)
+#define W4_PIN() MAGAT_SCHED_FENCE()
 #endif
 constexpr int w4_depth(int nt, int ksm) { return nt * ksm <= 8 ? 8 : MAGAT_W4_D; }    // short k steps (few MFMAs): deeper weight ring
 // first D - 1 k steps of a weight stream into the ring

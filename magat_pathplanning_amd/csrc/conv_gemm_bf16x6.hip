@@ -22,12 +22,9 @@
 #include <type_traits>
 
 #include "magat_common.h"
+#include "f16x3.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned short u16;
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
@@ -90,34 +87,7 @@ __device__ __forceinline__ void split_pair(float x, float y, unsigned& p1, unsig
   p3 = cvt_pk_bf16(sx, sy);
 }
 
-// fp16x2 split ("f16x3": x ~ h1 + h2, two RNE half planes = 22 significand bits; the product keeps h1g1 + h1g2 + h2g1,
-// dropping h2g2 <= 2^-22 |xw|): THREE v_mfma_f32_32x32x16_f16 per product instead of six bf16 ones.  fp16 has the
-// narrow exponent, so activations are clamped to +-65504 per plane (values up to 1.3e5 stay exact through the second
-// plane; larger ones saturate - unreachable for this network) and residuals below 6e-5 go subnormal (absolute error
-// <= 3e-8, the fp32 spacing of values near 0.5); weights are pre-scaled by a power of two so that both planes are
-// normal numbers (the scale is undone in the epilogue).
-__device__ __forceinline__ void split_pair_f16(float x, float y, unsigned& p1, unsigned& p2) {
-  // one v_med3_f32 per value (fminf(fmaxf()) costs an extra canonicalising v_max each)
-  x = __builtin_amdgcn_fmed3f(x, -65504.f, 65504.f);
-  y = __builtin_amdgcn_fmed3f(y, -65504.f, 65504.f);
-  const f16x2 h = __builtin_convertvector(f32x2{x, y}, f16x2);
-  p1 = __builtin_bit_cast(unsigned, h);
-  // residual x - hi: one mixed-precision fma per value (fma(hi, -1, x), exact; the f16 operand read from its half of the
-  // packed register) - not two conversions + v_pk_add_f32: packed fp32 instructions do not issue while an MFMA runs
-  // (tools/exp/mfma_valu.hip), and the loaders split while other waves of the SIMD multiply
-  float rx, ry;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(rx) : "v"(p1), "v"(x));
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(ry) : "v"(p1), "v"(y));
-  const f16x2 r = __builtin_convertvector(f32x2{rx, ry}, f16x2);
-  p2 = __builtin_bit_cast(unsigned, r);
-}
-// same, remembering in `clamped` whether a value was outside +-65504 (range guard)
-__device__ __forceinline__ void split_pair_f16(float x, float y, unsigned& p1, unsigned& p2, bool& clamped) {
-  // (negated compares: true for NaN as well - a NaN activation must take the float32 re-run, which hands it on like the
-  // reference does, not come out of the v_med3 clamp as a finite number)
-  clamped |= !(__builtin_fabsf(x) <= 65504.f) | !(__builtin_fabsf(y) <= 65504.f);
-  split_pair_f16(x, y, p1, p2);
-}
+// (the f16x3 split of the NPL == 2 loaders: f16x3_split_clamp / f16x3_split_clamp_flag of f16x3.h)
 
 // AF32: the activation operands (in, in2) are plain float32 and are split into their three bf16 planes by the
 // loader on the way into LDS (no 3-plane tensors in HBM, 2/3 of the activation traffic); weights are always
@@ -267,8 +237,8 @@ __global__ __launch_bounds__(256, 3) void conv_gemm_bf16x6_kernel(const SplitPar
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
         unsigned q1[2], q2[2];
-        split_pair_f16(fa32[i][0], fa32[i][1], q1[0], q2[0], clamped);
-        split_pair_f16(fa32[i][2], fa32[i][3], q1[1], q2[1], clamped);
+        f16x3_split_clamp_flag(fa32[i][0], fa32[i][1], q1[0], q2[0], clamped);
+        f16x3_split_clamp_flag(fa32[i][2], fa32[i][3], q1[1], q2[1], clamped);
         qs[0][i] = uint2{q1[0], q1[1]};
         qs[1][i] = uint2{q2[0], q2[1]};
       }
@@ -434,8 +404,8 @@ __global__ __launch_bounds__(256, 3) void conv_gemm_bf16x6_kernel(const SplitPar
         } else if (p.out_split == 3) {     // two f16 planes (the operand format of the next f16x3 layer: split once here,
           u16* ob = static_cast<u16*>(p.out);   // not once per tap and slab by every consumer)
           unsigned a1, a2, b1, b2;
-          split_pair_f16(v[0], v[1], a1, a2, clamped);
-          split_pair_f16(v[2], v[3], b1, b2, clamped);
+          f16x3_split_clamp_flag(v[0], v[1], a1, a2, clamped);
+          f16x3_split_clamp_flag(v[2], v[3], b1, b2, clamped);
           if (vec) {
             *reinterpret_cast<uint2*>(ob + o) = uint2{a1, b1};
             *reinterpret_cast<uint2*>(ob + p.out_plane + o) = uint2{a2, b2};
@@ -685,10 +655,10 @@ __global__ __launch_bounds__(256, (TM == 1 && !FUSE2) ? 3 : 2) void conv_gemm_f1
             }
           }
           unsigned h1[4], h2[4];
-          split_pair_f16(lo[0], lo[1], h1[0], h2[0], clamped);
-          split_pair_f16(lo[2], lo[3], h1[1], h2[1], clamped);
-          split_pair_f16(hi[0], hi[1], h1[2], h2[2], clamped);
-          split_pair_f16(hi[2], hi[3], h1[3], h2[3], clamped);
+          f16x3_split_clamp_flag(lo[0], lo[1], h1[0], h2[0], clamped);
+          f16x3_split_clamp_flag(lo[2], lo[3], h1[1], h2[1], clamped);
+          f16x3_split_clamp_flag(hi[0], hi[1], h1[2], h2[2], clamped);
+          f16x3_split_clamp_flag(hi[2], hi[3], h1[3], h2[3], clamped);
           qa[i][ks][0] = u32x4{h1[0], h1[1], h1[2], h1[3]};
           qa[i][ks][1] = u32x4{h2[0], h2[1], h2[2], h2[3]};
         }
@@ -864,8 +834,8 @@ __global__ __launch_bounds__(256, (TM == 1 && !FUSE2) ? 3 : 2) void conv_gemm_f1
             v[c] = vv[4 * q + c];
             if (insc2 != 1.f) asm("v_mul_f32 %0, %1, %2" : "=v"(v[c]) : "v"(v[c]), "v"(insc2));
           }
-          split_pair_f16(v[0], v[1], h1[2 * e], h2[2 * e], clamped);
-          split_pair_f16(v[2], v[3], h1[2 * e + 1], h2[2 * e + 1], clamped);
+          f16x3_split_clamp_flag(v[0], v[1], h1[2 * e], h2[2 * e], clamped);
+          f16x3_split_clamp_flag(v[2], v[3], h1[2 * e + 1], h2[2 * e + 1], clamped);
         }
         // accumulator layout -> operand k order: lane half h holds channels 16 ks + 8 e + 4 h + c in (e, c); an operand's lane
         // half h holds 16 ks + 8 h + i.  Half 0 keeps its e = 0 quad and takes half 1's e = 0 quad as i = 4..7; half 1 takes
@@ -983,8 +953,8 @@ __global__ __launch_bounds__(256, (TM == 1 && !FUSE2) ? 3 : 2) void conv_gemm_f1
               v[c] = acc[i][j][4 * q + c] * acc_scale + bq[j][q][c];
               if (p.relu) v[c] = magat_relu(v[c]);
             }
-            split_pair_f16(v[0], v[1], h1[2 * e], h2[2 * e], clamped);
-            split_pair_f16(v[2], v[3], h1[2 * e + 1], h2[2 * e + 1], clamped);
+            f16x3_split_clamp_flag(v[0], v[1], h1[2 * e], h2[2 * e], clamped);
+            f16x3_split_clamp_flag(v[2], v[3], h1[2 * e + 1], h2[2 * e + 1], clamped);
           }
           char* const o = ob + (long long)(((n0 >> 5) + j) * 2 + ks) * 4096;
           *reinterpret_cast<u32x4*>(o) = u32x4{h1[0], h1[1], h1[2], h1[3]};

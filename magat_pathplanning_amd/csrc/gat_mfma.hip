@@ -30,11 +30,9 @@
 #include <type_traits>
 
 #include "magat_common.h"
+#include "f16x3.h"
 
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 struct GatMfmaParams {
   const float* X;             // [B*N][ldx]
@@ -80,16 +78,9 @@ long long* g_gat_mfma_dbg = nullptr;
 #define GM_YST(ptr, val) *reinterpret_cast<float*>(ptr) = (val)
 #endif
 
-// A lone wave issues in order: vector work only runs under the matrix pipe when MFMAs and vector instructions ALTERNATE in
-// the instruction stream.  GM_PIN fences the scheduler: what is written between two fences stays between them.
-#define GM_PIN() __builtin_amdgcn_sched_barrier(0)
+#define GM_PIN() MAGAT_SCHED_FENCE()      // (f16x3.h)
 
-// LDS hand-over barrier without the vmcnt(0) of __syncthreads(): weight fragments and Y stores stay in flight
-#define GM_SYNC() do { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); } while (0)
-
-__device__ __forceinline__ f32x16 mfma16(const uint4& a, const uint4& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
+#define GM_SYNC() MAGAT_LDS_SYNC()
 
 // one 16-wide k step of a row of MT tiles: the three split products, tile after tile (no two consecutive MFMAs on one
 // accumulator when there is more than one tile)
@@ -103,27 +94,10 @@ __device__ __forceinline__ void mma_step_row(f32x16 (&acc)[MT], const uint4 (&a)
   }
 }
 
-// value pair -> its two f16 planes: hi = rne(v) (v_cvt_pk_f16_f32), lo = rne(v - hi) with the residual formed by one
-// mixed-precision fma per value (fma(hi, -1, v): exact).  No range clamp: a value beyond the f16 range turns into inf /
-// nan planes, and the caller's running maximum `vmax` of |v| raises the range flag, which makes the float32 form
-// re-write every output of the launch.
-__device__ __forceinline__ void split_pair(float x, float y, unsigned& p1, unsigned& p2) {
-  const f16x2 h = __builtin_convertvector(f32x2{x, y}, f16x2);
-  p1 = __builtin_bit_cast(unsigned, h);
-  float rx, ry;      // v - (float)h as fma(h, -1, v), the f16 operand read straight from its half of the packed register
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(rx) : "v"(p1), "v"(x));
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(ry) : "v"(p1), "v"(y));
-  const f16x2 r = __builtin_convertvector(f32x2{rx, ry}, f16x2);
-  p2 = __builtin_bit_cast(unsigned, r);
-}
 __device__ __forceinline__ float mul1(float a, float b) {      // one v_mul_f32 the vectorizer cannot pair into a packed op
   float r;
   asm("v_mul_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
   return r;
-}
-__device__ __forceinline__ void split2v(float x, float y, unsigned& p1, unsigned& p2, float& vmax) {
-  vmax = fmaxf(fmaxf(vmax, fabsf(x)), fabsf(y));
-  split_pair(x, y, p1, p2);
 }
 
 // 4 x 4 transpose inside every quad of lanes: afterwards a[r] of quad lane l holds what was a[l] of quad lane r (two butterfly
@@ -331,10 +305,10 @@ __global__ __launch_bounds__(256, 1) void gat_mfma_kernel(const GatMfmaParams p)
         for (int e = 0; e < 8; ++e) bad |= !(fabsf(xv[e]) <= 65504.f);
         if (bad) vmax = __builtin_inff();
         uint4 hi, lo;
-        split2v(xv[0], xv[1], hi.x, lo.x, vmax);
-        split2v(xv[2], xv[3], hi.y, lo.y, vmax);
-        split2v(xv[4], xv[5], hi.z, lo.z, vmax);
-        split2v(xv[6], xv[7], hi.w, lo.w, vmax);
+        f16x3_split_absmax(xv[0], xv[1], hi.x, lo.x, vmax);
+        f16x3_split_absmax(xv[2], xv[3], hi.y, lo.y, vmax);
+        f16x3_split_absmax(xv[4], xv[5], hi.z, lo.z, vmax);
+        f16x3_split_absmax(xv[6], xv[7], hi.w, lo.w, vmax);
         char* dst = lds + (row * 512 + ((ch ^ (row & 15)) << 4));
         *reinterpret_cast<uint4*>(dst) = hi;
         *reinterpret_cast<uint4*>(dst + 256) = lo;
@@ -468,13 +442,13 @@ __global__ __launch_bounds__(256, 1) void gat_mfma_kernel(const GatMfmaParams p)
               const float v01[2] = {mul1(accq[0][mt][4 * q], kInvScale), mul1(accq[0][mt][4 * q + 1], kInvScale)};
               GM_PIN();
               tap_one(KT - 1, t0 + 1);
-              split2v(v01[0], v01[1], hq[0], lq[0], vmax);
+              f16x3_split_absmax(v01[0], v01[1], hq[0], lq[0], vmax);
               GM_PIN();
               tap_one(KT - 1, t0 + 2);
               const float v23[2] = {mul1(accq[0][mt][4 * q + 2], kInvScale), mul1(accq[0][mt][4 * q + 3], kInvScale)};
               GM_PIN();
               tap_one(KT - 1, t0 + 3);
-              split2v(v23[0], v23[1], hq[1], lq[1], vmax);
+              f16x3_split_absmax(v23[0], v23[1], hq[1], lq[1], vmax);
               GM_PIN();
               tap_one(KT - 1, t0 + 4);
               char* o = lds + (jb[mt] + qx[q]);
@@ -638,10 +612,10 @@ __global__ __launch_bounds__(256, 1) void gat_mfma_kernel(const GatMfmaParams p)
               const float v23[2] = {mul1(acce[0][mt][4 * q + 2], inv), mul1(acce[0][mt][4 * q + 3], inv)};
               GM_PIN();
               tap_run(t0 + TR);
-              split_pair(v01[0], v01[1], ha[0], la[0]);
+              f16x3_split(v01[0], v01[1], ha[0], la[0]);
               GM_PIN();
               tap_run(t0 + 2 * TR);
-              split_pair(v23[0], v23[1], ha[1], la[1]);
+              f16x3_split(v23[0], v23[1], ha[1], la[1]);
               GM_PIN();
               tap_run(t0 + 3 * TR);
               const int jg = 32 * mt + 8 * q;
@@ -685,11 +659,11 @@ __global__ __launch_bounds__(256, 1) void gat_mfma_kernel(const GatMfmaParams p)
               uint2 hi, lo;
               if constexpr (KT == 3) tap_upto4(0, u0, um);
               const float v01[2] = {mul1(acc[k + 1][mt][4 * q], kInvScale), mul1(acc[k + 1][mt][4 * q + 1], kInvScale)};
-              split2v(v01[0], v01[1], hi.x, lo.x, vmax);
+              f16x3_split_absmax(v01[0], v01[1], hi.x, lo.x, vmax);
               GM_PIN();
               if constexpr (KT == 3) tap_upto4(0, um, u1);
               const float v23[2] = {mul1(acc[k + 1][mt][4 * q + 2], kInvScale), mul1(acc[k + 1][mt][4 * q + 3], kInvScale)};
-              split2v(v23[0], v23[1], hi.y, lo.y, vmax);
+              f16x3_split_absmax(v23[0], v23[1], hi.y, lo.y, vmax);
               GM_PIN();
               *reinterpret_cast<uint2*>(ub + i0 * 2) = hi;
               *reinterpret_cast<uint2*>(ub + (i0 * 2 + UP)) = lo;

@@ -20,6 +20,7 @@
 // at all - a lane keeps its operand fragments of row 32 w + lane % 32 in 64 registers, read straight from HBM in that layout.  What
 // is left - Q / U^T and A planes - is 139 KB: the one-launch form gat_mfma.hip (162 KB per instance, ends at N = 102) cannot reach.
 #include "magat_common.h"
+#include "f16x3.h"
 
 
 #ifdef MAGAT_DEBUG_HOOKS
@@ -32,9 +33,6 @@ extern "C" int magat_gat_mid_set_debug_buffer(long long* dev_buf) { g_gat_mid_db
 #endif
 
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 struct GatMidParams {
   const float* X;             // [B*N][ldx]
@@ -50,23 +48,6 @@ struct GatMidParams {
   long long* dbg;             // debug builds: phase stamps
   float* Ypre; int ldpre;     // HS, head-mean: the heads' pre-activation outputs [B*N][P F] (the caller's workspace); a small kernel forms the mean
 };
-
-__device__ __forceinline__ f32x16 mfma16(const uint4& a, const uint4& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-// two floats -> the two f16 planes (value = p1 + p2 to 22 bits).  Compiler-visible conversions only: an asm statement reading a
-// register an MFMA has just written gets none of the wait states the hazard recognizer inserts (round 6, gat_csr_fused.hip)
-__device__ __forceinline__ void split_pair(float x, float y, unsigned& p1, unsigned& p2) {
-  const f16x2 h = __builtin_convertvector(f32x2{x, y}, f16x2);
-  p1 = __builtin_bit_cast(unsigned, h);
-  const f32x2 back = __builtin_convertvector(h, f32x2);
-  const f16x2 r = __builtin_convertvector(f32x2{x - back[0], y - back[1]}, f16x2);
-  p2 = __builtin_bit_cast(unsigned, r);
-}
-__device__ __forceinline__ void split2v(float x, float y, unsigned& p1, unsigned& p2, float& vmax) {
-  vmax = fmaxf(fmaxf(vmax, fabsf(x)), fabsf(y));
-  split_pair(x, y, p1, p2);
-}
 
 // HS (few instances: the batch-1 step of the reference's inference loop): a workgroup per (instance, HEAD) instead of per instance -
 // one planning instance of 100 agents then runs on four CUs instead of one.  A head's arithmetic does not change; with head-mean
@@ -117,10 +98,10 @@ __global__ __launch_bounds__(64 * NT) void gat_mid_kernel(const GatMidParams p) 
 #pragma unroll
         for (int e = 0; e < 8; ++e) bad |= !(fabsf(xv[e]) <= 65504.f);
         if (bad) vmax = __builtin_inff();
-        split2v(xv[0], xv[1], xr[ks][0].x, xr[ks][1].x, vmax);
-        split2v(xv[2], xv[3], xr[ks][0].y, xr[ks][1].y, vmax);
-        split2v(xv[4], xv[5], xr[ks][0].z, xr[ks][1].z, vmax);
-        split2v(xv[6], xv[7], xr[ks][0].w, xr[ks][1].w, vmax);
+        f16x3_split_cv_absmax(xv[0], xv[1], xr[ks][0].x, xr[ks][1].x, vmax);
+        f16x3_split_cv_absmax(xv[2], xv[3], xr[ks][0].y, xr[ks][1].y, vmax);
+        f16x3_split_cv_absmax(xv[4], xv[5], xr[ks][0].z, xr[ks][1].z, vmax);
+        f16x3_split_cv_absmax(xv[6], xv[7], xr[ks][0].w, xr[ks][1].w, vmax);
       }
     } else {
       const float* Xb = p.X + (long long)inst * N * p.ldx;
@@ -137,10 +118,10 @@ __global__ __launch_bounds__(64 * NT) void gat_mid_kernel(const GatMidParams p) 
         for (int e = 0; e < 8; ++e) bad |= !(fabsf(xv[e]) <= 65504.f);
         if (bad) vmax = __builtin_inff();
         uint4 hi, lo;
-        split2v(xv[0], xv[1], hi.x, lo.x, vmax);
-        split2v(xv[2], xv[3], hi.y, lo.y, vmax);
-        split2v(xv[4], xv[5], hi.z, lo.z, vmax);
-        split2v(xv[6], xv[7], hi.w, lo.w, vmax);
+        f16x3_split_cv_absmax(xv[0], xv[1], hi.x, lo.x, vmax);
+        f16x3_split_cv_absmax(xv[2], xv[3], hi.y, lo.y, vmax);
+        f16x3_split_cv_absmax(xv[4], xv[5], hi.z, lo.z, vmax);
+        f16x3_split_cv_absmax(xv[6], xv[7], hi.w, lo.w, vmax);
         char* dst = lds + XO + row * RS + ch * 16;
         *reinterpret_cast<uint4*>(dst) = hi;
         *reinterpret_cast<uint4*>(dst + XPL) = lo;
@@ -247,8 +228,8 @@ __global__ __launch_bounds__(64 * NT) void gat_mid_kernel(const GatMidParams p) 
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             uint2 hi, lo;
-            split2v(acc[4 * q] * kInvScale, acc[4 * q + 1] * kInvScale, hi.x, lo.x, vmax);
-            split2v(acc[4 * q + 2] * kInvScale, acc[4 * q + 3] * kInvScale, hi.y, lo.y, vmax);
+            f16x3_split_cv_absmax(acc[4 * q] * kInvScale, acc[4 * q + 1] * kInvScale, hi.x, lo.x, vmax);
+            f16x3_split_cv_absmax(acc[4 * q + 2] * kInvScale, acc[4 * q + 3] * kInvScale, hi.y, lo.y, vmax);
             char* o = lds + QO + myrow * RS + (32 * ct + 8 * q + 4 * fh) * 2;
             *reinterpret_cast<uint2*>(o) = hi;
             *reinterpret_cast<uint2*>(o + XPL) = lo;
@@ -323,8 +304,8 @@ __global__ __launch_bounds__(64 * NT) void gat_mid_kernel(const GatMidParams p) 
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           unsigned ha[2], la[2];
-          split_pair(e[jt][4 * q] * inv, e[jt][4 * q + 1] * inv, ha[0], la[0]);
-          split_pair(e[jt][4 * q + 2] * inv, e[jt][4 * q + 3] * inv, ha[1], la[1]);
+          f16x3_split_cv(e[jt][4 * q] * inv, e[jt][4 * q + 1] * inv, ha[0], la[0]);
+          f16x3_split_cv(e[jt][4 * q + 2] * inv, e[jt][4 * q + 3] * inv, ha[1], la[1]);
           char* o = lds + AO + (32 * jt + 8 * q + 4 * fh) * SA + myrow * 2;
 #pragma unroll
           for (int c = 0; c < 4; ++c) {
@@ -382,8 +363,8 @@ __global__ __launch_bounds__(64 * NT) void gat_mid_kernel(const GatMidParams p) 
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             uint2 hi, lo;
-            split2v(acc[k + 1][ct][4 * q] * kInvScale, acc[k + 1][ct][4 * q + 1] * kInvScale, hi.x, lo.x, vmax);
-            split2v(acc[k + 1][ct][4 * q + 2] * kInvScale, acc[k + 1][ct][4 * q + 3] * kInvScale, hi.y, lo.y, vmax);
+            f16x3_split_cv_absmax(acc[k + 1][ct][4 * q] * kInvScale, acc[k + 1][ct][4 * q + 1] * kInvScale, hi.x, lo.x, vmax);
+            f16x3_split_cv_absmax(acc[k + 1][ct][4 * q + 2] * kInvScale, acc[k + 1][ct][4 * q + 3] * kInvScale, hi.y, lo.y, vmax);
             char* o = lds + UO + (32 * ct + fr) * SA + (32 * w + 8 * q + 4 * fh) * 2;
             *reinterpret_cast<uint2*>(o) = hi;
             *reinterpret_cast<uint2*>(o + UPL) = lo;

@@ -13,11 +13,9 @@
 // [2][NC][G] halves of 2^8 Bt: a lane's MFMA row operand is 16 contiguous bytes of a weight row; 16 KB per head at G = 32, L2 /
 // L1 hits).  Values beyond the f16 range raise range_flag and the caller's predicated two-launch float32 form rewrites the output.
 #include "magat_common.h"
+#include "f16x3.h"
 
 namespace {
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
 
 struct GatSmallParams {
   const float* X;             // [B*N][ldx]
@@ -30,23 +28,6 @@ struct GatSmallParams {
   int* range_flag;
   const float* x_scale;
 };
-
-__device__ __forceinline__ f32x16 mfma16(const uint4& a, const uint4& b, const f32x16& c) {
-  return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0);
-}
-__device__ __forceinline__ void split_pair(float x, float y, unsigned& p1, unsigned& p2) {
-  const f16x2 h = __builtin_convertvector(f32x2{x, y}, f16x2);
-  p1 = __builtin_bit_cast(unsigned, h);
-  float rx, ry;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(rx) : "v"(p1), "v"(x));
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(ry) : "v"(p1), "v"(y));
-  const f16x2 r = __builtin_convertvector(f32x2{rx, ry}, f16x2);
-  p2 = __builtin_bit_cast(unsigned, r);
-}
-__device__ __forceinline__ void split2v(float x, float y, unsigned& p1, unsigned& p2, float& vmax) {
-  vmax = fmaxf(fmaxf(vmax, fabsf(x)), fabsf(y));
-  split_pair(x, y, p1, p2);
-}
 
 template <int F, int KT, bool CONCAT>
 __global__ __launch_bounds__(256, F == 32 ? 2 : 1) void gat_small_kernel(const GatSmallParams p) {      // (32 features: two waves per SIMD - a second workgroup per CU at large batches)
@@ -90,10 +71,10 @@ __global__ __launch_bounds__(256, F == 32 ? 2 : 1) void gat_small_kernel(const G
         for (int e = 0; e < 8; ++e) bad |= !(fabsf(xv[e]) <= 65504.f);
         if (bad) vmax = __builtin_inff();
         uint4 hi, lo;
-        split2v(xv[0], xv[1], hi.x, lo.x, vmax);
-        split2v(xv[2], xv[3], hi.y, lo.y, vmax);
-        split2v(xv[4], xv[5], hi.z, lo.z, vmax);
-        split2v(xv[6], xv[7], hi.w, lo.w, vmax);
+        f16x3_split_absmax(xv[0], xv[1], hi.x, lo.x, vmax);
+        f16x3_split_absmax(xv[2], xv[3], hi.y, lo.y, vmax);
+        f16x3_split_absmax(xv[4], xv[5], hi.z, lo.z, vmax);
+        f16x3_split_absmax(xv[6], xv[7], hi.w, lo.w, vmax);
         char* dst = lds + XO + row * RS + ch * 16;
         *reinterpret_cast<uint4*>(dst) = hi;
         *reinterpret_cast<uint4*>(dst + 32 * RS) = lo;
@@ -170,8 +151,8 @@ __global__ __launch_bounds__(256, F == 32 ? 2 : 1) void gat_small_kernel(const G
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
           uint2 hi, lo;
-          split2v(acc[4 * q] * kInvScale, acc[4 * q + 1] * kInvScale, hi.x, lo.x, vmax);
-          split2v(acc[4 * q + 2] * kInvScale, acc[4 * q + 3] * kInvScale, hi.y, lo.y, vmax);
+          f16x3_split_absmax(acc[4 * q] * kInvScale, acc[4 * q + 1] * kInvScale, hi.x, lo.x, vmax);
+          f16x3_split_absmax(acc[4 * q + 2] * kInvScale, acc[4 * q + 3] * kInvScale, hi.y, lo.y, vmax);
           char* o = lds + QO + fr * RS + (32 * ct + 8 * q + 4 * fh) * 2;
           *reinterpret_cast<uint2*>(o) = hi;
           *reinterpret_cast<uint2*>(o + 32 * RS) = lo;
@@ -229,8 +210,8 @@ __global__ __launch_bounds__(256, F == 32 ? 2 : 1) void gat_small_kernel(const G
 #pragma unroll
       for (int q = 0; q < 4; ++q) {
         unsigned ha[2], la[2];
-        split_pair(e[4 * q] * inv, e[4 * q + 1] * inv, ha[0], la[0]);
-        split_pair(e[4 * q + 2] * inv, e[4 * q + 3] * inv, ha[1], la[1]);
+        f16x3_split(e[4 * q] * inv, e[4 * q + 1] * inv, ha[0], la[0]);
+        f16x3_split(e[4 * q + 2] * inv, e[4 * q + 3] * inv, ha[1], la[1]);
         char* o = lds + AO + (8 * q + 4 * fh) * SA + fr * 2;
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
@@ -278,8 +259,8 @@ __global__ __launch_bounds__(256, F == 32 ? 2 : 1) void gat_small_kernel(const G
 #pragma unroll
           for (int q = 0; q < 4; ++q) {
             uint2 hi, lo;
-            split2v(acc[k + 1][ct][4 * q] * kInvScale, acc[k + 1][ct][4 * q + 1] * kInvScale, hi.x, lo.x, vmax);
-            split2v(acc[k + 1][ct][4 * q + 2] * kInvScale, acc[k + 1][ct][4 * q + 3] * kInvScale, hi.y, lo.y, vmax);
+            f16x3_split_absmax(acc[k + 1][ct][4 * q] * kInvScale, acc[k + 1][ct][4 * q + 1] * kInvScale, hi.x, lo.x, vmax);
+            f16x3_split_absmax(acc[k + 1][ct][4 * q + 2] * kInvScale, acc[k + 1][ct][4 * q + 3] * kInvScale, hi.y, lo.y, vmax);
             char* o = lds + UO + (32 * ct + fr) * SA + (8 * q + 4 * fh) * 2;
             *reinterpret_cast<uint2*>(o) = hi;
             *reinterpret_cast<uint2*>(o + F * SA) = lo;

@@ -20,10 +20,7 @@
 #include <cstdlib>
 
 #include "magat_common.h"
-
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
+#include "f16x3.h"
 
 namespace {
 
@@ -38,37 +35,6 @@ struct L1Params {
   int M, H, W, Ho, Wo, Mt;
   int* range_flag;           // range guard: OR-ed with 1 when the 16x stem output or the layer1.conv1 output had to be clamped
 };
-
-__device__ __forceinline__ void split2(float x, float y, unsigned& p1, unsigned& p2) {
-  x = __builtin_amdgcn_fmed3f(x, -65504.f, 65504.f);
-  y = __builtin_amdgcn_fmed3f(y, -65504.f, 65504.f);
-  const f16x2 h = __builtin_convertvector(f32x2{x, y}, f16x2);
-  p1 = __builtin_bit_cast(unsigned, h);
-  // residual x - hi as one mixed-precision fma per value (fma(hi, -1, x): exact; the f16 operand is read from its half of the
-  // packed register) instead of two conversions and a packed subtract: v_pk_add_f32 does not issue while an MFMA runs
-  // (tools/exp/mfma_valu.hip), and this kernel's two waves per SIMD split while the other multiplies
-  float rx, ry;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(rx) : "v"(p1), "v"(x));
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(ry) : "v"(p1), "v"(y));
-  const f16x2 r = __builtin_convertvector(f32x2{rx, ry}, f16x2);
-  p2 = __builtin_bit_cast(unsigned, r);
-}
-
-// non-negative inputs: ReLU and the f16 range clamp are the same v_med3
-__device__ __forceinline__ void split2_relu(float x, float y, unsigned& p1, unsigned& p2) {
-  x = __builtin_amdgcn_fmed3f(x, 0.f, 65504.f);
-  y = __builtin_amdgcn_fmed3f(y, 0.f, 65504.f);
-  const f16x2 h = __builtin_convertvector(f32x2{x, y}, f16x2);
-  p1 = __builtin_bit_cast(unsigned, h);
-  // residual x - hi as one mixed-precision fma per value (fma(hi, -1, x): exact; the f16 operand is read from its half of the
-  // packed register) instead of two conversions and a packed subtract: v_pk_add_f32 does not issue while an MFMA runs
-  // (tools/exp/mfma_valu.hip), and this kernel's two waves per SIMD split while the other multiplies
-  float rx, ry;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(rx) : "v"(p1), "v"(x));
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(ry) : "v"(p1), "v"(y));
-  const f16x2 r = __builtin_convertvector(f32x2{rx, ry}, f16x2);
-  p2 = __builtin_bit_cast(unsigned, r);
-}
 
 constexpr float W0_SCALE = 16.f;    // stem weights (and bias) are split as planes of 16 w: the stem output is carried 16x
                                     // too large (exact; saturates beyond 4094) and layer1.conv1's scale undoes it
@@ -169,7 +135,7 @@ __global__ __launch_bounds__(256, 2) void layer1_fused_kernel(const L1Params p) 
 #pragma unroll
           for (int e = 0; e < 4; e += 2) {
             unsigned p1, p2;
-            split2(val[e], val[e + 1], p1, p2);          // (h1a | h1b << 16), (h2a | h2b << 16)
+            f16x3_split_clamp(val[e], val[e + 1], p1, p2);          // (h1a | h1b << 16), (h2a | h2b << 16)
             const int col = 4 * j + e;
             if (j < nv && col < p.W) dst[col] = __builtin_amdgcn_perm(p2, p1, 0x05040100u);          // h1a | h2a << 16
             if (j < nv && col + 1 < p.W) dst[col + 1] = __builtin_amdgcn_perm(p2, p1, 0x07060302u);  // h1b | h2b << 16
@@ -196,7 +162,7 @@ __global__ __launch_bounds__(256, 2) void layer1_fused_kernel(const L1Params p) 
     }
     unsigned h1[4], h2[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) split2(wv[2 * e], wv[2 * e + 1], h1[e], h2[e]);
+    for (int e = 0; e < 4; ++e) f16x3_split_clamp(wv[2 * e], wv[2 * e + 1], h1[e], h2[e]);
     wa[ks][0] = u32x4{h1[0], h1[1], h1[2], h1[3]};
     wa[ks][1] = u32x4{h2[0], h2[1], h2[2], h2[3]};
   }
@@ -293,8 +259,8 @@ __global__ __launch_bounds__(256, 2) void layer1_fused_kernel(const L1Params p) 
   #pragma unroll
             for (int e = 0; e < 2; ++e) {
               const int g = 2 * ks + e;
-              split2_relu(acc0[4 * g], acc0[4 * g + 1], h1[2 * e], h2[2 * e]);
-              split2_relu(acc0[4 * g + 2], acc0[4 * g + 3], h1[2 * e + 1], h2[2 * e + 1]);
+              f16x3_split_relu(acc0[4 * g], acc0[4 * g + 1], h1[2 * e], h2[2 * e]);
+              f16x3_split_relu(acc0[4 * g + 2], acc0[4 * g + 3], h1[2 * e + 1], h2[2 * e + 1]);
             }
             qa[ks][0] = u32x4{h1[0], h1[1], h1[2], h1[3]};
             qa[ks][1] = u32x4{h2[0], h2[1], h2[2], h2[3]};
@@ -307,8 +273,8 @@ __global__ __launch_bounds__(256, 2) void layer1_fused_kernel(const L1Params p) 
   #pragma unroll
               for (int e = 0; e < 2; ++e) {
                 const int g = 2 * ks + e;
-                split2_relu(acc0[4 * g] * (1.f / W0_SCALE), acc0[4 * g + 1] * (1.f / W0_SCALE), h1[2 * e], h2[2 * e]);
-                split2_relu(acc0[4 * g + 2] * (1.f / W0_SCALE), acc0[4 * g + 3] * (1.f / W0_SCALE), h1[2 * e + 1],
+                f16x3_split_relu(acc0[4 * g] * (1.f / W0_SCALE), acc0[4 * g + 1] * (1.f / W0_SCALE), h1[2 * e], h2[2 * e]);
+                f16x3_split_relu(acc0[4 * g + 2] * (1.f / W0_SCALE), acc0[4 * g + 3] * (1.f / W0_SCALE), h1[2 * e + 1],
                             h2[2 * e + 1]);
               }
               *reinterpret_cast<u32x4*>(o + ks * 4096) = u32x4{h1[0], h1[1], h1[2], h1[3]};
@@ -361,8 +327,8 @@ __global__ __launch_bounds__(256, 2) void layer1_fused_kernel(const L1Params p) 
             v[c] = fmaxf((acc1[4 * g + c] + acc1b[4 * g + c]) * scale1 + bq1[g][c], 0.f);
             clamped |= v[c] > 65504.f;
           }
-          split2(v[0], v[1], h1[2 * e], h2[2 * e]);
-          split2(v[2], v[3], h1[2 * e + 1], h2[2 * e + 1]);
+          f16x3_split_clamp(v[0], v[1], h1[2 * e], h2[2 * e]);
+          f16x3_split_clamp(v[2], v[3], h1[2 * e + 1], h2[2 * e + 1]);
         }
         *reinterpret_cast<u32x4*>(o + ks * 4096) = u32x4{h1[0], h1[1], h1[2], h1[3]};
         *reinterpret_cast<u32x4*>(o + 256 * 32 + ks * 4096) = u32x4{h2[0], h2[1], h2[2], h2[3]};

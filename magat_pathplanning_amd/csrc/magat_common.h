@@ -128,23 +128,7 @@ enum MagatLdsSlot {
 };
 static_assert(MAGAT_LDS_END <= MAGAT_LDS_SLOTS, "LDS attribute slots");
 
-// packed GAT weights: [Bt NC*G | colbias NC | pad to 4][bf16x3 planes 3*NC*G u16 | pad to 4 floats][f16x2 planes of
-// Bt * 2^8: 2*NC*G u16][float 2^-8][pad]: float offset of the f16 block
-__host__ __device__ inline size_t magat_gat_f16_block_offset(int NC, int G) {
-  const size_t a = (((size_t)NC * (G + 1) + 3) & ~(size_t)3) + ((size_t)3 * NC * G + 1) / 2;
-  return (a + 3) & ~(size_t)3;
-}
-
-// fragment-major f16x2 planes of Bt * 2^8 in 128-row blocks (G = 128, NC % 128 == 0; gat_mfma.hip): float offset behind the
-// row-major planes; NC * G more floats
-__host__ __device__ inline size_t magat_gat_frag_offset(int NC, int G) {
-  return (magat_gat_f16_block_offset(NC, G) + (size_t)NC * G + 4 + 3) & ~(size_t)3;
-}
-// bf16-storage CSR layer with the maps inside the graph kernels (gat_csr_fused.hip: KeyQuery, K = 2, G = F = 128, concat):
-// the fragment-major bf16 weights sit behind the one-launch kernel's fragments in the packed block (NC * G / 2 more floats)
-__host__ __device__ inline size_t magat_gat_csr_fused_offset(int NC, int G) {
-  return (magat_gat_frag_offset(NC, G) + (size_t)NC * G + 3) & ~(size_t)3;
-}
+// (the packed graph-layer weights and their offsets: gat_pack.h)
 int magat_gat_csr_fused_supported(int G, int F, int K, int P, int mode, int concat);
 int magat_gat_csr_fused_pack(const float* Bt, void* frag_out, int P, hipStream_t st);
 size_t magat_gat_csr_fused_order_bytes(int B, int N);

@@ -79,6 +79,7 @@ int magat_opt(int id) {
 static int g_experiment_build = 0;
 extern "C" int magat_experiment_mark(void) { g_experiment_build = 1; return 0; }
 extern "C" int magat_build_flavor(void) { return g_experiment_build; }
+extern "C" int magat_abi_version(void) { return 9; }
 
 extern "C" int magat_set_option(const char* name, int value) {
   if (!name) return MAGAT_ERR_NULL;

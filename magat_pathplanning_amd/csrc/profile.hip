@@ -7,6 +7,7 @@
 #include <vector>
 
 #include "magat_common.h"
+#include "f16x3.h"
 
 namespace {
 struct Span {
@@ -103,15 +104,13 @@ extern "C" int magat_profile_reset(void) {
 // 1.67-1.77 GHz, tools/chain_phase_probe.py).  bench.py reports a kernel's ISSUED matrix-core rate against this measured
 // ceiling next to the nominal one.
 namespace {
-typedef _Float16 mp_f16x8 __attribute__((ext_vector_type(8)));
-typedef float mp_f32x16 __attribute__((ext_vector_type(16)));
 __global__ __launch_bounds__(256) void mfma_sustained_kernel(float* out, int iters, long long* stamps) {
   // core-clock counter next to the constant 100 MHz counter, first and last instruction of the wave: the clock the chip HELD
   const long long c0 = (long long)__builtin_readcyclecounter(), r0 = (long long)__builtin_amdgcn_s_memrealtime();
-  mp_f32x16 acc[4];
+  f32x16 acc[4];
   for (int j = 0; j < 4; ++j)
     for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
-  mp_f16x8 a, b;
+  f16x8 a, b;
   for (int i = 0; i < 8; ++i) {      // pseudo-random operand bits: realistic toggling (constant operands draw less power)
     unsigned h = (threadIdx.x * 8 + i + blockIdx.x * 2048) * 2654435761u;
     h ^= h >> 15; h *= 2246822519u; h ^= h >> 13;

@@ -73,18 +73,6 @@ struct Stem8Params {
 #define S8_STAMP(i) do { } while (0)
 #endif
 
-__device__ __forceinline__ void split2s(float x, float y, unsigned& p1, unsigned& p2) {      // signed values (inputs, weights)
-  x = __builtin_amdgcn_fmed3f(x, -65504.f, 65504.f);
-  y = __builtin_amdgcn_fmed3f(y, -65504.f, 65504.f);
-  const f16x2 h = __builtin_convertvector(f32x2{x, y}, f16x2);
-  p1 = __builtin_bit_cast(unsigned, h);
-  float rx, ry;
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel_hi:[1,0,0]" : "=v"(rx) : "v"(p1), "v"(x));
-  asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(ry) : "v"(p1), "v"(y));
-  const f16x2 r = __builtin_convertvector(f32x2{rx, ry}, f16x2);
-  p2 = __builtin_bit_cast(unsigned, r);
-}
-
 template <typename TL>
 __device__ __forceinline__ void stem8_conv1(const Stem8Params& p, char* lds, int group, float scale1, bool& clamped) {
   constexpr int NT = TL::NT;
@@ -117,8 +105,8 @@ __device__ __forceinline__ void stem8_conv1(const Stem8Params& p, char* lds, int
         const int q = 2 * ks + e;
         const f32x2 v01 = __builtin_elementwise_fma(f32x2{acc[s][4 * q], acc[s][4 * q + 1]}, f32x2{scale1, scale1}, f32x2{bq[q][0], bq[q][1]});
         const f32x2 v23 = __builtin_elementwise_fma(f32x2{acc[s][4 * q + 2], acc[s][4 * q + 3]}, f32x2{scale1, scale1}, f32x2{bq[q][2], bq[q][3]});
-        split2(v01[0], v01[1], h1[2 * e], h2[2 * e], cl);
-        split2(v23[0], v23[1], h1[2 * e + 1], h2[2 * e + 1], cl);
+        f16x3_split_relu_max(v01[0], v01[1], h1[2 * e], h2[2 * e], cl);
+        f16x3_split_relu_max(v23[0], v23[1], h1[2 * e + 1], h2[2 * e + 1], cl);
       }
       if (mok) {
         S8_OUT_STORE(o + ks * 4096, (u32x4{h1[0], h1[1], h1[2], h1[3]}));
@@ -174,7 +162,7 @@ __global__ __launch_bounds__(512, 1) void stem8_kernel(const Stem8Params p) {
     }
     unsigned h1[4], h2[4];
 #pragma unroll
-    for (int e = 0; e < 4; ++e) split2s(wv[2 * e], wv[2 * e + 1], h1[e], h2[e]);
+    for (int e = 0; e < 4; ++e) f16x3_split_clamp(wv[2 * e], wv[2 * e + 1], h1[e], h2[e]);
     wa[ty][0] = u32x4{h1[0], h1[1], h1[2], h1[3]};
     wa[ty][1] = u32x4{h2[0], h2[1], h2[2], h2[3]};
   }
@@ -224,8 +212,8 @@ __global__ __launch_bounds__(512, 1) void stem8_kernel(const Stem8Params p) {
       // true for NaN too)
       xbad |= !(__builtin_fabsf(v0) <= 65504.f) || !(__builtin_fabsf(v1) <= 65504.f) || !(__builtin_fabsf(v2) <= 65504.f);
       unsigned h01, l01, h2x, l2x;
-      split2s(v0, v1, h01, l01);
-      split2s(v2, 1.f, h2x, l2x);
+      f16x3_split_clamp(v0, v1, h01, l01);
+      f16x3_split_clamp(v2, 1.f, h2x, l2x);
       char* dst = lds + S8_IN + a * S8_INAG + (y + 1) * S8_ROWB + (x + 1) * 8;
       *reinterpret_cast<uint2*>(dst) = uint2{h01, h2x};
       *reinterpret_cast<uint2*>(dst + S8_INPL) = uint2{l01, l2x};
@@ -289,7 +277,7 @@ __global__ __launch_bounds__(512, 1) void stem8_kernel(const Stem8Params p) {
       unsigned h1[4], h2[4];
       auto epi = [&](int c, const f32x16& acc, char* o) {
         const int ks = c >> 2, e = (c >> 1) & 1, half = c & 1, q = 2 * ks + e;
-        split2(acc[4 * q + 2 * half], acc[4 * q + 2 * half + 1], h1[2 * e + half], h2[2 * e + half], cl);
+        f16x3_split_relu_max(acc[4 * q + 2 * half], acc[4 * q + 2 * half + 1], h1[2 * e + half], h2[2 * e + half], cl);
         if ((c & 3) == 3) {
           *reinterpret_cast<u32x4*>(o + ks * 2 * S8_BLK) = u32x4{h1[0], h1[1], h1[2], h1[3]};
           *reinterpret_cast<u32x4*>(o + ks * 2 * S8_BLK + 4 * S8_BLK) = u32x4{h2[0], h2[1], h2[2], h2[3]};

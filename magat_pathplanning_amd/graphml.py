@@ -351,7 +351,7 @@ def gat_forward_rows(X, S, layer, out=None, want_attention=False, csr=None):
 
 
 def pack_torch(weight, weight_bias, mixer, taps, mode_name):
-    """Differentiable torch twin of pack_kernel (csrc/gat_f32.hip): Bt [NC][G] and column bias [NC]."""
+    """Differentiable torch twin of pack_kernel (csrc/gat_pack.hip; layout: pack_layout in csrc/gat_pack.h): Bt [NC][G] and column bias [NC]."""
     if mode_name == "GAT_origin":          # taps = filterWeight (1,K); h[p,f,k,g] = h_k * W[p,0,g,f]
         P, _, F, G = weight.shape
         K = taps.shape[1]
