@@ -716,6 +716,42 @@ int magat_mfma_sustained_f16_ex(double* tflops, double* clock_mhz, double* per_c
 long long magat_form_count(int id);
 int magat_form_reset(void);
 
+/* ------------------------------------------------------------------------------------------
+ * Expert schedules -> training samples (sim_expert.hip; added behind ABI 9, nothing above changes).  The reference turns
+ * an expert solver's schedule - one path per agent - into imitation samples on the host, per case, per step, per agent
+ * (onlineExpert/DataTransformer_local_onlineExpert.py:181-223, 291-353; utils/new_simulator.py:226-277).  These three
+ * entries do the integer / float64 part for C cases at once; states and GSOs come from magat_sim_fov_states /
+ * magat_sim_guided_states / magat_sim_gso[_radii] on pos viewed as (C*T, N, 2).  Device pointers, stream ordered, no
+ * allocation, no synchronisation; each call counts once in form "sim_expert" and is one span of its profiling tag (schedule:
+ * a memset of `bad` and one kernel; radius: two kernels; stats: one kernel).
+ *
+ * magat_sim_expert_schedule (obtainSchedule): paths (C,N,Lmax,2) int32 (row, col), padded behind lengths (C,N); goal
+ * (C,N,2); makespan (C,).  Case c has T_c = makespan[c] + 1 steps, the caller passes T = max T_c (steps at or behind T are
+ * not produced).  For t < T_c: pos = path[t] (t < L) or the goal, next = path[t + 1] (t < L - 1) or the goal, target = one-hot
+ * index of next - pos in the order up, left, down, right, stop.  pos (C,T,N,2) int32, target (C,T,N,5) float32, valid (C,T)
+ * uint8 (rows at t >= T_c: zeros, valid 0).  A difference that is none of the five moves (the reference raises ValueError)
+ * leaves that target row zero and sets bad[c] = t * N + n of the first such sample in (t, n) order; bad[c] = -1 otherwise. */
+int magat_sim_expert_schedule(const int32_t* paths, const int32_t* lengths, const int32_t* goal, const int32_t* makespan,
+                              int32_t* pos, float* target, uint8_t* valid, int32_t* bad, int C, int N, int Lmax, int T,
+                              void* stream);
+/* magat_sim_expert_radius (DataTransformer.computeAdjacencyMatrix, config.dynamic_commR): the threshold starts at comm_radius
+ * itself, is carried over all steps of a case and multiplied by 1.1 (float64) until every step's graph (distance <
+ * threshold) is connected; that ONE radius serves every step.  pos (C,T,N,2), valid (C,T) (invalid steps are ignored).
+ * step_grow (C,T) int32 scratch / output: the multiplications step t needs on its own (0 at invalid steps, -1: still
+ * disconnected after max_steps).  radii (C,) float64 = comm_radius * 1.1 * ... * 1.1 (grow_steps[c] = max_t step_grow
+ * multiplications in sequence: bit-equal to the reference's chain); grow_steps[c] = -1 when a step stayed disconnected (radii[c]
+ * then holds the radius at the limit).  N <= 5460 (three ints per agent in 64 KB of LDS): more is MAGAT_ERR_UNSUPPORTED. */
+int magat_sim_expert_radius(const int32_t* pos, const uint8_t* valid, double comm_radius, int32_t* step_grow, double* radii,
+                            int32_t* grow_steps, int C, int T, int N, int max_steps, void* stream);
+/* magat_sim_expert_stats (multiRobotSimNew.getPathTarget): follows the argmax actions of target (C,T,N,5) from start (C,N,2)
+ * over the valid steps.  expert_first_move / expert_end_step (C,N) int32: step + 1 of the first non-stop action / of the
+ * first arrival at the goal, 0 when that never happens (the reference's "== 0" tests, reproduced); flowtimeTarget[c] = sum
+ * (end - first + 1), makespanTarget[c] = max end - min first + 1; expert_pos (C,T+1,N,2) int32, row 0 = start (rows behind
+ * an invalid step repeat the last position). */
+int magat_sim_expert_stats(const float* target, const int32_t* start, const int32_t* goal, const uint8_t* valid,
+                           int32_t* expert_first_move, int32_t* expert_end_step, int32_t* makespan_target,
+                           int32_t* flowtime_target, int32_t* expert_pos, int C, int T, int N, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

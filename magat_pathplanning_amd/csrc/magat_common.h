@@ -38,9 +38,11 @@ void magat_form_note(int id);      // which form a launch took (MAGAT_FORM_*; pr
 // Tags and forms added behind an unchanged ABI version are numbered here: MAGAT_PROF_TAGS / MAGAT_FORMS of the public header
 // stay what the bindings of ABI 9 were built against, the library's own tables (profile.hip) hold the *_ALL counts.
 #define MAGAT_TAG_SIM_GUIDED 26     // A*-guided state tensors (sim_guidance.hip)
-#define MAGAT_PROF_TAGS_ALL 27
+#define MAGAT_TAG_SIM_EXPERT 27     // expert schedule -> samples: decode, radius, statistics (sim_expert.hip)
+#define MAGAT_PROF_TAGS_ALL 28
 #define MAGAT_FORM_SIM_GUIDED 16    // magat_sim_guided_states launched its one-wave-per-agent search kernel
-#define MAGAT_FORMS_ALL 17
+#define MAGAT_FORM_SIM_EXPERT 17    // one of the magat_sim_expert_* entries launched (one count per call)
+#define MAGAT_FORMS_ALL 18
 static_assert(MAGAT_PROF_TAGS_ALL >= MAGAT_PROF_TAGS && MAGAT_FORMS_ALL >= MAGAT_FORMS, "internal tag / form tables");
 
 // bf16x6 split-MFMA GEMM (conv_gemm_bf16x6.hip), reached through magat_conv_gemm_f32 when desc->in_fmt == 1

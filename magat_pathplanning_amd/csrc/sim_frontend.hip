@@ -10,6 +10,7 @@
 #include <cstdint>
 
 #include "magat_common.h"
+#include "sim_connect.h"
 
 namespace {
 
@@ -65,18 +66,7 @@ __device__ __forceinline__ double wave_sum_f64(double v) {
 //   (ctz, clear, two dependent reads, an add) was ~120 cycles an edge and as long as the busiest lane's row.
 //   Sturm count: the determinant recurrence p_r = (alpha_r - x) p_{r-1} - beta_r^2 p_{r-2} (sign changes = eigenvalues below x)
 //   instead of the pivot recurrence: no fp64 division on the chain; rescaled every eight rows.
-// The reference's edge test is float64: sqrt(dx^2 + dy^2) < R on integer cell offsets.  The correctly rounded square root is
-// monotone, so the test is "squared distance < q" for one integer q per radius: the smallest q whose rounded root is not below R,
-// found by stepping from floor(R^2) with the very same float64 expression - exact, and no square root per pair.
-__device__ inline long long sim_dist2_bound(double R) {
-  if (!(R > 0.0)) return 0;                                  // sqrt(.) >= 0: nothing is closer than R
-  if (R >= 3.0e9) return 0x7fffffffffffffffLL;               // int32 coordinates: squared distances stay below 2^65 / 4
-  long long q = (long long)floor(R * R);
-  while (q > 0 && !(sqrt((double)(q - 1)) < R)) --q;
-  while (sqrt((double)q) < R) ++q;
-  return q;
-}
-
+// (the float64 edge test as an integer bound on the squared distance: sim_dist2_bound, sim_connect.h)
 __host__ __device__ inline int gso_nbr_words(int N) { return ((N + 3) >> 2) | 1; }      // odd: the lanes' rows fall in different banks
 
 __device__ double gso_lambda_wave(const unsigned* rows, int words, const double* inv, double* u, unsigned* nbr, double* alpha,
@@ -481,8 +471,8 @@ __global__ __launch_bounds__(SIM_THREADS) void fov_states_kernel(const uint8_t* 
 
 // ---- step-0 communication radius (multiRobotSimNew.computeAdjacencyMatrix, step == 0 branch, new_simulator.py:759-768):
 // r = R0 / 1.1;  do { r = r * 1.1;  W = (distance < r) } while (!isConnected(W)).  The reference tests connectivity through
-// the Laplacian's spectrum (graphTools.isConnected: exactly one eigenvalue below 1e-9); here it is a reachability sweep
-// from agent 0 over the same float64 distance test - the same predicate, evaluated exactly.  One workgroup per instance.
+// the Laplacian's spectrum; here it is the reachability sweep of sim_connect.h (shared with sim_expert.hip).  One workgroup per
+// instance.
 __global__ __launch_bounds__(SIM_THREADS) void sim_radius_kernel(const int* __restrict__ pos, double R0,
                                                                  double* __restrict__ radii_out, int* __restrict__ steps_out,
                                                                  int N, int max_steps) {
@@ -503,32 +493,7 @@ __global__ __launch_bounds__(SIM_THREADS) void sim_radius_kernel(const int* __re
     r = r * 1.1;
     ++steps;
     const long long d2_bound = sim_dist2_bound(r);
-    __syncthreads();
-    for (int n = t; n < N; n += nt) seen[n] = n == 0 ? 1 : 0;
-    while (true) {
-      __syncthreads();
-      if (t == 0) changed = 0;
-      __syncthreads();
-      for (int i = t; i < N; i += nt) {
-        if (seen[i]) continue;
-        bool hit = false;
-        for (int j = 0; j < N && !hit; ++j) {
-          if (!seen[j] || j == i) continue;
-          const long long dx = px[i] - px[j], dy = py[i] - py[j];
-          hit = dx * dx + dy * dy < d2_bound;
-        }
-        if (hit) { seen[i] = 1; changed = 1; }
-      }
-      __syncthreads();
-      if (!changed) break;
-    }
-    if (t == 0) count = 0;
-    __syncthreads();
-    int c = 0;
-    for (int n = t; n < N; n += nt) c += seen[n];
-    if (c) atomicAdd(&count, c);
-    __syncthreads();
-    connected = count == N;
+    connected = sim_graph_connected(px, py, seen, &changed, &count, N, d2_bound, t, nt);
   }
   if (t == 0) {
     radii_out[b] = r;
