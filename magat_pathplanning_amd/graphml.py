@@ -50,10 +50,40 @@ def _param_key(*tensors):
     return tuple((t.data_ptr(), t._version, str(t.device)) for t in tensors)
 
 
+def _require_device(t, path="HIP GAT path"):
+    if not t.is_cuda:
+        raise nat.MagatNativeError("the %s needs device tensors; got %s (no CPU fallback)" % (path, t.device))
+
+
+def _gso3(S, B, N, dev):
+    """GSO intake of every route: S (B,N,N) | (B,1,N,N) of any dtype, anywhere -> contiguous (B,N,N) float32 | float64 on `dev`
+    (anything that is not f32 / f64 is widened to float32).  A tensor that already is all of that comes back as a VIEW of
+    itself - same data_ptr(), same _version: CsrStructure.matches keys on both, and a copy here would throw away the structure
+    built at addGSO time (a re-build and a host wait on every step of config 5)."""
+    S3 = S.reshape(B, N, N)
+    return S3.to(dev, S3.dtype if S3.dtype in (torch.float32, torch.float64) else torch.float32).contiguous()
+
+
+def _edge_rows(rowptr, B, N):
+    """Row index (0 .. B*N-1) of every stored edge, in CSR order, from the absolute offsets rowptr [B*(N+1)]."""
+    rp = rowptr.view(B, N + 1).long()
+    return torch.repeat_interleave(torch.arange(B * N, device=rowptr.device), (rp[:, 1:] - rp[:, :-1]).reshape(-1))
+
+
+def _flat_bias(layer, dev):
+    """The layer's bias (F,1) as the kernels read it: F contiguous float32 on `dev`, or None."""
+    return None if layer.bias is None else layer.bias.detach().to(dev, torch.float32).reshape(-1).contiguous()
+
+
+def _packed_cols(mode_name, G, F, K, P):
+    """NC: rows of the packed matrix Bt [NC][G] (pack_layout in csrc/gat_pack.h) = columns of the layer's one dense product."""
+    return P * G + P * K * F if mode_name == "KeyQuery" else (P * K * F + 2 * P + 31) // 32 * 32
+
+
 def _packed_weights(layer, dev, stream, G, F, K, P, mode):
     lib = nat.lib()
     sc = layer._scratch
-    tensors = layer._pack_tensors()          # (weight, weight_bias | None, mixer, taps)
+    tensors = layer._pack_tensors()          # (weight, weight_bias | None, mixer, taps); GraphFilterBatch: taps alone
     key = _param_key(*[t for t in tensors if t is not None]) + (str(dev),)
     if sc.packed is None or sc.packed_key != key:
         nfl = lib.magat_gat_packed_floats(G, F, K, P, mode)
@@ -221,8 +251,7 @@ def gat_forward_rows_csr(X, rowptr, colidx, nnz, layer, out=None, want_attention
     the index arrays were allocated with (the kernels use it as a stride / for sizing only).  csc: optional
     (cscptr, cscsrc, cscpos) made by magat_gso_csr_build - skips the per-call transpose.
     Returns (out (B*N, ld), att (P, nnz) CSR-ordered fp32 attention or None)."""
-    if not X.is_cuda:
-        raise nat.MagatNativeError("the HIP GAT path needs device tensors; got %s (no CPU fallback)" % X.device)
+    _require_device(X)
     lib = nat.lib()
     B, N, G = X.shape
     F, K, P = layer.F, layer.K, layer.P
@@ -249,7 +278,7 @@ def gat_forward_rows_csr(X, rowptr, colidx, nnz, layer, out=None, want_attention
             raise TypeError("out must be %s for %s rows" % (sdt, X.dtype))
         f32out = bf16 and out.dtype == torch.float32      # the last kernel widens the bf16-rounded result itself
         att = torch.empty(P, max(nnz, 1), dtype=torch.float32, device=dev) if want_attention else None
-        bias = None if layer.bias is None else layer.bias.detach().to(dev, torch.float32).reshape(-1).contiguous()
+        bias = _flat_bias(layer, dev)
         tail = (nnz, nat.ptr(packed), nat.ptr(bias), nat.ptr(out), out.stride(0), nat.ptr(att), nat.ptr(sc.workspace),
                 sc.workspace.numel(), B, N, G, F, K, P, mode, concat, stream)
         if csc is not None:
@@ -267,12 +296,8 @@ def gat_forward_rows_csr(X, rowptr, colidx, nnz, layer, out=None, want_attention
 
 def _csr_attention_to_dense(att, rowptr, colidx, nnz, B, N, P):
     """(P,nnz) CSR-ordered attention -> (B,P,1,N,N) dense, only for returnAttentionGSO() callers."""
-    dev = att.device
-    rp = rowptr.view(B, N + 1).long()
-    deg = (rp[:, 1:] - rp[:, :-1]).reshape(-1)
-    rows = torch.repeat_interleave(torch.arange(B * N, device=dev), deg)
-    dense = torch.zeros(P, B * N, N, dtype=torch.float32, device=dev)
-    dense[:, rows, colidx[:nnz].long()] = att[:, :nnz]
+    dense = torch.zeros(P, B * N, N, dtype=torch.float32, device=att.device)
+    dense[:, _edge_rows(rowptr, B, N), colidx[:nnz].long()] = att[:, :nnz]
     return dense.view(P, B, N, N).permute(1, 0, 2, 3).unsqueeze(2).contiguous()
 
 
@@ -292,8 +317,7 @@ def gat_forward_rows(X, S, layer, out=None, want_attention=False, csr=None):
     out: optional (B*N, ld) float32 view whose first P*F|F columns receive the result.
     csr: optional CsrStructure made from this S at addGSO time (large-graph / bf16-storage path).
     Returns (out (B*N, ld) with the result in columns [0, width), aij (B,P,1,N,N) device tensor or None)."""
-    if not X.is_cuda:
-        raise nat.MagatNativeError("the HIP GAT path needs device tensors; got %s (no CPU fallback)" % X.device)
+    _require_device(X)
     lib = nat.lib()
     B, N, G = X.shape
     F, K, P = layer.F, layer.K, layer.P
@@ -306,31 +330,23 @@ def gat_forward_rows(X, S, layer, out=None, want_attention=False, csr=None):
     bf16 = X.dtype == torch.bfloat16           # bf16 storage: always the CSR kernels (the LDS kernel is fp32-only)
     if X.dtype != torch.float32 and not bf16:
         X = X.float()
-    S3 = S.reshape(B, N, N)
-    if S3.dtype not in (torch.float32, torch.float64):
-        S3 = S3.float()
-    if not S3.is_contiguous():
-        S3 = S3.contiguous()
-    if S3.device != X.device:
-        S3 = S3.to(X.device)
     dev = X.device
+    S3 = _gso3(S, B, N, dev)
     sc = layer._scratch
     if bf16 or not dense_route(N, layer, want_attention) or (out is not None and out.data_ptr() % 16):
         # graph too large for the LDS-resident kernel (or bf16 storage): same layer through the CSR kernels
-        rule = 1 if layer.attentionMode == "GAT_origin" else 0
+        rule, csc = layer.edge_rule, None
         if CsrStructure.supported(B, N):
             # structure made on the device, no host synchronisation: at addGSO time (csr), or here
             if csr is None or not csr.matches(S3, rule):
-                if layer._scratch.csr is None:
-                    layer._scratch.csr = CsrStructure()
-                csr = layer._scratch.csr.build(S3, rule)
-            nnz = csr.ready(X.device)
-            out, att = gat_forward_rows_csr(X, csr.rowptr, csr.colidx, nnz, layer, out=out,
-                                            want_attention=want_attention, csc=(csr.cscptr, csr.csc[0], csr.csc[1]))
-            aij = _csr_attention_to_dense(att, csr.rowptr, csr.colidx, nnz, B, N, P) if want_attention else None
-            return out, aij
-        rowptr, colidx, nnz = dense_gso_to_csr(S3, self_loops=layer.attentionMode == "GAT_origin")
-        out, att = gat_forward_rows_csr(X, rowptr, colidx, nnz, layer, out=out, want_attention=want_attention)
+                if sc.csr is None:
+                    sc.csr = CsrStructure()
+                csr = sc.csr.build(S3, rule)
+            nnz = csr.ready(dev)
+            rowptr, colidx, csc = csr.rowptr, csr.colidx, (csr.cscptr, csr.csc[0], csr.csc[1])
+        else:
+            rowptr, colidx, nnz = dense_gso_to_csr(S3, self_loops=rule)
+        out, att = gat_forward_rows_csr(X, rowptr, colidx, nnz, layer, out=out, want_attention=want_attention, csc=csc)
         aij = _csr_attention_to_dense(att, rowptr, colidx, nnz, B, N, P) if want_attention else None
         return out, aij
     with torch.cuda.device(dev):
@@ -342,7 +358,7 @@ def gat_forward_rows(X, S, layer, out=None, want_attention=False, csr=None):
             out = torch.empty(B * N, width, dtype=torch.float32, device=dev)
         ldy = out.stride(0)
         aij = torch.empty(B, P, 1, N, N, dtype=torch.float32, device=dev) if want_attention else None
-        bias = None if layer.bias is None else layer.bias.detach().to(dev, torch.float32).reshape(-1).contiguous()
+        bias = _flat_bias(layer, dev)
         nat.check(lib.magat_gat_forward_planned_f32(
             nat.ptr(X), nat.ptr(S3), 1 if S3.dtype == torch.float64 else 0, nat.ptr(sc.packed), nat.ptr(bias),
             nat.ptr(out), ldy, nat.ptr(aij), nat.ptr(sc.workspace), sc.workspace.numel(),
@@ -359,13 +375,13 @@ def pack_torch(weight, weight_bias, mixer, taps, mode_name):
     else:
         P, F, _, K, G = taps.shape
         U = taps[:, :, 0].permute(0, 2, 1, 3).reshape(P * K * F, G)
+    nc = _packed_cols(mode_name, G, F, K, P)
     if mode_name == "KeyQuery":
         Bt = torch.cat((weight[:, 0].reshape(P * G, G), U), dim=0)
-        return Bt, torch.zeros(Bt.shape[0], dtype=Bt.dtype, device=Bt.device)
+        return Bt, torch.zeros(nc, dtype=Bt.dtype, device=Bt.device)
     W = weight[:, 0]                                            # (P,F,G)
     a1, a2 = mixer[:, 0, :F], mixer[:, 0, F:]
     v1, v2 = torch.einsum("pf,pfg->pg", a1, W), torch.einsum("pf,pfg->pg", a2, W)
-    nc = (P * K * F + 2 * P + 31) // 32 * 32
     pad = torch.zeros(nc - P * K * F - 2 * P, G, dtype=U.dtype, device=U.device)
     Bt = torch.cat((U, v1, v2, pad), dim=0)
     if weight_bias is None:
@@ -409,8 +425,7 @@ class _GatTrainFunction(torch.autograd.Function):
         with torch.cuda.device(dev):
             stream = nat.current_stream(dev)
             packed = _packed_weights(layer, dev, stream, G, F, K, P, mode)
-            nc = (lib.magat_gat_packed_floats(G, F, K, P, mode) - 0)  # total floats; NC recovered below
-            NC = P * G + P * K * F if mode == nat.MODE_KEYQUERY else (P * K * F + 2 * P + 31) // 32 * 32
+            NC = _packed_cols(layer.attentionMode, G, F, K, P)
             Ypre = torch.empty(M, P * F, dtype=torch.float32, device=dev)
             att = torch.empty(P, max(nnz, 1), dtype=torch.float32, device=dev)
             Z = torch.empty(M, NC, dtype=torch.float32, device=dev)
@@ -513,6 +528,27 @@ def _is_relu(fn):
     return fn is nn.functional.relu or fn is torch.relu or isinstance(fn, nn.ReLU)
 
 
+class _DropsDeviceState:
+    """Pickling (and deepcopy) of a graph layer leaves its device state behind: the copy starts with a fresh _Scratch, no
+    attention tensor and no edge views."""
+
+    def __getstate__(self):
+        st = self.__dict__.copy()
+        st.update(_scratch=None, aij=None, _edge_views=None)
+        return st
+
+    def __setstate__(self, st):
+        super().__setstate__(st)
+        self._scratch = _Scratch()
+
+
+def _register_bias(layer, bias):
+    if bias:
+        layer.bias = nn.Parameter(torch.empty(layer.F, 1))
+    else:
+        layer.register_parameter("bias", None)
+
+
 class _EdgeView:
     """Edge feature e of a layer as an E = 1 layer: the parameter slices (views: gradients reach the parameters) and its own
     packed-weights cache."""
@@ -529,7 +565,7 @@ class _EdgeView:
         return w[:, e:e + 1], None if wb is None else wb[:, e:e + 1], mx[:, e:e + 1], tp_e
 
 
-class GraphFilterBatchAttentional(nn.Module):
+class GraphFilterBatchAttentional(_DropsDeviceState, nn.Module):
     """Drop-in for the reference class of the same name (graphML.py:4506-4685)."""
 
     _edge_views = None
@@ -547,29 +583,33 @@ class GraphFilterBatchAttentional(nn.Module):
         self.concatenate = concatenate
         self.attentionMode = attentionMode
         self.return_attention = False      # materialise aij (B,P,E,N,N) like graphML.py:4650 only on request
+        self._scratch = _Scratch()
+        self._register_parameters(bias)
+        self.reset_parameters()
+
+    def _register_parameters(self, bias):
+        # (the order of registration is the order of the state_dict: mixer, weight_bias, filterWeight, bias, weight)
+        G, F, K, P, E = self.G, self.F, self.K, self.P, self.E
         self.mixer = nn.Parameter(torch.empty(P, E, 2 * F))
         self.weight_bias = nn.Parameter(torch.empty(P, E, F))
         self.filterWeight = nn.Parameter(torch.empty(P, F, E, K, G))
-        if bias:
-            self.bias = nn.Parameter(torch.empty(F, 1))
-        else:
-            self.register_parameter("bias", None)
-        if attentionMode == "KeyQuery":
-            self.weight = nn.Parameter(torch.empty(P, E, G, G))
-        else:
-            self.weight = nn.Parameter(torch.empty(P, E, F, G))
-        self._scratch = _Scratch()
-        self.reset_parameters()
+        _register_bias(self, bias)
+        self.weight = nn.Parameter(torch.empty(P, E, G if self.attentionMode == "KeyQuery" else F, G))
 
     # torch.float32 (default) or torch.bfloat16: HBM storage type of the node features inside the layer at inference
     # (BASELINE config 5).  bf16 always takes the CSR kernels; arithmetic stays fp32.  Not part of the state_dict.
     storage_dtype = torch.float32
 
+    @property
+    def edge_rule(self):
+        """Edge rule of the CSR builders (magat_gso_row_degrees): 0 |S| > 1e-9, 1 GAT_origin's |float(S) + I| > 1e-9."""
+        return 1 if self.attentionMode == "GAT_origin" else 0
+
     def _pack_tensors(self):
         return self.weight, self.weight_bias, self.mixer, self.filterWeight
 
     def reset_parameters(self):
-        # graphML.py:4604-4612
+        # graphML.py:4604-4612 (draw order: weight, mixer, filterWeight, bias)
         stdv = 1.0 / math.sqrt(self.G * self.P)
         with torch.no_grad():
             self.weight.uniform_(-stdv, stdv)
@@ -578,17 +618,6 @@ class GraphFilterBatchAttentional(nn.Module):
             self.filterWeight.uniform_(-stdv, stdv)
             if self.bias is not None:
                 self.bias.uniform_(-stdv, stdv)
-
-    def __getstate__(self):
-        st = self.__dict__.copy()
-        st["_scratch"] = None
-        st["aij"] = None
-        st["_edge_views"] = None
-        return st
-
-    def __setstate__(self, st):
-        super().__setstate__(st)
-        self._scratch = _Scratch()
 
     def addGSO(self, S):
         assert len(S.shape) == 4
@@ -615,10 +644,7 @@ class GraphFilterBatchAttentional(nn.Module):
         elif needs_grad and x.is_cuda and not self.return_attention:
             # training on the GPU: HIP forward + backward of the graph layer (CSR kernels), ReLU / head merge in torch
             N = self.N
-            S3 = self.S.reshape(B, N, N).to(x.device)
-            if S3.dtype not in (torch.float32, torch.float64):
-                S3 = S3.float()
-            rowptr, colidx, nnz = dense_gso_to_csr(S3.contiguous(), self_loops=self.attentionMode == "GAT_origin")
+            rowptr, colidx, nnz = dense_gso_to_csr(_gso3(self.S, B, N, x.device), self_loops=self.edge_rule)
             w_, wb_, mx_, tp_ = self._pack_tensors()
             Ypre, _ = _GatTrainFunction.apply(x.permute(0, 2, 1).contiguous(), w_, wb_, mx_, tp_, self.bias, rowptr,
                                               colidx, nnz, self)
@@ -655,17 +681,13 @@ class GraphFilterBatchAttentional(nn.Module):
                                        "kernels: move the module and its input to the GPU")
         B, _, N = x.shape
         P, F, E = self.P, self.F, self.E
-        S = self.S.to(x.device)
-        if S.dtype not in (torch.float32, torch.float64):
-            S = S.float()
-        origin = self.attentionMode == "GAT_origin"
-        if E == 1:
-            Su, loops = S.reshape(B, N, N), origin
-        elif origin:
-            Su, loops = (S.float() + torch.eye(N, dtype=torch.float32, device=S.device).view(1, 1, N, N)).abs().sum(dim=1), False
-        else:
-            Su, loops = S.abs().sum(dim=1), False
-        rowptr, colidx, nnz = dense_gso_to_csr(Su.contiguous(), self_loops=loops)
+        Su, rule = _gso3(self.S, B * E, N, x.device), self.edge_rule
+        if E > 1:           # the union mask as a GSO of its own, under the plain rule (GAT_origin's self-loops are in the sum)
+            Su = Su.view(B, E, N, N)
+            if rule:
+                Su = Su.float() + torch.eye(N, dtype=torch.float32, device=Su.device)
+            Su, rule = Su.abs().sum(dim=1), 0
+        rowptr, colidx, nnz = dense_gso_to_csr(Su, self_loops=rule)
         rows = x.permute(0, 2, 1).contiguous()
         if self._edge_views is None or len(self._edge_views) != E:
             self._edge_views = [_EdgeView(self, e) for e in range(E)]
@@ -675,16 +697,9 @@ class GraphFilterBatchAttentional(nn.Module):
             Ye, att = _GatTrainFunction.apply(rows, w_, wb_, mx_, tp_, self.bias if e == 0 else None, rowptr, colidx, nnz, view)
             Ypre = Ye if Ypre is None else Ypre + Ye
             atts.append(att)
-        if self.return_attention:
-            rp = rowptr.view(B, N + 1)
-            deg = (rp[:, 1:] - rp[:, :-1]).reshape(-1).long()
-            r = torch.repeat_interleave(torch.arange(B * N, device=x.device), deg)
-            A = torch.zeros(P, E, B * N, N, dtype=torch.float32, device=x.device)
-            for e, att in enumerate(atts):
-                A[:, e, r, colidx[:nnz].long()] = att[:, :nnz]
-            self.aij = A.view(P, E, B, N, N).permute(2, 0, 1, 3, 4).contiguous()
-        else:
-            self.aij = None
+        self.aij = None
+        if self.return_attention:       # (B,P,E,N,N): one dense tensor per edge feature, side by side on the E axis
+            self.aij = torch.cat([_csr_attention_to_dense(att, rowptr, colidx, nnz, B, N, P) for att in atts], dim=2)
         y = Ypre.view(B, N, P, F).permute(0, 2, 3, 1)                  # B x P x F x N, as graphML.py:4650 hands it over
         if self.concatenate:
             y = self.nonlinearity(y)
@@ -707,31 +722,23 @@ class GraphFilterBatchAttentional_Origin(GraphFilterBatchAttentional):
 
     def __init__(self, G, F, K, P, E=1, bias=True, nonlinearity=nn.functional.relu, concatenate=True,
                  attentionMode="GAT_origin"):
-        nn.Module.__init__(self)
         if G != F:
             raise NotImplementedError("GAT_origin needs F == G (the reference reshapes W (P,G,E,F) into (P,F,E,1,G))")
-        self.G, self.F, self.K, self.P, self.E = G, F, K, P, E
-        self.S = None
-        self.aij = None
-        self.nonlinearity = nonlinearity
-        self.concatenate = concatenate
-        self.attentionMode = "GAT_origin"
-        self.return_attention = False
+        super().__init__(G, F, K, P, E, bias, nonlinearity, concatenate, "GAT_origin")
+
+    def _register_parameters(self, bias):
+        # (state_dict order: mixer, weight, filterWeight, bias)
+        G, F, K, P, E = self.G, self.F, self.K, self.P, self.E
         self.mixer = nn.Parameter(torch.empty(P, E, 2 * F))
         self.weight = nn.Parameter(torch.empty(P, E, F, G))
         self.filterWeight = nn.Parameter(torch.empty(E, K))
-        if bias:
-            self.bias = nn.Parameter(torch.empty(F, 1))
-        else:
-            self.register_parameter("bias", None)
-        self._scratch = _Scratch()
-        self.reset_parameters()
+        _register_bias(self, bias)
 
     def _pack_tensors(self):
         return self.weight, None, self.mixer, self.filterWeight
 
     def reset_parameters(self):
-        # graphML.py:4259-4266
+        # graphML.py:4259-4266 (draw order: weight, mixer, filterWeight, bias)
         stdv = 1.0 / math.sqrt(self.G * self.P)
         with torch.no_grad():
             self.weight.uniform_(-stdv, stdv)
@@ -780,7 +787,7 @@ class _GnnTrainFunction(torch.autograd.Function):
         return dx, dw, db, None
 
 
-class GraphFilterBatch(nn.Module):
+class GraphFilterBatch(_DropsDeviceState, nn.Module):
     """Drop-in for the reference's non-attentional graph filter (graphML.py:5581-5700; BatchLSIGF :5485-5579), the GNN
     baseline of the paper:  y = bias + sum_k (x S^k) h_k  with the GSO VALUES as edge weights (`x @ S.float()`), no
     nonlinearity inside.  Parameters: weight (F,E,K,G), bias (F,1); init U(+-1/sqrt(G K)).  Inference on the HIP CSR kernels
@@ -794,12 +801,14 @@ class GraphFilterBatch(nn.Module):
         self.G, self.F, self.K, self.E = G, F, K, E
         self.S = None
         self.weight = nn.Parameter(torch.empty(F, E, K, G))
-        if bias:
-            self.bias = nn.Parameter(torch.empty(F, 1))
-        else:
-            self.register_parameter("bias", None)
+        _register_bias(self, bias)
         self._scratch = _Scratch()
         self.reset_parameters()
+
+    edge_rule = 2           # every non-zero float(S) is an edge, and its value the edge's weight
+
+    def _pack_tensors(self):
+        return None, None, None, self.weight
 
     def reset_parameters(self):
         stdv = 1.0 / math.sqrt(self.G * self.K)       # graphML.py:5654-5659
@@ -812,11 +821,6 @@ class GraphFilterBatch(nn.Module):
         assert len(S.shape) == 4 and S.shape[1] == self.E and S.shape[2] == S.shape[3]     # graphML.py:5661-5668
         self.N = S.shape[2]
         self.S = S
-
-    def __getstate__(self):
-        d = self.__dict__.copy()
-        d["_scratch"] = _Scratch()
-        return d
 
     def forward(self, x):
         B, Gin, Nin = x.shape
@@ -846,21 +850,15 @@ class GraphFilterBatch(nn.Module):
     def _csr(self, dev, B):
         """CSR arrays of float(S) (every non-zero entry, values kept) for the HIP kernels."""
         N = self.N
-        S3 = self.S.reshape(B, N, N).to(dev)
-        if S3.dtype not in (torch.float32, torch.float64):
-            S3 = S3.float()
-        S3 = S3.contiguous()
-        rowptr, colidx, nnz = dense_gso_to_csr(S3, self_loops=2)          # rule 2: every non-zero float(S)
-        rp = rowptr.view(B, N + 1).long()
-        rows = torch.repeat_interleave(torch.arange(B * N, device=dev), (rp[:, 1:] - rp[:, :-1]).reshape(-1))
-        vals = S3.reshape(B * N, N)[rows, colidx[:nnz].long()].float().contiguous() if nnz else \
+        S3 = _gso3(self.S, B, N, dev)
+        rowptr, colidx, nnz = dense_gso_to_csr(S3, self_loops=self.edge_rule)
+        vals = S3.reshape(B * N, N)[_edge_rows(rowptr, B, N), colidx[:nnz].long()].float().contiguous() if nnz else \
             torch.zeros(1, dtype=torch.float32, device=dev)
         return rowptr, colidx, vals, nnz
 
     def _forward_hip(self, x):
         """x (B,G,N) device tensor -> (y (B,F,N) view, X rows (M,G), csr) on the HIP CSR kernels."""
-        if not x.is_cuda:
-            raise nat.MagatNativeError("the HIP path needs device tensors; got %s (no CPU fallback)" % x.device)
+        _require_device(x, "HIP path")
         lib = nat.lib()
         dev = x.device
         B, _, N = x.shape
@@ -869,18 +867,11 @@ class GraphFilterBatch(nn.Module):
         sc = self._scratch
         with torch.cuda.device(dev):
             stream = nat.current_stream(dev)
-            key = _param_key(self.weight) + (str(dev),)
-            if sc.packed is None or sc.packed_key != key:
-                nfl = lib.magat_gat_packed_floats(self.G, self.F, self.K, 1, nat.MODE_GNN)
-                sc.packed = torch.empty(nfl, dtype=torch.float32, device=dev)
-                w = self.weight.detach().to(dev, torch.float32).contiguous()
-                nat.check(lib.magat_gat_pack_weights(None, None, None, nat.ptr(w), nat.ptr(sc.packed), self.G, self.F,
-                                                     self.K, 1, nat.MODE_GNN, stream), "magat_gat_pack_weights")
-                sc.packed_key = key
+            _packed_weights(self, dev, stream, self.G, self.F, self.K, 1, nat.MODE_GNN)
             need = lib.magat_gat_csr_workspace_bytes(B, N, nnz, self.G, self.F, self.K, 1, nat.MODE_GNN, 1)
             _workspace(sc, need, dev)
             out = torch.empty(B * N, self.F, dtype=torch.float32, device=dev)
-            bias = None if self.bias is None else self.bias.detach().to(dev, torch.float32).reshape(-1).contiguous()
+            bias = _flat_bias(self, dev)
             nat.check(lib.magat_gnn_forward_csr_f32(
                 nat.ptr(X), nat.ptr(rowptr), nat.ptr(colidx), nat.ptr(vals), nnz, nat.ptr(sc.packed), nat.ptr(bias),
                 nat.ptr(out), out.stride(0), nat.ptr(sc.workspace), sc.workspace.numel(), B, N, self.G, self.F,

@@ -33,8 +33,8 @@ import torch.nn as nn
 
 from . import _native as nat
 from . import encoder as enc
-from .graphml import (_MODES, CsrStructure, dense_route, GraphFilterBatchAttentional, GraphFilterBatchAttentional_Origin,
-                      gat_forward_rows)
+from .graphml import (_MODES, _flat_bias, _gso3, CsrStructure, dense_route, GraphFilterBatchAttentional,
+                      GraphFilterBatchAttentional_Origin, gat_forward_rows)
 from .resnet import ResNet, ResNetSlim
 
 # config.bottleneckMode -> what the reference file of that name feeds the action MLP (the GAT files ..._GAT_bottleneck*.py
@@ -625,7 +625,7 @@ class DecentralPlannerGATNet(_PlannerBase):
                      not dense_route(N_, layer)) and CsrStructure.supported(B_, N_)):
                 # large graph / bf16 storage: the layer runs on the CSR kernels.  ONE pass over S does the scrub and leaves
                 # the bit matrix the CSR + CSC structure is built from (no host synchronisation, nothing re-read later)
-                self._rt.csr.build(S, 1 if layer.attentionMode == "GAT_origin" else 0, scrub_nan=scrub, gso_mode=gso_mode)
+                self._rt.csr.build(S, layer.edge_rule, scrub_nan=scrub, gso_mode=gso_mode)
                 self.S = S.unsqueeze(1)
                 return
             self._rt.csr.key = None
@@ -685,7 +685,7 @@ class DecentralPlannerGATNet(_PlannerBase):
         pl.rt_key, pl.B, pl.N, pl.dev, pl.dev_index = rt.key, B, N, dev, dev.index
         pl.ws, pl.gws, pl.packed, pl.x_scale = rt.ws, sc.workspace, sc.packed, sc.x_scale
         pl.feat, pl.comp, pl.gat = feat, comp, gat
-        pl.bias = None if layer.bias is None else layer.bias.detach().to(dev, torch.float32).reshape(-1).contiguous()
+        pl.bias = _flat_bias(layer, dev)
         F, K, P = layer.F, layer.K, layer.P
         mode = _MODES[layer.attentionMode]
         concat = 1 if layer.concatenate else 0
@@ -1002,11 +1002,9 @@ class DecentralPlannerBottleneckNet(DecentralPlannerNet):
             Ns = S.shape[-1]
             self._check_gso_shape(B, N)
             rows = self._buf("gat", (M, self.gat_width), dev)
-            S3 = S.reshape(B, Ns, Ns)
-            if S3.device != dev or S3.dtype not in (torch.float32, torch.float64) or not S3.is_contiguous():
-                S3 = S3.to(dev, torch.float32 if S3.dtype not in (torch.float32, torch.float64) else S3.dtype).contiguous()
+            S3 = _gso3(S, B, Ns, dev)
             w = layer.weight.detach().to(dev, torch.float32).contiguous()
-            b = None if layer.bias is None else layer.bias.detach().to(dev, torch.float32).contiguous()
+            b = _flat_bias(layer, dev)
             # graph layer + its ReLU (GFL.1) in one launch: no CSR structure, no host round trip
             rc = nat.lib().magat_gnn_forward_dense_f32(nat.ptr(comp), comp.stride(0), nat.ptr(S3),
                                                        1 if S3.dtype == torch.float64 else 0, nat.ptr(w), nat.ptr(b),

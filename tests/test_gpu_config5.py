@@ -319,3 +319,31 @@ def test_config5_model_bf16_at_1000_agents(gpu_device):
         net32.addGSO(S.to(gpu_device))
         got32 = net32(x.to(gpu_device)).cpu()
     assert (got32 - ref).abs().max().item() <= 1e-4
+
+
+def test_gat_forward_rows_keeps_the_structure_built_at_addgso_time(gpu_device):
+    """The structure is keyed on the GSO's data_ptr() and _version (CsrStructure.matches): the layer's GSO intake must hand a
+    contiguous device f32 GSO - here as the (B,1,N,N) view the model stores - back as itself, or every step would re-build
+    the structure and wait for its edge count.  Proof by state: the key stays, the layer never builds a structure of its own."""
+    from magat_pathplanning_amd.graphml import CsrStructure, GraphFilterBatchAttentional, dense_route, gat_forward_rows
+    from magat_pathplanning_amd.synthetic import comm_gso
+    B, N, G, K, P = 2, 130, 16, 2, 2                       # 130 agents: just past the LDS-resident kernels
+    torch.manual_seed(5)
+    layer = GraphFilterBatchAttentional(G, G, K, P, attentionMode="KeyQuery").to(gpu_device).eval()
+    assert not dense_route(N, layer) and CsrStructure.supported(B, N)
+    S = comm_gso(B, N, 40, seed=11, dtype=torch.float32).to(gpu_device)
+    X = torch.randn(B, N, G, device=gpu_device)
+    csr = CsrStructure().build(S, layer.edge_rule)         # "addGSO time"
+    key = csr.key
+    outs = []
+    with torch.no_grad():
+        for _ in range(2):
+            assert csr.matches(S, layer.edge_rule)
+            out, _ = gat_forward_rows(X, S.view(B, 1, N, N), layer, csr=csr)
+            outs.append(out.clone())
+    torch.cuda.synchronize()
+    assert csr.key == key and csr.matches(S, layer.edge_rule)
+    assert layer._scratch.csr is None
+    assert csr.nnz == int((S.abs() > 1e-9).sum())
+    assert outs[0].shape == (B * N, P * G) and bool(torch.isfinite(outs[0]).all()) and float(outs[0].abs().max()) > 0
+    assert torch.equal(outs[0], outs[1])
