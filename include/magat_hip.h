@@ -752,6 +752,32 @@ int magat_sim_expert_stats(const float* target, const int32_t* start, const int3
                            int32_t* expert_first_move, int32_t* expert_end_step, int32_t* makespan_target,
                            int32_t* flowtime_target, int32_t* expert_pos, int C, int T, int N, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * A multi-agent path-finding expert (sim_mapf.hip; added behind ABI 9, nothing above changes): prioritized planning with an
+ * exact space-time search per agent, for C cases at once - the schedules that magat_sim_expert_schedule takes.  It is NOT
+ * ECBS: no bound on the flowtime, and a case can stay unsolved in a given priority order (the caller retries with another).
+ * Device pointers, stream ordered, no allocation, no synchronisation; one kernel, one count in form "sim_mapf", one span of its
+ * profiling tag.
+ *
+ * map (H,W) or (C,H,W) uint8 (non-zero: obstacle), start / goal (C,N,2) int32 (row, col), order (C,N) int32: the priority
+ * order of each case, a permutation of 0..N-1 (NULL: index order).  T: the horizon, every path has at most T cells.  Agents
+ * are planned one after another against the reservations of those before them: R_0 = {start}, R_{t+1} = free & ~V[t+1] &
+ * (R_t | U_d shift_d(R_t & ~A_opp(d)[t+1])) (V[t]: cells held at t, A_d[t]: cells entered at t in direction d; the A term
+ * forbids swaps); the agent arrives at t* = the first t with the goal in R_t behind the last t at which a planned agent holds
+ * the goal, and holds it from then on; its path is traced back taking the first of up, left, down, right, stop that fits.
+ * paths (C,N,T,2) int32 padded with the path's last cell, lengths (C,N) = t* + 1, makespan (C,) = max lengths - 1: the layout
+ * of the expert entries above.  solved (C,) uint8; failed_agent (C,) int32: -1, or the agent at which the case stopped - no t*
+ * below T, a start or goal off the map or on an obstacle, or the start / goal of an agent earlier in the order; -2: the order
+ * row is no permutation.  In an unsolved case the agents planned before the failure keep their paths, the others get their
+ * start cell with length 1.  workspace: magat_sim_mapf_workspace_bytes(C, T) = C * T * 5 * 64 * 8 bytes, 8-byte aligned,
+ * zeroed by the call itself.  Limits: H, W <= 64, T <= 256, a workspace of that size - otherwise MAGAT_ERR_UNSUPPORTED and
+ * nothing is launched. */
+size_t magat_sim_mapf_workspace_bytes(int C, int T);
+int magat_sim_mapf_plan(const uint8_t* map, int map_batched, int H, int W, const int32_t* start, const int32_t* goal,
+                        const int32_t* order /* [C][N] or NULL = index order */, int32_t* paths /* [C][N][T][2] */,
+                        int32_t* lengths, int32_t* makespan, uint8_t* solved, int32_t* failed_agent, void* workspace,
+                        size_t workspace_bytes, int C, int N, int T, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -39,10 +39,12 @@ void magat_form_note(int id);      // which form a launch took (MAGAT_FORM_*; pr
 // stay what the bindings of ABI 9 were built against, the library's own tables (profile.hip) hold the *_ALL counts.
 #define MAGAT_TAG_SIM_GUIDED 26     // A*-guided state tensors (sim_guidance.hip)
 #define MAGAT_TAG_SIM_EXPERT 27     // expert schedule -> samples: decode, radius, statistics (sim_expert.hip)
-#define MAGAT_PROF_TAGS_ALL 28
+#define MAGAT_TAG_SIM_MAPF 28       // prioritized space-time planning of C cases (sim_mapf.hip)
+#define MAGAT_PROF_TAGS_ALL 29
 #define MAGAT_FORM_SIM_GUIDED 16    // magat_sim_guided_states launched its one-wave-per-agent search kernel
 #define MAGAT_FORM_SIM_EXPERT 17    // one of the magat_sim_expert_* entries launched (one count per call)
-#define MAGAT_FORMS_ALL 18
+#define MAGAT_FORM_SIM_MAPF 18      // magat_sim_mapf_plan launched its one-wave-per-case planning kernel
+#define MAGAT_FORMS_ALL 19
 static_assert(MAGAT_PROF_TAGS_ALL >= MAGAT_PROF_TAGS && MAGAT_FORMS_ALL >= MAGAT_FORMS, "internal tag / form tables");
 
 // bf16x6 split-MFMA GEMM (conv_gemm_bf16x6.hip), reached through magat_conv_gemm_f32 when desc->in_fmt == 1
@@ -126,6 +128,7 @@ enum MagatLdsSlot {
   MAGAT_LDS_GAT_RERUN_S, MAGAT_LDS_GAT_RERUN_S_END = MAGAT_LDS_GAT_RERUN_S + 5,    // gat_rerun_small_kernel<32 | 64 | 128, without | with the tail>
   MAGAT_LDS_GNND_0,      // gnn_dense.hip: 5 slots (column slice x rows per thread)
   MAGAT_LDS_GNND_END = MAGAT_LDS_GNND_0 + 5,
+  MAGAT_LDS_SIM_MAPF = MAGAT_LDS_GNND_END,      // sim_mapf.hip: the R layers of horizons above 128
   MAGAT_LDS_END
 };
 static_assert(MAGAT_LDS_END <= MAGAT_LDS_SLOTS, "LDS attribute slots");

@@ -1,0 +1,229 @@
+// A multi-agent path-finding expert for C cases at once: prioritized planning with an exact space-time search per agent
+// (restated cell by cell in tests/mapf_restatement.py).  It is NOT ECBS: no bound on the flowtime, and a case
+// can stay unsolved in a given priority order.
+//   magat_sim_mapf_workspace_bytes   the reservation boards: 5 * T * 64 * 8 bytes per case
+//   magat_sim_mapf_plan              one wavefront per case plans its agents one after another in `order`
+// One wavefront per case, lane = map row, one 64-bit word per row (H, W <= 64): a whole board - the free cells, a reachable
+// set R_t, a reservation layer - is one register pair across the wave.  Moving a board left / right is a 64-bit shift,
+// up / down a DPP wave shift.  Everything is integer and bit arithmetic.
+//   reservation boards   global workspace [case][t][V, A_up, A_left, A_down, A_right][row]: a board is one coalesced 512-byte load;
+//                        zeroed here.  They do not depend on the search, so they are loaded MAPF_AHEAD layers ahead.
+//   R layers             LDS, T * 512 bytes; every lane writes and reads only its own row, the backtrace tests each source cell
+//                        on the lane that owns its row.
+//   path of one agent    LDS, (row << 8 | col) per step, written by lane 0 in the backtrace; reserving it and writing it out
+//                        is parallel over t.
+// Every store is a per-lane (vector) store from plain C++.
+#include <cstdint>
+
+#include "magat_common.h"
+
+namespace {
+
+typedef unsigned long long u64;
+constexpr int MAPF_SIDE = 64;       // rows = lanes, columns = bits
+constexpr int MAPF_MAX_T = 256;
+constexpr int MAPF_BOARDS = 5;      // V, then A_d in the key order up, left, down, right
+constexpr int MAPF_AHEAD = 4;       // layers of reservation boards in flight
+
+// DPP wave shifts of both halves of a board word; the lane without a source gets zero
+template <int CTRL>
+__device__ __forceinline__ u64 wave_shift(u64 v) {
+  const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)v, CTRL, 0xf, 0xf, true);
+  const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(v >> 32), CTRL, 0xf, 0xf, true);
+  return ((u64)hi << 32) | lo;
+}
+__device__ __forceinline__ u64 cells_up(u64 v) { return wave_shift<0x130>(v); }        // wave_shl:1 - row r takes row r + 1
+__device__ __forceinline__ u64 cells_down(u64 v) { return wave_shift<0x138>(v); }      // wave_shr:1 - row r takes row r - 1
+__device__ __forceinline__ bool wave_any(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0ull; }
+__device__ __forceinline__ bool has_bit(u64 w, int c) { return (w >> c) & 1ull; }
+
+__device__ __forceinline__ const u64* board_row(const u64* boards, int t, int b, int row) {
+  return boards + ((long long)t * MAPF_BOARDS + b) * MAPF_SIDE + row;
+}
+
+// R_0 = {start}; R_{t+1} = free & ~V[t+1] & (R_t | U_d shift_d(R_t & ~A_opp(d)[t+1])).  Returns t* = the first t > last with the
+// goal in R_t (last: the largest t with the goal in V[t]), or -1: R_t ran empty or t reached T - 1.  Wave-uniform.
+__device__ int mapf_search(const u64* boards, u64* R, u64 free, int sr, int sc, int gr, int gc, int T, int lane) {
+  int last = -1;
+  for (int base = (T - 1) & ~63; base >= 0; base -= 64) {      // lanes over t, highest 64 first
+    const int t = base + lane;
+    const u64 m = __builtin_amdgcn_ballot_w64(t < T && has_bit(*board_row(boards, t < T ? t : 0, 0, gr), gc));
+    if (m) {
+      last = base + 63 - __clzll(m);
+      break;
+    }
+  }
+  if (last >= T - 1) return -1;      // the goal is held for ever
+  u64 cur = lane == sr ? 1ull << sc : 0ull;
+  R[lane] = cur;
+  u64 ahead[MAPF_AHEAD][MAPF_BOARDS];
+#pragma unroll
+  for (int k = 0; k < MAPF_AHEAD; ++k)
+#pragma unroll
+    for (int b = 0; b < MAPF_BOARDS; ++b) ahead[k][b] = 1 + k < T ? *board_row(boards, 1 + k, b, lane) : 0ull;
+  for (int t0 = 0;; t0 += MAPF_AHEAD) {
+#pragma unroll
+    for (int k = 0; k < MAPF_AHEAD; ++k) {
+      const int t = t0 + k;      // cur = R_t, ahead[k] = the boards of layer t + 1
+      if (t > last && wave_any(lane == gr && has_bit(cur, gc))) return t;
+      if (t == T - 1 || !wave_any(cur != 0ull)) return -1;
+      const u64 v = ahead[k][0], a_up = ahead[k][1], a_left = ahead[k][2], a_down = ahead[k][3], a_right = ahead[k][4];
+      const int tn = t + 1 + MAPF_AHEAD;
+#pragma unroll
+      for (int b = 0; b < MAPF_BOARDS; ++b) ahead[k][b] = tn < T ? *board_row(boards, tn, b, lane) : 0ull;
+      // the swap rule: u -> u + d is closed when a planned agent enters u in the direction opposite to d in the same step
+      const u64 moved = cells_up(cur & ~a_down) | ((cur & ~a_right) >> 1) | cells_down(cur & ~a_up) | ((cur & ~a_left) << 1);
+      cur = (cur | moved) & free & ~v;
+      R[(t + 1) * MAPF_SIDE + lane] = cur;
+    }
+  }
+}
+
+// Walks from (goal, t*) down to t = 1: the move INTO (r, c) is the first of up, left, down, right, stop whose source cell is in
+// R_{t-1} and, for a real move, not in A_opp(d)[t].  Each candidate is tested by the lane of its row (a row off the map has
+// no lane or an empty word).  Lane 0 writes the cells.
+__device__ void mapf_backtrace(const u64* boards, const u64* R, int* cells, int gr, int gc, int tstar, int W, int lane) {
+  int r = gr, c = gc;
+  if (lane == 0) cells[tstar] = r << 8 | c;
+  u64 ahead[MAPF_AHEAD][4];
+#pragma unroll
+  for (int k = 0; k < MAPF_AHEAD; ++k)
+#pragma unroll
+    for (int b = 0; b < 4; ++b) ahead[k][b] = tstar - k >= 1 ? *board_row(boards, tstar - k, 1 + b, lane) : 0ull;
+  for (int t0 = tstar; t0 >= 1; t0 -= MAPF_AHEAD) {
+#pragma unroll
+    for (int k = 0; k < MAPF_AHEAD; ++k) {
+      const int t = t0 - k;
+      if (t < 1) break;
+      const u64 a_up = ahead[k][0], a_left = ahead[k][1], a_down = ahead[k][2], a_right = ahead[k][3];
+      const int tn = t - MAPF_AHEAD;
+#pragma unroll
+      for (int b = 0; b < 4; ++b) ahead[k][b] = tn >= 1 ? *board_row(boards, tn, 1 + b, lane) : 0ull;
+      const u64 prev = R[(t - 1) * MAPF_SIDE + lane];
+      const bool up = lane == r + 1 && has_bit(prev & ~a_down, c);                    // moved up: came from the row below
+      const bool left = lane == r && c + 1 < W && has_bit(prev & ~a_right, c + 1 < W ? c + 1 : c);
+      const bool down = lane == r - 1 && has_bit(prev & ~a_up, c);
+      const bool right = lane == r && c >= 1 && has_bit(prev & ~a_left, c >= 1 ? c - 1 : c);
+      if (wave_any(up)) r += 1;
+      else if (wave_any(left)) c += 1;
+      else if (wave_any(down)) r -= 1;
+      else if (wave_any(right)) c -= 1;      // else stop: (r, c) is in R_{t-1}
+      if (lane == 0) cells[t - 1] = r << 8 | c;
+    }
+  }
+}
+
+__global__ __launch_bounds__(64) void mapf_plan_kernel(const uint8_t* __restrict__ map, long long map_stride, int H, int W,
+                                                       const int* __restrict__ start, const int* __restrict__ goal,
+                                                       const int* __restrict__ order, int* paths, int* lengths,
+                                                       int* __restrict__ makespan, uint8_t* __restrict__ solved,
+                                                       int* __restrict__ failed_agent, u64* workspace, int N, int T) {
+  extern __shared__ __align__(16) unsigned char smem_raw[];
+  u64* R = reinterpret_cast<u64*>(smem_raw);      // [T][64]
+  __shared__ int cells[MAPF_MAX_T];               // the path being reserved
+  const int cs = blockIdx.x, lane = threadIdx.x;
+  u64* boards = workspace + (long long)cs * T * MAPF_BOARDS * MAPF_SIDE;
+  for (int i = lane; i < T * MAPF_BOARDS * MAPF_SIDE; i += 64) boards[i] = 0ull;
+  // free cells: row r of the map read by the lanes over its columns, one ballot per row; lanes >= H and bits >= W stay zero
+  const uint8_t* mp = map + cs * map_stride;
+  u64 free = 0ull;
+  for (int r = 0; r < H; ++r) {
+    const u64 word = __builtin_amdgcn_ballot_w64(lane < W && mp[r * W + (lane < W ? lane : 0)] == 0);
+    if (lane == r) free = word;
+  }
+  const long long a0 = (long long)cs * N;
+  const int* ord = order ? order + a0 : nullptr;
+  int* len = lengths + a0;
+  // is `order` a permutation?  N entries in range, none named twice (counted in `lengths`, which is written again below)
+  bool bad_order = false;
+  if (ord) {
+    for (int n = lane; n < N; n += 64) len[n] = 0;
+    __syncthreads();
+    for (int k = lane; k < N; k += 64) {
+      const int a = ord[k];
+      if (a < 0 || a >= N || atomicAdd(&len[a], 1) != 0) bad_order = true;
+    }
+    bad_order = wave_any(bad_order);
+  }
+  __syncthreads();      // the zeroed boards, and the counts before `lengths` is written
+  u64 starts = 0ull, goals = 0ull;      // the planned agents' start and goal cells
+  int failed = bad_order ? -2 : -1, longest = 1, k = 0;
+  for (; failed == -1 && k < N; ++k) {
+    const int a = __builtin_amdgcn_readfirstlane(ord ? ord[k] : k);
+    const int sr = start[(a0 + a) * 2], sc = start[(a0 + a) * 2 + 1], gr = goal[(a0 + a) * 2], gc = goal[(a0 + a) * 2 + 1];
+    const bool inside = sr >= 0 && sr < H && sc >= 0 && sc < W && gr >= 0 && gr < H && gc >= 0 && gc < W;
+    const u64 sbit = inside ? 1ull << sc : 0ull, gbit = inside ? 1ull << gc : 0ull;
+    const bool ok = wave_any(lane == sr && (free & ~starts & sbit)) && wave_any(lane == gr && (free & ~goals & gbit));
+    const int tstar = ok ? mapf_search(boards, R, free, sr, sc, gr, gc, T, lane) : -1;
+    if (tstar < 0) {
+      failed = a;
+      break;
+    }
+    mapf_backtrace(boards, R, cells, gr, gc, tstar, W, lane);
+    __syncthreads();
+    // reserve and write out, lanes over t: layer t belongs to one lane, so no two lanes touch one word
+    int* p = paths + (a0 + a) * T * 2;
+    for (int t = lane; t < T; t += 64) {
+      const int cell = cells[t < tstar ? t : tstar], cr = cell >> 8, cc = cell & 255;
+      boards[((long long)t * MAPF_BOARDS) * MAPF_SIDE + cr] |= 1ull << cc;
+      if (t >= 1 && t <= tstar) {
+        const int from = cells[t - 1], dr = cr - (from >> 8), dc = cc - (from & 255);
+        const int d = dr == -1 ? 0 : dc == -1 ? 1 : dr == 1 ? 2 : dc == 1 ? 3 : 4;
+        if (d < 4) boards[((long long)t * MAPF_BOARDS + 1 + d) * MAPF_SIDE + cr] |= 1ull << cc;
+      }
+      p[2 * t] = cr;
+      p[2 * t + 1] = cc;
+    }
+    if (lane == 0) len[a] = tstar + 1;
+    if (lane == sr) starts |= sbit;
+    if (lane == gr) goals |= gbit;
+    longest = tstar + 1 > longest ? tstar + 1 : longest;
+    __syncthreads();      // the next agent loads these boards and reuses `cells`
+  }
+  // the failing agent and the agents behind it (every agent when `order` is no permutation): the start cell, length 1
+  if (failed != -1) {
+    for (; k < N; ++k) {
+      const int a = failed == -2 ? k : __builtin_amdgcn_readfirstlane(ord ? ord[k] : k);
+      const int sr = start[(a0 + a) * 2], sc = start[(a0 + a) * 2 + 1];
+      int* p = paths + (a0 + a) * T * 2;
+      for (int t = lane; t < T; t += 64) {
+        p[2 * t] = sr;
+        p[2 * t + 1] = sc;
+      }
+      if (lane == 0) len[a] = 1;
+    }
+  }
+  if (lane == 0) {
+    makespan[cs] = longest - 1;
+    solved[cs] = failed == -1 ? 1 : 0;
+    failed_agent[cs] = failed;
+  }
+}
+
+}  // namespace
+
+extern "C" size_t magat_sim_mapf_workspace_bytes(int C, int T) {
+  if (C <= 0 || T <= 0) return 0;
+  return (size_t)C * T * MAPF_BOARDS * MAPF_SIDE * sizeof(u64);
+}
+
+extern "C" int magat_sim_mapf_plan(const uint8_t* map, int map_batched, int H, int W, const int32_t* start, const int32_t* goal,
+                                   const int32_t* order, int32_t* paths, int32_t* lengths, int32_t* makespan, uint8_t* solved,
+                                   int32_t* failed_agent, void* workspace, size_t workspace_bytes, int C, int N, int T,
+                                   void* stream) {
+  if (!map || !start || !goal || !paths || !lengths || !makespan || !solved || !failed_agent || !workspace) return MAGAT_ERR_NULL;
+  if (H <= 0 || W <= 0 || C <= 0 || N <= 0 || T <= 0) return MAGAT_ERR_BAD_SHAPE;
+  if (H > MAPF_SIDE || W > MAPF_SIDE || T > MAPF_MAX_T) return MAGAT_ERR_UNSUPPORTED;
+  if (workspace_bytes < magat_sim_mapf_workspace_bytes(C, T)) return MAGAT_ERR_UNSUPPORTED;
+  if (reinterpret_cast<uintptr_t>(workspace) % sizeof(u64)) return MAGAT_ERR_WORKSPACE;
+  const size_t lds = (size_t)T * MAPF_SIDE * sizeof(u64);      // <= 128 KB, + 1 KB static
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (lds > 64 * 1024 && magat_ensure_dyn_lds(reinterpret_cast<const void*>(&mapf_plan_kernel), MAGAT_LDS_SIM_MAPF, lds) != MAGAT_OK)
+    return MAGAT_ERR_LAUNCH;
+  magat_form_note(MAGAT_FORM_SIM_MAPF);
+  const int pid = magat_prof_begin(MAGAT_TAG_SIM_MAPF, st);
+  hipLaunchKernelGGL(mapf_plan_kernel, dim3((unsigned)C), dim3(64), lds, st, map, map_batched ? (long long)H * W : 0LL, H, W, start,
+                     goal, order, paths, lengths, makespan, solved, failed_agent, static_cast<u64*>(workspace), N, T);
+  magat_prof_end(pid, st);
+  return magat_check_launch();
+}

@@ -1,0 +1,129 @@
+"""A multi-agent path-finding expert on the device: the solver at the head of the expert pipeline (expert.py turns ITS
+schedules into training samples), for C cases at once.  The reference calls pre-built ecbs / cbs / sipp binaries, one
+subprocess per case (onlineExpert/ECBS_onlineExpert.py:81-104); this is prioritized planning with an exact space-time search
+per agent (csrc/sim_mapf.hip).  It is NOT ECBS: it gives no bound on the flowtime, and it is incomplete - a case
+can fail in one priority order and succeed in another, or stay unsolved.
+
+    res = solve_cases(obstacle_map, start, goal)                          # plans, re-plans the unsolved cases in a new order
+    pack = solved_pack(res)                                               # the solved cases, as pack_schedules lays them out
+    s = expert_samples(obstacle_map, comm_radius=config.commR, **pack)    # (a (C,H,W) map: index it with pack_cases(res))
+
+The online expert - re-solving the cases a running episode is failing at, from where the agents stand now:
+
+    ep = BatchedEpisode(obstacle_map, pos, goal, maxstep, comm_radius=config.commR)
+    ... ep.step(logits) ...
+    res = solve_cases(ep.map, ep.pos, ep.goal)                            # schedules that start at the current positions
+
+HIP only: CPU tensors raise MagatNativeError.  plan_prioritized is stream ordered and never waits for the device;
+solve_cases reads `solved` back once per round."""
+import torch
+
+from . import _native as nat
+from .simulator import _dev_i32
+
+MAX_HORIZON = 256
+PACK_KEYS = ("paths", "lengths", "goal", "start", "makespan")
+
+
+def default_horizon(H, W, N):
+    return min(MAX_HORIZON, 2 * (H + W) + N)
+
+
+def plan_prioritized(obstacle_map, start, goal, order=None, horizon=None):
+    """One call of magat_sim_mapf_plan: obstacle_map (H,W) or (C,H,W) (non-zero: obstacle; H, W <= 64), start / goal (C,N,2)
+    (row, col), order (C,N): each case's priority order, a permutation of its agents (None: index order).  Agents are planned
+    one after another; each takes the earliest arrival that the agents before it leave open, waits included, and holds its
+    goal from then on.  Returns a dict of device tensors: paths (C,N,horizon,2) int32 padded with each path's last cell,
+    lengths (C,N), goal, start (C,N,2), makespan (C,) = max lengths - 1 (pack_schedules' layout), solved (C,) uint8 and
+    failed_agent (C,) int32 - -1, or the agent at which the case stopped: no arrival inside the horizon, a start or goal off
+    the map, on an obstacle or shared with an agent earlier in the order; -2: the order row is no permutation.  In an unsolved
+    case the agents before the failure keep their paths, the others get their start cell with length 1.
+
+    horizon: the most cells a path may have, at most 256; the default min(256, 2 * (H + W) + N) is a default, not a
+    guarantee - it has not been measured against any family of maps, and a case whose agents need longer comes back unsolved.
+    Stream ordered, no host synchronisation."""
+    start, goal = _dev_i32(start, "start"), _dev_i32(goal, "goal")
+    if not isinstance(obstacle_map, torch.Tensor) or not obstacle_map.is_cuda:
+        raise nat.MagatNativeError("obstacle_map must be a device tensor (no CPU fallback)")
+    m = obstacle_map.to(torch.uint8).contiguous()
+    assert start.dim() == 3 and start.shape[2] == 2 and goal.shape == start.shape, "start and goal must be (C,N,2)"
+    C, N, _ = start.shape
+    assert m.dim() in (2, 3) and (m.dim() == 2 or m.shape[0] == C), "obstacle_map must be (H,W) or (C,H,W)"
+    H, W = m.shape[-2], m.shape[-1]
+    if order is not None:
+        order = _dev_i32(order, "order")
+        assert tuple(order.shape) == (C, N), "order must be (C,N)"
+    T = default_horizon(H, W, N) if horizon is None else int(horizon)
+    dev = start.device
+    lib = nat.lib()
+    paths = torch.empty(C, N, T, 2, dtype=torch.int32, device=dev)
+    lengths = torch.empty(C, N, dtype=torch.int32, device=dev)
+    makespan = torch.empty(C, dtype=torch.int32, device=dev)
+    solved = torch.empty(C, dtype=torch.uint8, device=dev)
+    failed = torch.empty(C, dtype=torch.int32, device=dev)
+    ws = torch.empty(max(int(lib.magat_sim_mapf_workspace_bytes(C, T)), 8), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        nat.check(lib.magat_sim_mapf_plan(nat.ptr(m), 1 if m.dim() == 3 else 0, H, W, nat.ptr(start), nat.ptr(goal),
+                                          nat.ptr(order), nat.ptr(paths), nat.ptr(lengths), nat.ptr(makespan), nat.ptr(solved),
+                                          nat.ptr(failed), nat.ptr(ws), ws.numel(), C, N, T, nat.current_stream(dev)),
+                  "magat_sim_mapf_plan")
+    return dict(paths=paths, lengths=lengths, goal=goal, start=start, makespan=makespan, solved=solved, failed_agent=failed)
+
+
+def promote(order, agent):
+    """order (K,N), agent (K,): each row with its agent moved to the front, the others keeping their relative order (tensor
+    ops on the device)."""
+    hit = order == agent[:, None].to(order.dtype)
+    rest = torch.argsort(hit.to(torch.int8), dim=1, descending=True, stable=True)      # the hit first, then the old order
+    return torch.gather(order, 1, rest)
+
+
+def solve_cases(obstacle_map, start, goal, horizon=None, retries=8):
+    """plan_prioritized in index order, then up to `retries` re-plans of the cases still unsolved, each with that case's
+    failed_agent moved to the front of its order.  Returns plan_prioritized's dict (every case holds its LAST plan) plus order
+    (C,N) int32 (the order of that plan), rounds (C,) int32 (the plans made for the case, 1 = solved at once) and T =
+    int(makespan.max()) + 1 over the solved cases (1 when there is none).
+
+    Cases still unsolved STAY in the batch with solved == 0, and their paths are not schedules: expert_samples, expert_stats
+    and BatchedEpisode replays must only be fed solved cases.  solved_pack(res) drops the others -
+    idx = res["solved"].nonzero().flatten(); tensor.index_select(0, idx) for every tensor of the dict - and returns exactly
+    the keys that expert_samples takes as **pack.
+
+    One host synchronisation per round (the read of `solved`), one more for T."""
+    res = plan_prioritized(obstacle_map, start, goal, None, horizon)
+    C, N, _ = res["start"].shape
+    dev = res["start"].device
+    order = torch.arange(N, dtype=torch.int32, device=dev).repeat(C, 1)
+    rounds = torch.ones(C, dtype=torch.int32, device=dev)
+    T = res["paths"].shape[2]
+    batched = obstacle_map.dim() == 3
+    for _ in range(int(retries)):
+        idx = torch.nonzero(res["solved"] == 0).flatten()      # (the host learns how many are left: the synchronisation)
+        if idx.numel() == 0:
+            break
+        again = promote(order.index_select(0, idx), res["failed_agent"].index_select(0, idx))
+        sub = plan_prioritized(obstacle_map.index_select(0, idx) if batched else obstacle_map,
+                               res["start"].index_select(0, idx), res["goal"].index_select(0, idx), again, T)
+        for key in ("paths", "lengths", "makespan", "solved", "failed_agent"):
+            res[key].index_copy_(0, idx, sub[key])
+        order.index_copy_(0, idx, again)
+        rounds.index_add_(0, idx, torch.ones_like(idx, dtype=torch.int32))
+    done = res["makespan"][res["solved"] != 0]
+    res.update(order=order, rounds=rounds, T=int(done.max().item()) + 1 if done.numel() else 1)
+    return res
+
+
+def pack_cases(res):
+    """Indices (K,) int64 of the solved cases of a plan_prioritized / solve_cases result."""
+    return torch.nonzero(res["solved"] != 0).flatten()
+
+
+def solved_pack(res):
+    """The solved cases of a result in pack_schedules' form - paths, lengths, goal, start, makespan and T = max(makespan) + 1
+    - for expert_schedule / expert_samples (**pack).  Raises ValueError when no case is solved.  (Synchronises.)"""
+    idx = pack_cases(res)
+    if idx.numel() == 0:
+        raise ValueError("solved_pack: no case of the batch is solved")
+    pack = {key: res[key].index_select(0, idx) for key in PACK_KEYS}
+    pack["T"] = int(pack["makespan"].max().item()) + 1
+    return pack

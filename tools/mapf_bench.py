@@ -1,0 +1,74 @@
+"""Times the path-finding expert (magat_pathplanning_amd/mapf.py, csrc/sim_mapf.hip) at two batch shapes:
+
+    512 cases of 20 x 20 / 10 agents / T = 64          128 cases of 50 x 50 / 100 agents / T = 128
+
+Device events around plan_prioritized (10 warm-ups, median of 50 calls), the share of cases solved at the first try and after
+solve_cases' retries, and - with --restatement K - the CPU seconds that tests/mapf_restatement.py (a per-cell Python
+restatement, NOT ECBS; the only comparison there is) needs for the first K cases of each shape.  One JSON line per shape.
+
+    python tools/mapf_bench.py [--restatement K] [--no-device]"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+import mapf_restatement as mr  # noqa: E402
+
+SHAPES = (dict(name="20x20_n10", C=512, size=20, N=10, T=64, density=0.1, seed=101),
+          dict(name="50x50_n100", C=128, size=50, N=100, T=128, density=0.1, seed=102))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--restatement", type=int, default=0, help="time the Python restatement on this many cases per shape")
+    ap.add_argument("--no-device", action="store_true")
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--calls", type=int, default=50)
+    args = ap.parse_args()
+    for sh in SHAPES:
+        m, start, goal = mr.random_batch(sh["seed"], sh["C"], sh["size"], sh["size"], sh["N"], sh["density"])
+        out = dict(shape=sh["name"], cases=sh["C"], agents=sh["N"], T=sh["T"])
+        if not args.no_device:
+            import torch
+            from magat_pathplanning_amd import plan_prioritized, solve_cases
+            assert torch.cuda.is_available(), "mapf_bench needs a GPU (no fallback)"
+            d = [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in (m, start, goal)]
+            for _ in range(args.warmup):
+                res = plan_prioritized(*d, horizon=sh["T"])
+            torch.cuda.synchronize()
+            ms = []
+            for _ in range(args.calls):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                res = plan_prioritized(*d, horizon=sh["T"])
+                e1.record()
+                e1.synchronize()
+                ms.append(e0.elapsed_time(e1))
+            ms.sort()
+            t0 = time.perf_counter()
+            full = solve_cases(*d, horizon=sh["T"], retries=8)
+            torch.cuda.synchronize()
+            solve_ms = (time.perf_counter() - t0) * 1e3
+            solved = full["solved"] != 0
+            out.update(plan_ms_median=ms[len(ms) // 2], plan_ms_min=ms[0], plan_ms_max=ms[-1],
+                       plan_us_per_case=ms[len(ms) // 2] * 1e3 / sh["C"], solved_first_try=float(res["solved"].float().mean()),
+                       solved_after_retries=float(solved.float().mean()), rounds_max=int(full["rounds"].max()),
+                       solve_cases_ms_host_clock=solve_ms, makespan_max_solved=int(full["makespan"][solved].max()))
+        if args.restatement:
+            k = min(args.restatement, sh["C"])
+            t0 = time.perf_counter()
+            ref = mr.plan_batch(m, start[:k], goal[:k], None, sh["T"])
+            sec = time.perf_counter() - t0
+            out.update(restatement_cases=k, restatement_cpu_s=sec, restatement_cpu_s_per_case=sec / k,
+                       restatement_solved_first_try=float(ref["solved"].mean()))
+        print(json.dumps(out), flush=True)
+
+
+if __name__ == "__main__":
+    main()
