@@ -778,6 +778,33 @@ int magat_sim_mapf_plan(const uint8_t* map, int map_batched, int H, int W, const
                         int32_t* lengths, int32_t* makespan, uint8_t* solved, int32_t* failed_agent, void* workspace,
                         size_t workspace_bytes, int C, int N, int T, void* stream);
 
+/* ------------------------------------------------------------------------------------------
+ * Planning cases made on the device (sim_cases.hip; added behind ABI 9, nothing above changes): the first step of the expert
+ * pipeline, the reference's offlineExpert/CasesGenerator.py - an obstacle map, its largest free component, a start and a goal
+ * per agent - for C cases in one launch; its outputs are what magat_sim_mapf_plan takes.  Device pointers, stream ordered, no
+ * allocation, no workspace, no synchronisation; one kernel.  It adds no profiling tag and no form of its own: as the head of
+ * the same pipeline it counts once in form "sim_mapf" and is one span of that profiling tag.
+ *
+ * kind: MAGAT_CASES_MAZE - the reference's mapGen: `aisles` walks of `walk` steps over the even lattice (the caller computes
+ * aisles = int(density * (H / 2) * (W / 2)), walk = int(complexity * 5 * (H + W))); MAGAT_CASES_UNIFORM - cell (r, c) is an
+ * obstacle iff its 32-bit draw < threshold = floor(density * 2^32); MAGAT_CASES_GIVEN - map_in (H,W), or (C,H,W) when
+ * map_batched, uint8, non-zero: obstacle (map_in may be NULL for the other kinds).  The kept free region is the largest
+ * 4-connected free component (ties: the one holding the lowest row-major cell); every other free cell is an obstacle in
+ * map_out (C,H,W) uint8 (0 / 1), free_cells (C,) = F, its size.  start / goal (C,N,2) int32 (row, col): starts are N distinct
+ * cells of the region, uniform over ordered tuples, goals likewise, redrawn as a whole (at most 64 times) until goal[a] !=
+ * start[a] for every agent.  valid (C,) uint8 = 1 iff F >= N + 1 and a goal tuple was accepted; otherwise start and goal are -1.
+ * Random numbers: draw(seed, first_case + c, stream, index), a counter-based hash - a case depends on its
+ * GLOBAL index first_case + c, not on C or its place in the batch.
+ * Limits: H, W <= 64; maze: H, W >= 4, aisles <= 4096, walk <= 1024; N <= H * W; 0 <= first_case, first_case + C <= 2^32 -
+ * otherwise MAGAT_ERR_UNSUPPORTED and nothing is launched (null pointers -5, non-positive sizes or an unknown kind -1). */
+#define MAGAT_CASES_MAZE 0
+#define MAGAT_CASES_UNIFORM 1
+#define MAGAT_CASES_GIVEN 2
+int magat_sim_cases_generate(int kind, const uint8_t* map_in /* NULL unless GIVEN */, int map_batched, int H, int W, int aisles,
+                             int walk, uint64_t threshold, uint64_t seed, int64_t first_case, uint8_t* map_out /* [C][H][W] */,
+                             int32_t* start, int32_t* goal /* [C][N][2] */, int32_t* free_cells, uint8_t* valid, int C, int N,
+                             void* stream);
+
 #ifdef __cplusplus
 }
 #endif

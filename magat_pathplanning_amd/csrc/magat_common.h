@@ -39,11 +39,11 @@ void magat_form_note(int id);      // which form a launch took (MAGAT_FORM_*; pr
 // stay what the bindings of ABI 9 were built against, the library's own tables (profile.hip) hold the *_ALL counts.
 #define MAGAT_TAG_SIM_GUIDED 26     // A*-guided state tensors (sim_guidance.hip)
 #define MAGAT_TAG_SIM_EXPERT 27     // expert schedule -> samples: decode, radius, statistics (sim_expert.hip)
-#define MAGAT_TAG_SIM_MAPF 28       // prioritized space-time planning of C cases (sim_mapf.hip)
+#define MAGAT_TAG_SIM_MAPF 28       // prioritized space-time planning of C cases (sim_mapf.hip), and making the cases (sim_cases.hip)
 #define MAGAT_PROF_TAGS_ALL 29
 #define MAGAT_FORM_SIM_GUIDED 16    // magat_sim_guided_states launched its one-wave-per-agent search kernel
 #define MAGAT_FORM_SIM_EXPERT 17    // one of the magat_sim_expert_* entries launched (one count per call)
-#define MAGAT_FORM_SIM_MAPF 18      // magat_sim_mapf_plan launched its one-wave-per-case planning kernel
+#define MAGAT_FORM_SIM_MAPF 18      // magat_sim_mapf_plan launched its one-wave-per-case planning kernel, or magat_sim_cases_generate its generator
 #define MAGAT_FORMS_ALL 19
 static_assert(MAGAT_PROF_TAGS_ALL >= MAGAT_PROF_TAGS && MAGAT_FORMS_ALL >= MAGAT_FORMS, "internal tag / form tables");
 

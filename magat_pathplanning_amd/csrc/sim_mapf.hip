@@ -16,26 +16,14 @@
 #include <cstdint>
 
 #include "magat_common.h"
+#include "row_board.h"      // u64, wave_shift, cells_up / cells_down, wave_any, has_bit
 
 namespace {
 
-typedef unsigned long long u64;
 constexpr int MAPF_SIDE = 64;       // rows = lanes, columns = bits
 constexpr int MAPF_MAX_T = 256;
 constexpr int MAPF_BOARDS = 5;      // V, then A_d in the key order up, left, down, right
 constexpr int MAPF_AHEAD = 4;       // layers of reservation boards in flight
-
-// DPP wave shifts of both halves of a board word; the lane without a source gets zero
-template <int CTRL>
-__device__ __forceinline__ u64 wave_shift(u64 v) {
-  const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)v, CTRL, 0xf, 0xf, true);
-  const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(v >> 32), CTRL, 0xf, 0xf, true);
-  return ((u64)hi << 32) | lo;
-}
-__device__ __forceinline__ u64 cells_up(u64 v) { return wave_shift<0x130>(v); }        // wave_shl:1 - row r takes row r + 1
-__device__ __forceinline__ u64 cells_down(u64 v) { return wave_shift<0x138>(v); }      // wave_shr:1 - row r takes row r - 1
-__device__ __forceinline__ bool wave_any(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0ull; }
-__device__ __forceinline__ bool has_bit(u64 w, int c) { return (w >> c) & 1ull; }
 
 __device__ __forceinline__ const u64* board_row(const u64* boards, int t, int b, int row) {
   return boards + ((long long)t * MAPF_BOARDS + b) * MAPF_SIDE + row;
