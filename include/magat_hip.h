@@ -205,7 +205,11 @@ int magat_cast_rows(const void* src, void* dst, int to_bf16, long long M, int wi
  * (the caller's autograd owns those), att [P][nnz] (CSR order), Z [M][NC], T [(K-2)][M][P*F] (intermediate hop
  * states, NULL if K <= 2) and the CSC view (cscptr [B*(N+1)], cscsrc/cscpos/csctmp [nnz]).
  * Backward of the graph part: dZ [M][NC] (gradient wrt every column of Z) and dXd [M][G] (direct score term of dX);
- * the caller finishes with two plain GEMMs  dX = dXd + dZ @ Bt,  dBt = dZ^T @ X.  datt [P][nnz] is scratch. */
+ * the caller finishes with two plain GEMMs  dX = dXd + dZ @ Bt,  dBt = dZ^T @ X.  datt [P][nnz] is scratch.
+ * Both answer before anything is launched, in this order: a NULL among the pointers the shape uses (colidx may be NULL when
+ * nnz == 0, T when K <= 2, bias always) MAGAT_ERR_NULL; B, N, K, P <= 0 or nnz < 0 MAGAT_ERR_BAD_SHAPE; a mode that is not one
+ * of the three attention modes, G != F, a width outside {16,32,64,128,256} and (forward: it transposes the GSO) N > 8190
+ * MAGAT_ERR_UNSUPPORTED; more than 2^31 - 1 rows (forward) or workgroups in the largest launch MAGAT_ERR_BAD_SHAPE. */
 int magat_gat_train_forward_f32(const float* X, const int* rowptr, const int* colidx, long long nnz, const float* packed,
                                 const float* bias, float* Ypre, float* att, float* Z, float* T, int* cscptr,
                                 int* cscsrc, int* cscpos, int* csctmp, int B, int N, int G, int F, int K, int P,
@@ -219,7 +223,8 @@ int magat_gat_train_backward_f32(const float* dYpre, const float* X, const float
  * x and in the taps:  Y = b + sum_k A^k X H_k^T  (A = row operator of "x @ S"), so  dU_k = (A^T)^k dY  is the forward hop
  * run over the CSR rows of S.  dY [M][F] -> dZ [M][K*F], slice k = dU_k.  The caller finishes with two plain GEMMs:
  * dX = dZ @ Bt (Bt [K*F][G], row k*F+f = weight[f,0,k,:]),  dweight[f,0,k,:] = (dZ^T X)[k*F+f],  dbias = column sums of dY.
- * rowptr / colidx / vals: the CSR arrays magat_gnn_forward_csr_f32 takes. */
+ * rowptr / colidx / vals: the CSR arrays magat_gnn_forward_csr_f32 takes.  Answers before anything is launched: NULL pointers
+ * (colidx / vals may be NULL when nnz == 0 or K == 1), then sizes <= 0, then the width, then a hop grid past 2^31 - 1. */
 int magat_gnn_backward_csr_f32(const float* dY, const int* rowptr, const int* colidx, const float* vals, long long nnz,
                                float* dZ, int B, int N, int F, int K, void* stream);
 

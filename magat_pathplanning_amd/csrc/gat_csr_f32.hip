@@ -326,6 +326,11 @@ __global__ void csr_k1_kernel(const CsrParams p) {
 }
 
 
+// Largest N of the entries that transpose the GSO themselves (magat_hip.h: "any N <= 8190"): csr_transpose_kernel keeps
+// 2 N + 2 ints in LDS, under 64 KiB.  (The check once read `bytes > 64 KiB` and let N = 8191 - exactly 64 KiB - through.)
+constexpr int CSR_MAX_N = 8190;
+static_assert((2 * CSR_MAX_N + 2) * sizeof(int) < 64 * 1024 && (2 * (CSR_MAX_N + 1) + 2) * sizeof(int) >= 64 * 1024, "");
+
 struct WsLayout {
   size_t status, z, cscptr, cscsrc, cscpos, csctmp, att, t0, t1, ytmp, order, total;
 };
@@ -893,7 +898,7 @@ int csr_forward(const ST* X, const int* rowptr, const int* colidx, long long nnz
   const bool gnn = mode == MAGAT_MODE_GNN;     // fixed edge weights (the GSO values) instead of attention
   if (gnn && (P != 1 || (nnz > 0 && K > 1 && !edge_vals) || (G & 3))) return MAGAT_ERR_BAD_SHAPE;
   if ((!gnn && G != F) || !supported_width(F)) return MAGAT_ERR_UNSUPPORTED;
-  if ((size_t)(2 * N + 2) * sizeof(int) > 64 * 1024) return MAGAT_ERR_UNSUPPORTED;   // transpose LDS (N <= 8190)
+  if (N > CSR_MAX_N) return MAGAT_ERR_UNSUPPORTED;
   const int width = concat ? P * F : F;
   if (ldy < width || (ldy & 3)) return MAGAT_ERR_BAD_SHAPE;
   // X rows are read in 16-byte pieces (the maps GEMMs, the range guard's float32 re-run, the fused bf16 kernels): an X that is
@@ -1140,10 +1145,14 @@ extern "C" int magat_gat_train_forward_f32(const float* X, const int* rowptr, co
   if (B <= 0 || N <= 0 || nnz < 0 || K <= 0 || P <= 0) return MAGAT_ERR_BAD_SHAPE;
   if (mode < MAGAT_MODE_KEYQUERY || mode > MAGAT_MODE_GAT_ORIGIN) return MAGAT_ERR_UNSUPPORTED;
   if (G != F || !supported_width(G)) return MAGAT_ERR_UNSUPPORTED;
-  if ((size_t)(2 * N + 2) * sizeof(int) > 64 * 1024) return MAGAT_ERR_UNSUPPORTED;
+  if (N > CSR_MAX_N) return MAGAT_ERR_UNSUPPORTED;
+  const long long M = (long long)B * N;
+  // sizes the launches below cannot express (the maps GEMM takes its row count as an int; the hop grid is the largest), refused
+  // here and not behind the maps GEMM
+  if (M > 0x7fffffffLL || (long long)((B + MAGAT_NUM_XCD - 1) / MAGAT_NUM_XCD) * MAGAT_NUM_XCD * P * ((N + 3) / 4) > 0x7fffffffLL)
+    return MAGAT_ERR_BAD_SHAPE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const PackLayout L = pack_layout(G, F, K, P, mode);
-  const long long M = (long long)B * N;
   // float32 MFMA maps: Z is kept for the backward, and with caller-owned buffers there is no status word for a guarded
   // split GEMM (the maps are 5 % of a training step either way)
   int rc = magat_gat_maps_gemm(X, packed, Z, (int)M, G, L.NC, L.NC, stream, 0, nullptr, 1);

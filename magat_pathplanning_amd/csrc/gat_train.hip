@@ -237,10 +237,14 @@ __global__ void gnn_bwd_seed_kernel(const float* __restrict__ dY, float* __restr
   }
 }
 
+// workgroups of a wave-per-row launch: whole XCD rounds of instances, `per_instance_factor` x 4-row tiles each
+long long rows_grid(int B, int N, int per_instance_factor) {
+  return (long long)((B + MAGAT_NUM_XCD - 1) / MAGAT_NUM_XCD) * MAGAT_NUM_XCD * per_instance_factor * ((N + 3) / 4);
+}
+
 template <int W, typename KFn>
 int launch_rows(KFn kern, const TrainParams& p, int per_instance_factor, hipStream_t st) {
-  const int tiles = (p.N + 3) / 4;
-  const long long grid = (long long)((p.B + MAGAT_NUM_XCD - 1) / MAGAT_NUM_XCD) * MAGAT_NUM_XCD * per_instance_factor * tiles;
+  const long long grid = rows_grid(p.B, p.N, per_instance_factor);
   if (grid > 0x7fffffffLL) return MAGAT_ERR_BAD_SHAPE;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), 0, st, p);
   return magat_check_launch();
@@ -254,8 +258,13 @@ extern "C" int magat_gat_train_backward_f32(const float* dYpre, const float* X, 
                                             float* datt, int B, int N, int G, int F, int K, int P, int mode,
                                             void* stream) {
   if (!dYpre || !X || !Z || !att || !rowptr || !cscptr || !cscsrc || !cscpos || !dZ || !dXd || !datt) return MAGAT_ERR_NULL;
+  if (nnz > 0 && !colidx) return MAGAT_ERR_NULL;
+  if (K > 2 && !T) return MAGAT_ERR_NULL;
   if (B <= 0 || N <= 0 || nnz < 0 || K <= 0 || P <= 0) return MAGAT_ERR_BAD_SHAPE;
+  if (mode < MAGAT_MODE_KEYQUERY || mode > MAGAT_MODE_GAT_ORIGIN) return MAGAT_ERR_UNSUPPORTED;
   if (G != F || !supported_width(G)) return MAGAT_ERR_UNSUPPORTED;
+  // the largest grid of the call (the hops: P heads per instance), refused here and not behind the memsets and the seed launch
+  if (K > 1 && rows_grid(B, N, P) > 0x7fffffffLL) return MAGAT_ERR_BAD_SHAPE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const PackLayout L = pack_layout(G, F, K, P, mode);
   TrainParams p = {};
@@ -291,15 +300,14 @@ extern "C" int magat_gnn_backward_csr_f32(const float* dY, const int* rowptr, co
   if (nnz > 0 && K > 1 && (!colidx || !vals)) return MAGAT_ERR_NULL;
   if (B <= 0 || N <= 0 || nnz < 0 || K <= 0) return MAGAT_ERR_BAD_SHAPE;
   if (!supported_width(F)) return MAGAT_ERR_UNSUPPORTED;
+  const long long grid = rows_grid(B, N, 1);
+  if (K > 1 && grid > 0x7fffffffLL) return MAGAT_ERR_BAD_SHAPE;      // (before the seed launch)
   hipStream_t st = static_cast<hipStream_t>(stream);
   const long long M = (long long)B * N;
   long long blocks = (M * (F / 4) + 255) / 256;
   if (blocks > 4096) blocks = 4096;
   hipLaunchKernelGGL(gnn_bwd_seed_kernel, dim3((unsigned)blocks), dim3(256), 0, st, dY, dZ, M, F, K);
   int rc = magat_check_launch();
-  const int tiles = (N + 3) / 4;
-  const long long grid = (long long)((B + MAGAT_NUM_XCD - 1) / MAGAT_NUM_XCD) * MAGAT_NUM_XCD * tiles;
-  if (grid > 0x7fffffffLL) return MAGAT_ERR_BAD_SHAPE;
   for (int k = 1; k < K && rc == MAGAT_OK; ++k) {
     MAGAT_WIDTH_SWITCH(F, hipLaunchKernelGGL(gnn_bwd_hop_kernel<WW>, dim3((unsigned)grid), dim3(256), 0, st, rowptr, colidx,
                                              vals, dZ, B, N, K, k));
