@@ -784,6 +784,30 @@ int magat_sim_mapf_plan(const uint8_t* map, int map_batched, int H, int W, const
                         size_t workspace_bytes, int C, int N, int T, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * The wide forms of the solver above and of the case generator below (sim_mapf_wide.hip, sim_cases_wide.hip; added behind ABI 9, nothing above changes,
+ * the 64 x 64 forms and their refusals included): maps up to 256 x 256, horizons up to 1024.  The same algorithms cell for
+ * cell, the same output layouts, the same random streams - where both forms take a shape, they write the same bytes.  One
+ * workgroup of rows(H) = 64 * ceil(H / 64) threads per case, thread = map row, words(W) = 1 (W <= 64), 2 (W <= 128) or 4 words
+ * per row.  Same arguments in the same order, same order of the checks and same codes; counted in form "sim_mapf" and its
+ * profiling tag like the 64 x 64 forms; stream ordered, no allocation, no synchronisation, one kernel per call.
+ *
+ * magat_sim_mapf_plan_wide: H, W <= 256, 1 <= T <= 1024.  workspace: magat_sim_mapf_wide_workspace_bytes(C, H, W, T) =
+ * C * T * 6 * rows(H) * words(W) * 8 bytes, 8-byte aligned - per case and layer t the five reservation boards and, behind
+ * them, the reachable set of the agent being planned, [case][t][V, A_up, A_left, A_down, A_right, R][row][word]; the call
+ * zeroes the reservation boards itself.  (The size is 0 for a non-positive argument or H, W > 256.)
+ * magat_sim_cases_generate_wide: H, W <= 256, N <= 4096 and N <= H * W; the maze bounds and first_case as below (kind and
+ * everything else are documented there; the MAGAT_CASES_* values are plain ints). */
+size_t magat_sim_mapf_wide_workspace_bytes(int C, int H, int W, int T);
+int magat_sim_mapf_plan_wide(const uint8_t* map, int map_batched, int H, int W, const int32_t* start, const int32_t* goal,
+                             const int32_t* order /* [C][N] or NULL = index order */, int32_t* paths /* [C][N][T][2] */,
+                             int32_t* lengths, int32_t* makespan, uint8_t* solved, int32_t* failed_agent, void* workspace,
+                             size_t workspace_bytes, int C, int N, int T, void* stream);
+int magat_sim_cases_generate_wide(int kind, const uint8_t* map_in /* NULL unless GIVEN */, int map_batched, int H, int W,
+                                  int aisles, int walk, uint64_t threshold, uint64_t seed, int64_t first_case,
+                                  uint8_t* map_out /* [C][H][W] */, int32_t* start, int32_t* goal /* [C][N][2] */,
+                                  int32_t* free_cells, uint8_t* valid, int C, int N, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Planning cases made on the device (sim_cases.hip; added behind ABI 9, nothing above changes): the first step of the expert
  * pipeline, the reference's offlineExpert/CasesGenerator.py - an obstacle map, its largest free component, a start and a goal
  * per agent - for C cases in one launch; its outputs are what magat_sim_mapf_plan takes.  Device pointers, stream ordered, no

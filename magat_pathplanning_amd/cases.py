@@ -19,6 +19,7 @@ from . import _native as nat
 
 KINDS = {"maze": 0, "uniform": 1, "given": 2}      # include/magat_hip.h MAGAT_CASES_*
 CASE_KEYS = ("map", "start", "goal", "free_cells", "valid")
+MAX_SIDE = 64      # above it: the wide form (csrc/sim_cases_wide.hip), maps up to 256 x 256
 
 
 def maze_steps(H, W, density, complexity):
@@ -32,7 +33,7 @@ def uniform_threshold(density):
 
 
 def generate_cases(C, H, W, N, density=0.1, complexity=0.01, kind="maze", obstacle_map=None, seed=0, first_case=0,
-                   device="cuda"):
+                   device="cuda", wide=False):
     """One call of magat_sim_cases_generate: C cases of N agents on H x W maps (H, W <= 64; N <= H * W).  Returns a dict of
     device tensors: map (C,H,W) uint8 (1: obstacle), start / goal (C,N,2) int32 (row, col), free_cells (C,) int32 and valid
     (C,) uint8.
@@ -50,7 +51,11 @@ def generate_cases(C, H, W, N, density=0.1, complexity=0.01, kind="maze", obstac
     an invalid case has start = goal = -1 and must not be fed to the solver: valid_cases(cases) drops it.
 
     seed (0 .. 2^64 - 1) and the global case index first_case + c fix a case: generate_cases(40, ...) equals
-    generate_cases(20, ...) followed by generate_cases(20, ..., first_case=20).  Stream ordered, no host synchronisation."""
+    generate_cases(20, ...) followed by generate_cases(20, ..., first_case=20).
+
+    wide=True lifts the limits to H, W <= 256 (and N <= 4096): a shape with H, W <= 64 still goes to
+    magat_sim_cases_generate, a larger one to magat_sim_cases_generate_wide - the same cases from the same draws, one
+    workgroup per case.  wide=False refuses H or W above 64 as before.  Stream ordered, no host synchronisation."""
     dev = torch.device(device)
     if dev.type != "cuda":
         raise nat.MagatNativeError("generate_cases: device must be a GPU (no CPU fallback), got %r" % (device,))
@@ -78,13 +83,13 @@ def generate_cases(C, H, W, N, density=0.1, complexity=0.01, kind="maze", obstac
                goal=torch.empty(max(C, 0), max(N, 0), 2, dtype=torch.int32, device=dev),
                free_cells=torch.empty(max(C, 0), dtype=torch.int32, device=dev),
                valid=torch.empty(max(C, 0), dtype=torch.uint8, device=dev))
+    entry = "magat_sim_cases_generate_wide" if wide and (H > MAX_SIDE or W > MAX_SIDE) else "magat_sim_cases_generate"
     with torch.cuda.device(dev):
-        nat.check(nat.lib().magat_sim_cases_generate(KINDS[kind], nat.ptr(m), 1 if m is not None and m.dim() == 3 else 0, H, W,
-                                                     aisles, walk, threshold, int(seed) & ((1 << 64) - 1), int(first_case),
-                                                     nat.ptr(out["map"]), nat.ptr(out["start"]), nat.ptr(out["goal"]),
-                                                     nat.ptr(out["free_cells"]), nat.ptr(out["valid"]), C, N,
-                                                     nat.current_stream(dev)),
-                  "magat_sim_cases_generate")
+        nat.check(getattr(nat.lib(), entry)(KINDS[kind], nat.ptr(m), 1 if m is not None and m.dim() == 3 else 0, H, W,
+                                            aisles, walk, threshold, int(seed) & ((1 << 64) - 1), int(first_case),
+                                            nat.ptr(out["map"]), nat.ptr(out["start"]), nat.ptr(out["goal"]),
+                                            nat.ptr(out["free_cells"]), nat.ptr(out["valid"]), C, N, nat.current_stream(dev)),
+                  entry)
     return out
 
 

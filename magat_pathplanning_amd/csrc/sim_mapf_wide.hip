@@ -1,0 +1,269 @@
+// The wide form of the path-finding expert of sim_mapf.hip: the same prioritized planning, cell for cell (restated
+// in tests/mapf_restatement.py), on maps up to 256 x 256 with horizons up to 1024.
+//   magat_sim_mapf_wide_workspace_bytes   C * T * 6 * rows * words * 8 bytes, rows = 64 * ceil(H / 64), words = 1, 2 or 4 >= W / 64
+//   magat_sim_mapf_plan_wide              one workgroup per case plans its agents one after another in `order`
+// One workgroup of `rows` threads per case, thread = map row, `words` 64-bit words per row in registers (row_board.h: wide
+// boards).  Left / right are multi-word shifts, up / down DPP wave shifts whose boundary rows cross the wavefronts through LDS:
+// one __syncthreads per layer, and the votes of the layer (goal reached, set empty; the backtrace's four candidates) ride on it.
+//   layers    global workspace [case][t][V, A_up, A_left, A_down, A_right, R][row][word]: the five reservation boards of a layer
+//             (zeroed here) and, behind them, the reachable set R_t of the agent being planned.  A thread loads and stores its
+//             own row of a board (8 * words contiguous bytes, coalesced over the threads).  The reservation boards do not depend
+//             on the search, nor do the R layers on the walk back, so both loops keep WMAPF_AHEAD layers of loads in flight.
+//   path      LDS, (row << 8 | col) per step, written by thread 0 in the backtrace; reserving it and writing it out is
+//             parallel over t.
+// Every store is a per-lane (vector) store from plain C++.
+#include <cstdint>
+
+#include "magat_common.h"
+#include "row_board.h"
+
+namespace {
+
+constexpr int WMAPF_MAX_T = 1024;
+constexpr int WMAPF_BOARDS = 6;      // V, then A_d in the key order up, left, down, right, then R
+constexpr int WMAPF_R = 5;
+constexpr int WMAPF_AHEAD = 4;       // layers of boards in flight
+
+__host__ __device__ constexpr int wide_rows(int H) { return 64 * ((H + 63) / 64); }
+__host__ __device__ constexpr int wide_words(int W) { return W <= 64 ? 1 : W <= 128 ? 2 : 4; }
+
+// the layers of one case: every thread touches its own row of a board, but for the reservations of a path
+template <int NW>
+struct wide_layers {
+  u64* base;
+  int rows;
+  __device__ __forceinline__ u64* at(int t, int b, int row) const { return base + (((long long)t * WMAPF_BOARDS + b) * rows + row) * NW; }
+  __device__ __forceinline__ wboard<NW> load(int t, int b, int row) const {
+    wboard<NW> r;
+    const u64* p = at(t, b, row);
+#pragma unroll
+    for (int k = 0; k < NW; ++k) r.w[k] = p[k];
+    return r;
+  }
+  __device__ __forceinline__ void store(int t, int b, int row, const wboard<NW>& v) const {
+    u64* p = at(t, b, row);
+#pragma unroll
+    for (int k = 0; k < NW; ++k) p[k] = v.w[k];
+  }
+};
+
+// R_0 = {start}; R_{t+1} = free & ~V[t+1] & (R_t | U_d shift_d(R_t & ~A_opp(d)[t+1])).  Returns t* = the first t > last with the
+// goal in R_t (last: the largest t with the goal in V[t]), or -1: R_t ran empty or t reached T - 1.  The same for every thread.
+template <int NW>
+__device__ int wmapf_search(const wide_layers<NW>& L, wide_seat& s, const wboard<NW>& free, int sr, int sc, int gr, int gc, int T,
+                            int tid, int nt) {
+  int hit = -1;      // threads over t, ascending: the last hit of the wave is its largest
+  for (int base = 0; base < T; base += nt) {
+    const int t = base + tid;
+    const u64 m = __builtin_amdgcn_ballot_w64(t < T && has_bit(L.at(t < T ? t : 0, 0, gr)[gc >> 6], gc & 63));
+    if (m) hit = base + 64 * s.wave + 63 - __clzll(m);
+  }
+  wide_post(s, 0, hit);
+  const int last = wide_max(s, wide_sync(s), 0);
+  if (last >= T - 1) return -1;      // the goal is held for ever
+  wboard<NW> cur = tid == sr ? wb_bit<NW>(sc) : wb_zero<NW>();
+  L.store(0, WMAPF_R, tid, cur);
+  wboard<NW> ahead[WMAPF_AHEAD][5];
+#pragma unroll
+  for (int k = 0; k < WMAPF_AHEAD; ++k)
+#pragma unroll
+    for (int b = 0; b < 5; ++b) ahead[k][b] = 1 + k < T ? L.load(1 + k, b, tid) : wb_zero<NW>();
+  for (int t0 = 0;; t0 += WMAPF_AHEAD) {
+#pragma unroll
+    for (int k = 0; k < WMAPF_AHEAD; ++k) {
+      const int t = t0 + k;      // cur = R_t, ahead[k] = the boards of layer t + 1
+      const wboard<NW> v = ahead[k][0], a_up = ahead[k][1], a_left = ahead[k][2], a_down = ahead[k][3], a_right = ahead[k][4];
+      const int tn = t + 1 + WMAPF_AHEAD;
+#pragma unroll
+      for (int b = 0; b < 5; ++b) ahead[k][b] = tn < T ? L.load(tn, b, tid) : wb_zero<NW>();
+      // the swap rule: u -> u + d is closed when a planned agent enters u in the direction opposite to d in the same step
+      const wboard<NW> going_up = cur & ~a_down, going_down = cur & ~a_up;
+      wide_post_rows(s, going_up, going_down);
+      wide_post(s, 0, (int)wave_any(tid == gr && wb_has(cur, gc)) | (int)wave_any(wb_any(cur)) << 1);
+      const int p = wide_sync(s);
+      const int votes = wide_or(s, p, 0);
+      if (t > last && (votes & 1)) return t;
+      if (t == T - 1 || !(votes & 2)) return -1;
+      const wboard<NW> moved = wide_cells_up(s, p, going_up) | wb_left(cur & ~a_right) | wide_cells_down(s, p, going_down) |
+                               wb_right(cur & ~a_left);
+      cur = (cur | moved) & free & ~v;
+      L.store(t + 1, WMAPF_R, tid, cur);
+    }
+  }
+}
+
+// Walks from (goal, t*) down to t = 1: the move INTO (r, c) is the first of up, left, down, right, stop whose source cell is in
+// R_{t-1} and, for a real move, not in A_opp(d)[t].  Each candidate is tested by the thread of its row (a row off the map has
+// no thread or an empty row), the workgroup votes.  Thread 0 writes the cells.
+template <int NW>
+__device__ void wmapf_backtrace(const wide_layers<NW>& L, wide_seat& s, int* cells, int gr, int gc, int tstar, int W, int tid) {
+  int r = gr, c = gc;
+  if (tid == 0) cells[tstar] = r << 8 | c;
+  wboard<NW> ahead[WMAPF_AHEAD][5];      // A_up, A_left, A_down, A_right of layer t, and R_{t-1}
+#pragma unroll
+  for (int k = 0; k < WMAPF_AHEAD; ++k)
+#pragma unroll
+    for (int b = 0; b < 5; ++b)
+      ahead[k][b] = tstar - k >= 1 ? (b < 4 ? L.load(tstar - k, 1 + b, tid) : L.load(tstar - k - 1, WMAPF_R, tid)) : wb_zero<NW>();
+  for (int t0 = tstar; t0 >= 1; t0 -= WMAPF_AHEAD) {
+#pragma unroll
+    for (int k = 0; k < WMAPF_AHEAD; ++k) {
+      const int t = t0 - k;
+      if (t < 1) break;
+      const wboard<NW> a_up = ahead[k][0], a_left = ahead[k][1], a_down = ahead[k][2], a_right = ahead[k][3], prev = ahead[k][4];
+      const int tn = t - WMAPF_AHEAD;
+#pragma unroll
+      for (int b = 0; b < 5; ++b)
+        ahead[k][b] = tn >= 1 ? (b < 4 ? L.load(tn, 1 + b, tid) : L.load(tn - 1, WMAPF_R, tid)) : wb_zero<NW>();
+      const bool up = tid == r + 1 && wb_has(prev & ~a_down, c);                      // moved up: came from the row below
+      const bool left = tid == r && c + 1 < W && wb_has(prev & ~a_right, c + 1 < W ? c + 1 : c);
+      const bool down = tid == r - 1 && wb_has(prev & ~a_up, c);
+      const bool right = tid == r && c >= 1 && wb_has(prev & ~a_left, c >= 1 ? c - 1 : c);
+      wide_post(s, 0, (int)wave_any(up) | (int)wave_any(left) << 1 | (int)wave_any(down) << 2 | (int)wave_any(right) << 3);
+      const int votes = wide_or(s, wide_sync(s), 0);
+      if (votes & 1) r += 1;
+      else if (votes & 2) c += 1;
+      else if (votes & 4) r -= 1;
+      else if (votes & 8) c -= 1;      // else stop: (r, c) is in R_{t-1}
+      if (tid == 0) cells[t - 1] = r << 8 | c;
+    }
+  }
+}
+
+template <int NW>
+__global__ __launch_bounds__(WIDE_SIDE) void wmapf_plan_kernel(const uint8_t* __restrict__ map, long long map_stride, int H, int W,
+                                                               const int* __restrict__ start, const int* __restrict__ goal,
+                                                               const int* __restrict__ order, int* paths, int* lengths,
+                                                               int* __restrict__ makespan, uint8_t* __restrict__ solved,
+                                                               int* __restrict__ failed_agent, u64* workspace, int N, int T) {
+  __shared__ wide_mail mail;
+  __shared__ int cells[WMAPF_MAX_T];      // the path being reserved
+  const int cs = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;      // nt = rows
+  wide_seat s{&mail, tid & 63, tid >> 6, nt >> 6, 0};
+  const long long layer_words = (long long)WMAPF_BOARDS * nt * NW;
+  const wide_layers<NW> L{workspace + (long long)cs * T * layer_words, nt};
+  for (int t = 0; t < T; ++t)      // the reservation boards; an R layer is written before it is read
+    for (int i = tid; i < 5 * nt * NW; i += nt) L.base[t * layer_words + i] = 0ull;
+  // free cells: the rows of this wave, each read by the lanes over its columns, one ballot per word; rows >= H and bits >= W
+  // stay zero
+  const uint8_t* mp = map + cs * map_stride;
+  wboard<NW> free = wb_zero<NW>();
+  for (int r = 64 * s.wave; r < H && r < 64 * s.wave + 64; ++r) {
+#pragma unroll
+    for (int k = 0; k < NW; ++k) {
+      const int col = 64 * k + s.lane;
+      const u64 word = __builtin_amdgcn_ballot_w64(col < W && mp[r * W + (col < W ? col : 0)] == 0);
+      if (tid == r) free.w[k] = word;
+    }
+  }
+  const long long a0 = (long long)cs * N;
+  const int* ord = order ? order + a0 : nullptr;
+  int* len = lengths + a0;
+  // is `order` a permutation?  N entries in range, none named twice (counted in `lengths`, which is written again below)
+  bool bad_order = false;
+  if (ord) {
+    for (int n = tid; n < N; n += nt) len[n] = 0;
+    __syncthreads();
+    bool bad = false;
+    for (int k = tid; k < N; k += nt) {
+      const int a = ord[k];
+      if (a < 0 || a >= N || atomicAdd(&len[a], 1) != 0) bad = true;
+    }
+    wide_post(s, 0, (int)wave_any(bad));
+    bad_order = wide_or(s, wide_sync(s), 0) != 0;
+  }
+  __syncthreads();      // the zeroed boards, and the counts before `lengths` is written
+  wboard<NW> starts = wb_zero<NW>(), goals = wb_zero<NW>();      // the planned agents' start and goal cells
+  int failed = bad_order ? -2 : -1, longest = 1, k = 0;
+  for (; failed == -1 && k < N; ++k) {
+    const int a = __builtin_amdgcn_readfirstlane(ord ? ord[k] : k);
+    const int sr = start[(a0 + a) * 2], sc = start[(a0 + a) * 2 + 1], gr = goal[(a0 + a) * 2], gc = goal[(a0 + a) * 2 + 1];
+    const bool inside = sr >= 0 && sr < H && sc >= 0 && sc < W && gr >= 0 && gr < H && gc >= 0 && gc < W;
+    const wboard<NW> sbit = inside ? wb_bit<NW>(sc) : wb_zero<NW>(), gbit = inside ? wb_bit<NW>(gc) : wb_zero<NW>();
+    wide_post(s, 0, (int)wave_any(tid == sr && wb_any(free & ~starts & sbit)) | (int)wave_any(tid == gr && wb_any(free & ~goals & gbit)) << 1);
+    const bool ok = wide_or(s, wide_sync(s), 0) == 3;
+    const int tstar = ok ? wmapf_search<NW>(L, s, free, sr, sc, gr, gc, T, tid, nt) : -1;
+    if (tstar < 0) {
+      failed = a;
+      break;
+    }
+    wmapf_backtrace<NW>(L, s, cells, gr, gc, tstar, W, tid);
+    __syncthreads();
+    // reserve and write out, threads over t: layer t belongs to one thread, so no two threads touch one word
+    int* p = paths + (a0 + a) * T * 2;
+    for (int t = tid; t < T; t += nt) {
+      const int cell = cells[t < tstar ? t : tstar], cr = cell >> 8, cc = cell & 255;
+      L.at(t, 0, cr)[cc >> 6] |= 1ull << (cc & 63);
+      if (t >= 1 && t <= tstar) {
+        const int from = cells[t - 1], dr = cr - (from >> 8), dc = cc - (from & 255);
+        const int d = dr == -1 ? 0 : dc == -1 ? 1 : dr == 1 ? 2 : dc == 1 ? 3 : 4;
+        if (d < 4) L.at(t, 1 + d, cr)[cc >> 6] |= 1ull << (cc & 63);
+      }
+      p[2 * t] = cr;
+      p[2 * t + 1] = cc;
+    }
+    if (tid == 0) len[a] = tstar + 1;
+    if (tid == sr) starts = starts | sbit;
+    if (tid == gr) goals = goals | gbit;
+    longest = tstar + 1 > longest ? tstar + 1 : longest;
+    __syncthreads();      // the next agent loads these boards and reuses `cells`
+  }
+  // the failing agent and the agents behind it (every agent when `order` is no permutation): the start cell, length 1
+  if (failed != -1) {
+    for (; k < N; ++k) {
+      const int a = failed == -2 ? k : __builtin_amdgcn_readfirstlane(ord ? ord[k] : k);
+      const int sr = start[(a0 + a) * 2], sc = start[(a0 + a) * 2 + 1];
+      int* p = paths + (a0 + a) * T * 2;
+      for (int t = tid; t < T; t += nt) {
+        p[2 * t] = sr;
+        p[2 * t + 1] = sc;
+      }
+      if (tid == 0) len[a] = 1;
+    }
+  }
+  if (tid == 0) {
+    makespan[cs] = longest - 1;
+    solved[cs] = failed == -1 ? 1 : 0;
+    failed_agent[cs] = failed;
+  }
+}
+
+}  // namespace
+
+extern "C" size_t magat_sim_mapf_wide_workspace_bytes(int C, int H, int W, int T) {
+  if (C <= 0 || H <= 0 || W <= 0 || T <= 0 || H > WIDE_SIDE || W > WIDE_SIDE) return 0;
+  return (size_t)C * T * WMAPF_BOARDS * wide_rows(H) * wide_words(W) * sizeof(u64);
+}
+
+extern "C" int magat_sim_mapf_plan_wide(const uint8_t* map, int map_batched, int H, int W, const int32_t* start, const int32_t* goal,
+                                        const int32_t* order, int32_t* paths, int32_t* lengths, int32_t* makespan, uint8_t* solved,
+                                        int32_t* failed_agent, void* workspace, size_t workspace_bytes, int C, int N, int T,
+                                        void* stream) {
+  if (!map || !start || !goal || !paths || !lengths || !makespan || !solved || !failed_agent || !workspace) return MAGAT_ERR_NULL;
+  if (H <= 0 || W <= 0 || C <= 0 || N <= 0 || T <= 0) return MAGAT_ERR_BAD_SHAPE;
+  if (H > WIDE_SIDE || W > WIDE_SIDE || T > WMAPF_MAX_T) return MAGAT_ERR_UNSUPPORTED;
+  if (workspace_bytes < magat_sim_mapf_wide_workspace_bytes(C, H, W, T)) return MAGAT_ERR_UNSUPPORTED;
+  if (reinterpret_cast<uintptr_t>(workspace) % sizeof(u64)) return MAGAT_ERR_WORKSPACE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const dim3 grid((unsigned)C), block((unsigned)wide_rows(H));
+  const long long map_stride = map_batched ? (long long)H * W : 0LL;
+  u64* ws = static_cast<u64*>(workspace);
+  magat_form_note(MAGAT_FORM_SIM_MAPF);
+  const int pid = magat_prof_begin(MAGAT_TAG_SIM_MAPF, st);
+  switch (wide_words(W)) {
+    case 1:
+      hipLaunchKernelGGL(wmapf_plan_kernel<1>, grid, block, 0, st, map, map_stride, H, W, start, goal, order, paths, lengths, makespan,
+                         solved, failed_agent, ws, N, T);
+      break;
+    case 2:
+      hipLaunchKernelGGL(wmapf_plan_kernel<2>, grid, block, 0, st, map, map_stride, H, W, start, goal, order, paths, lengths, makespan,
+                         solved, failed_agent, ws, N, T);
+      break;
+    default:
+      hipLaunchKernelGGL(wmapf_plan_kernel<4>, grid, block, 0, st, map, map_stride, H, W, start, goal, order, paths, lengths, makespan,
+                         solved, failed_agent, ws, N, T);
+      break;
+  }
+  magat_prof_end(pid, st);
+  return magat_check_launch();
+}

@@ -22,14 +22,16 @@ from . import _native as nat
 from .simulator import _dev_i32
 
 MAX_HORIZON = 256
+MAX_SIDE = 64
+WIDE_MAX_HORIZON = 1024      # the wide form (csrc/sim_mapf_wide.hip): maps up to 256 x 256
 PACK_KEYS = ("paths", "lengths", "goal", "start", "makespan")
 
 
-def default_horizon(H, W, N):
-    return min(MAX_HORIZON, 2 * (H + W) + N)
+def default_horizon(H, W, N, wide=False):
+    return min(WIDE_MAX_HORIZON if wide else MAX_HORIZON, 2 * (H + W) + N)
 
 
-def plan_prioritized(obstacle_map, start, goal, order=None, horizon=None):
+def plan_prioritized(obstacle_map, start, goal, order=None, horizon=None, wide=False):
     """One call of magat_sim_mapf_plan: obstacle_map (H,W) or (C,H,W) (non-zero: obstacle; H, W <= 64), start / goal (C,N,2)
     (row, col), order (C,N): each case's priority order, a permutation of its agents (None: index order).  Agents are planned
     one after another; each takes the earliest arrival that the agents before it leave open, waits included, and holds its
@@ -41,6 +43,12 @@ def plan_prioritized(obstacle_map, start, goal, order=None, horizon=None):
 
     horizon: the most cells a path may have, at most 256; the default min(256, 2 * (H + W) + N) is a default, not a
     guarantee - it has not been measured against any family of maps, and a case whose agents need longer comes back unsolved.
+
+    wide=True lifts the limits to H, W <= 256 and horizon <= 1024 (default min(1024, 2 * (H + W) + N), likewise not measured
+    against any family of maps): a shape with H, W <= 64 and horizon <= 256 still goes to magat_sim_mapf_plan, with the same
+    result as wide=False; a larger one to magat_sim_mapf_plan_wide - the same algorithm, one workgroup per case, and a
+    workspace of horizon * 6 * 64 ceil(H / 64) * (1, 2 or 4 words >= W / 64) * 8 bytes per case.  wide=False refuses H or W
+    above 64 and horizons above 256 as before.
     Stream ordered, no host synchronisation."""
     start, goal = _dev_i32(start, "start"), _dev_i32(goal, "goal")
     if not isinstance(obstacle_map, torch.Tensor) or not obstacle_map.is_cuda:
@@ -53,20 +61,22 @@ def plan_prioritized(obstacle_map, start, goal, order=None, horizon=None):
     if order is not None:
         order = _dev_i32(order, "order")
         assert tuple(order.shape) == (C, N), "order must be (C,N)"
-    T = default_horizon(H, W, N) if horizon is None else int(horizon)
+    T = default_horizon(H, W, N, wide) if horizon is None else int(horizon)
     dev = start.device
     lib = nat.lib()
+    to_wide = bool(wide) and (H > MAX_SIDE or W > MAX_SIDE or T > MAX_HORIZON)
     paths = torch.empty(C, N, T, 2, dtype=torch.int32, device=dev)
     lengths = torch.empty(C, N, dtype=torch.int32, device=dev)
     makespan = torch.empty(C, dtype=torch.int32, device=dev)
     solved = torch.empty(C, dtype=torch.uint8, device=dev)
     failed = torch.empty(C, dtype=torch.int32, device=dev)
-    ws = torch.empty(max(int(lib.magat_sim_mapf_workspace_bytes(C, T)), 8), dtype=torch.uint8, device=dev)
+    ws_bytes = lib.magat_sim_mapf_wide_workspace_bytes(C, H, W, T) if to_wide else lib.magat_sim_mapf_workspace_bytes(C, T)
+    ws = torch.empty(max(int(ws_bytes), 8), dtype=torch.uint8, device=dev)
+    entry = "magat_sim_mapf_plan_wide" if to_wide else "magat_sim_mapf_plan"
     with torch.cuda.device(dev):
-        nat.check(lib.magat_sim_mapf_plan(nat.ptr(m), 1 if m.dim() == 3 else 0, H, W, nat.ptr(start), nat.ptr(goal),
-                                          nat.ptr(order), nat.ptr(paths), nat.ptr(lengths), nat.ptr(makespan), nat.ptr(solved),
-                                          nat.ptr(failed), nat.ptr(ws), ws.numel(), C, N, T, nat.current_stream(dev)),
-                  "magat_sim_mapf_plan")
+        nat.check(getattr(lib, entry)(nat.ptr(m), 1 if m.dim() == 3 else 0, H, W, nat.ptr(start), nat.ptr(goal),
+                                      nat.ptr(order), nat.ptr(paths), nat.ptr(lengths), nat.ptr(makespan), nat.ptr(solved),
+                                      nat.ptr(failed), nat.ptr(ws), ws.numel(), C, N, T, nat.current_stream(dev)), entry)
     return dict(paths=paths, lengths=lengths, goal=goal, start=start, makespan=makespan, solved=solved, failed_agent=failed)
 
 
@@ -78,7 +88,7 @@ def promote(order, agent):
     return torch.gather(order, 1, rest)
 
 
-def solve_cases(obstacle_map, start, goal, horizon=None, retries=8):
+def solve_cases(obstacle_map, start, goal, horizon=None, retries=8, wide=False):
     """plan_prioritized in index order, then up to `retries` re-plans of the cases still unsolved, each with that case's
     failed_agent moved to the front of its order.  Returns plan_prioritized's dict (every case holds its LAST plan) plus order
     (C,N) int32 (the order of that plan), rounds (C,) int32 (the plans made for the case, 1 = solved at once) and T =
@@ -89,8 +99,9 @@ def solve_cases(obstacle_map, start, goal, horizon=None, retries=8):
     idx = res["solved"].nonzero().flatten(); tensor.index_select(0, idx) for every tensor of the dict - and returns exactly
     the keys that expert_samples takes as **pack.
 
+    wide: as in plan_prioritized, for the first plan and every re-plan.
     One host synchronisation per round (the read of `solved`), one more for T."""
-    res = plan_prioritized(obstacle_map, start, goal, None, horizon)
+    res = plan_prioritized(obstacle_map, start, goal, None, horizon, wide)
     C, N, _ = res["start"].shape
     dev = res["start"].device
     order = torch.arange(N, dtype=torch.int32, device=dev).repeat(C, 1)
@@ -103,7 +114,7 @@ def solve_cases(obstacle_map, start, goal, horizon=None, retries=8):
             break
         again = promote(order.index_select(0, idx), res["failed_agent"].index_select(0, idx))
         sub = plan_prioritized(obstacle_map.index_select(0, idx) if batched else obstacle_map,
-                               res["start"].index_select(0, idx), res["goal"].index_select(0, idx), again, T)
+                               res["start"].index_select(0, idx), res["goal"].index_select(0, idx), again, T, wide)
         for key in ("paths", "lengths", "makespan", "solved", "failed_agent"):
             res[key].index_copy_(0, idx, sub[key])
         order.index_copy_(0, idx, again)

@@ -1,8 +1,11 @@
-"""Times the path-finding expert (magat_pathplanning_amd/mapf.py, csrc/sim_mapf.hip) at two batch shapes:
+"""Times the path-finding expert (magat_pathplanning_amd/mapf.py, csrc/sim_mapf.hip) at two batch shapes, and its wide form
+(csrc/sim_mapf_wide.hip, wide=True, the default wide horizon) at two more:
 
     512 cases of 20 x 20 / 10 agents / T = 64          128 cases of 50 x 50 / 100 agents / T = 128
+    64 cases of 65 x 65 / 100 agents / T = 360         8 cases of 200 x 200 / 1000 agents / T = 1024
 
-Device events around plan_prioritized (10 warm-ups, median of 50 calls), the share of cases solved at the first try and after
+Device events around plan_prioritized (10 warm-ups, median of 50 calls; when one call takes more than a second, 1 warm-up and
+the median of 5, and the line says so in "calls"), the share of cases solved at the first try and after
 solve_cases' retries, and - with --restatement K - the CPU seconds that tests/mapf_restatement.py (a per-cell Python
 restatement, NOT ECBS; the only comparison there is) needs for the first K cases of each shape.  One JSON line per shape.
 
@@ -21,7 +24,9 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import mapf_restatement as mr  # noqa: E402
 
 SHAPES = (dict(name="20x20_n10", C=512, size=20, N=10, T=64, density=0.1, seed=101),
-          dict(name="50x50_n100", C=128, size=50, N=100, T=128, density=0.1, seed=102))
+          dict(name="50x50_n100", C=128, size=50, N=100, T=128, density=0.1, seed=102),
+          dict(name="wide_65x65_n100", C=64, size=65, N=100, T=360, density=0.1, seed=103, wide=True),
+          dict(name="wide_200x200_n1000", C=8, size=200, N=1000, T=1024, density=0.1, seed=104, wide=True))
 
 
 def main():
@@ -39,20 +44,27 @@ def main():
             from magat_pathplanning_amd import plan_prioritized, solve_cases
             assert torch.cuda.is_available(), "mapf_bench needs a GPU (no fallback)"
             d = [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in (m, start, goal)]
-            for _ in range(args.warmup):
-                res = plan_prioritized(*d, horizon=sh["T"])
+            wide = sh.get("wide", False)
+            t0 = time.perf_counter()
+            res = plan_prioritized(*d, horizon=sh["T"], wide=wide)
+            torch.cuda.synchronize()
+            slow = time.perf_counter() - t0 > 1.0      # (the first call of a process also loads the code object)
+            warmup, calls = (1, min(args.calls, 5)) if slow else (args.warmup, args.calls)
+            out.update(warmup=warmup, calls=calls)
+            for _ in range(warmup):
+                res = plan_prioritized(*d, horizon=sh["T"], wide=wide)
             torch.cuda.synchronize()
             ms = []
-            for _ in range(args.calls):
+            for _ in range(calls):
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
                 e0.record()
-                res = plan_prioritized(*d, horizon=sh["T"])
+                res = plan_prioritized(*d, horizon=sh["T"], wide=wide)
                 e1.record()
                 e1.synchronize()
                 ms.append(e0.elapsed_time(e1))
             ms.sort()
             t0 = time.perf_counter()
-            full = solve_cases(*d, horizon=sh["T"], retries=8)
+            full = solve_cases(*d, horizon=sh["T"], retries=8, wide=wide)
             torch.cuda.synchronize()
             solve_ms = (time.perf_counter() - t0) * 1e3
             solved = full["solved"] != 0
