@@ -281,6 +281,21 @@ int magat_sim_fov_states(const uint8_t* map, int map_batched, int H, int W, cons
 int magat_sim_guided_states(const uint8_t* map, int map_batched, int H, int W, const int32_t* pos, const int32_t* goal,
                             float* x, int FOV, int B, int N, int mode, int dynamic_obstacles, uint8_t* agent_view,
                             void* stream);
+/* magat_sim_guided_states_wide: MAGAT_GUIDE_GLOBAL and MAGAT_GUIDE_SEMI on maps up to 256 x 256 (any FOV the narrow entry takes:
+ *   a canvas of up to 286 x 286 cells, 266 x 266 at FOV 9), the same search step for step and the same tensors; a shape the
+ *   narrow entry takes gives the same bits here.  The grid / closed board and the two parent-bit boards stay in LDS, 2 to 5
+ *   64-bit words a canvas row; the open list - one 64-bit entry a cell, f << 36 | g << 18 | row << 9 | col, room for every cell
+ *   of the canvas - lives in `workspace`: min(B N, 1024) workgroups of one wavefront are launched, each owns one slab of
+ *   (H + 2(FOV/2) + 2) (W + 2(FOV/2) + 2) entries and walks the agents blockIdx, blockIdx + gridDim, ...
+ *   magat_sim_guided_states_wide_workspace_bytes(B, N, H, W, FOV) = min(B N, 1024) * canvas rows * canvas columns * 8 (0 for a
+ *   shape the entry refuses); 8-byte aligned; not read before it is written, nothing to zero.  Checks in the narrow entry's
+ *   order and with its codes, MAGAT_GUIDE_LOCAL and H or W > 256 MAGAT_ERR_UNSUPPORTED; then workspace NULL MAGAT_ERR_NULL,
+ *   too small MAGAT_ERR_UNSUPPORTED, misaligned MAGAT_ERR_WORKSPACE (magat_sim_mapf_plan_wide's codes) - nothing is launched.
+ *   Same profiling tag and form counter as the narrow entry, no host synchronisation. */
+size_t magat_sim_guided_states_wide_workspace_bytes(int B, int N, int H, int W, int FOV);
+int magat_sim_guided_states_wide(const uint8_t* map, int map_batched, int H, int W, const int32_t* pos, const int32_t* goal,
+                                 float* x, int FOV, int B, int N, int mode, int dynamic_obstacles, uint8_t* agent_view,
+                                 void* workspace, size_t workspace_bytes, void* stream);
 
 /* magat_sim_move: multiRobotSimNew.move + check_collision (utils/new_simulator.py:334-454, 471-520),
  *   batched: action key = argmax of the 5 logits (convectToActionKey_softmax :863-869; or given keys `actions_in`), proposed
@@ -332,6 +347,17 @@ typedef struct magat_sim_step_desc {
   int32_t* makespan_out;     /* [B] or NULL */
 } magat_sim_step_desc;
 int magat_sim_step(const magat_sim_step_desc* d, void* stream);
+
+/* magat_sim_move_wide / magat_sim_step_wide: magat_sim_move / magat_sim_step, rule for rule and flag for flag, with the cell
+ * grid in `workspace` instead of LDS: H, W <= 256 and N <= 4096 (otherwise MAGAT_ERR_UNSUPPORTED, nothing is launched).
+ * magat_sim_move_wide_workspace_bytes(B, H, W, N) = B * H * W * 4 (0 for a shape the entries refuse), 4-byte aligned, written
+ * before it is read.  workspace NULL MAGAT_ERR_NULL, too small MAGAT_ERR_UNSUPPORTED, misaligned MAGAT_ERR_WORKSPACE.  One
+ * workgroup per instance, 16 N bytes of LDS. */
+size_t magat_sim_move_wide_workspace_bytes(int B, int H, int W, int N);
+int magat_sim_move_wide(const float* logits, const int32_t* actions_in, const uint8_t* map, int map_batched, int H, int W,
+                        int32_t* pos, const int32_t* goal, int32_t* actions_out, int8_t* moves_out, uint8_t* reached_out,
+                        int32_t* flags_out, int B, int N, void* workspace, size_t workspace_bytes, void* stream);
+int magat_sim_step_wide(const magat_sim_step_desc* d, void* workspace, size_t workspace_bytes, void* stream);
 
 /* Dense GSO -> everything the CSR kernels need, for N <= 1024, in ONE streaming pass over S plus one small kernel, with no
  * host synchronisation: addGSO's in-place scrub (scrub_nan / gso_mode 0|1 as magat_gso_prepare; values are written back only

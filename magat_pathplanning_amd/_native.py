@@ -126,6 +126,11 @@ _SIGNATURES = {
     "magat_sim_fov_states": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P]),
     "magat_sim_guided_states": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P]),
     "magat_sim_move": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
+    "magat_sim_guided_states_wide_workspace_bytes": (_Z, [_I] * 5),
+    "magat_sim_guided_states_wide": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _Z, _P]),
+    "magat_sim_move_wide_workspace_bytes": (_Z, [_I] * 4),
+    "magat_sim_move_wide": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _Z, _P]),
+    "magat_sim_step_wide": (_I, [ctypes.POINTER(SimStepDesc), _P, _Z, _P]),
     "magat_gso_prepare": (_I, [_P, _I, _Z, _I, _I, _P]),
     "magat_conv_gemm_f32": (_I, [ctypes.POINTER(ConvGemmDesc), _P]),
     "magat_conv_wgrad_workspace_floats": (_Z, [_I] * 7),

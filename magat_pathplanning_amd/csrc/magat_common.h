@@ -129,6 +129,7 @@ enum MagatLdsSlot {
   MAGAT_LDS_GNND_0,      // gnn_dense.hip: 5 slots (column slice x rows per thread)
   MAGAT_LDS_GNND_END = MAGAT_LDS_GNND_0 + 5,
   MAGAT_LDS_SIM_MAPF = MAGAT_LDS_GNND_END,      // sim_mapf.hip: the R layers of horizons above 128
+  MAGAT_LDS_SIM_MOVE_WIDE,                      // sim_frontend.hip: the move step with its cell grid in a workspace, N near 4096
   MAGAT_LDS_END
 };
 static_assert(MAGAT_LDS_END <= MAGAT_LDS_SLOTS, "LDS attribute slots");

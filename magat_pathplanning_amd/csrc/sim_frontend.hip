@@ -505,6 +505,9 @@ __global__ __launch_bounds__(SIM_THREADS) void sim_radius_kernel(const int* __re
 // One workgroup per instance; a single int32 cell grid in LDS is reused for the three lookups the reference does with
 // Python dicts: occupant of a cell (swap test), claimants of a target cell (atomicMin of a priority key), and the
 // "forced to stay" cells of the backward cascade.
+// WIDE (magat_sim_move_wide / magat_sim_step_wide, maps up to 256 x 256): the same body with the cell grid in the caller's
+// workspace, 4 H W bytes an instance, instead of LDS; the per-agent arrays stay in LDS.  An instance is still one workgroup, and
+// __syncthreads() orders the workgroup's global stores, loads and atomics between the phases exactly as it orders the LDS ones.
 struct SimBook {
   uint8_t* reach;          // [B][N] sticky reach-goal flags (null: no bookkeeping)
   int* first_move;         // [B][N]
@@ -515,13 +518,14 @@ struct SimBook {
   int* makespan_out;       // [B]
 };
 
+template <bool WIDE>
 __global__ __launch_bounds__(1024) void sim_move_kernel(const float* __restrict__ logits, const int* __restrict__ actions_in,
                                                         const uint8_t* __restrict__ map, long long map_stride, int H, int Wm,
                                                         int* __restrict__ pos, const int* __restrict__ goal,
                                                         int* __restrict__ actions_out, signed char* __restrict__ moves_out,
                                                         uint8_t* __restrict__ reached_out, int* __restrict__ flags_out,
                                                         int N, int policy, const double* __restrict__ uniforms,
-                                                        SimBook bk) {
+                                                        SimBook bk, unsigned* wide_grid) {
   extern __shared__ __align__(16) unsigned char smem_raw[];
   const int b = blockIdx.x, t = threadIdx.x, nt = blockDim.x;
   const int cells = H * Wm;
@@ -551,8 +555,8 @@ __global__ __launch_bounds__(1024) void sim_move_kernel(const float* __restrict_
     if (flags_out && t == 0) flags_out[b] = 0;
   }
   if (active) {
-  unsigned* grid = reinterpret_cast<unsigned*>(smem_raw);            // [cells]
-  int* px = reinterpret_cast<int*>(grid + cells);                    // [N]
+  unsigned* grid = WIDE ? wide_grid + (long long)b * cells : reinterpret_cast<unsigned*>(smem_raw);      // [cells]
+  int* px = WIDE ? reinterpret_cast<int*>(smem_raw) : reinterpret_cast<int*>(grid + cells);              // [N]
   int* py = px + N;
   int* mc = py + N;                                                  // move code 0..4 (4 = stop)
   int* aux = mc + N;                                                 // per-agent scratch: swap flag, then forced flag
@@ -791,35 +795,48 @@ extern "C" int magat_sim_fov_states(const uint8_t* map, int map_batched, int H, 
 }
 
 namespace {
+constexpr int MOVE_WIDE_SIDE = 256, MOVE_WIDE_AGENTS = 4096;
+
+// workspace == nullptr: the form with the cell grid in LDS (magat_sim_move, magat_sim_step)
 int sim_move_launch(const float* logits, const int32_t* actions_in, const uint8_t* map, int map_batched, int H, int W,
                     int32_t* pos, const int32_t* goal, int32_t* actions_out, int8_t* moves_out, uint8_t* reached_out,
-                    int32_t* flags_out, int B, int N, int policy, const double* uniforms, const SimBook& bk, void* stream) {
+                    int32_t* flags_out, int B, int N, int policy, const double* uniforms, const SimBook& bk, void* stream,
+                    bool wide = false, void* workspace = nullptr, size_t workspace_bytes = 0) {
   if ((!logits && !actions_in) || !map || !pos) return MAGAT_ERR_NULL;
   if (B <= 0 || N <= 0 || N > 65535 || H <= 0 || W <= 0) return MAGAT_ERR_BAD_SHAPE;
   if (policy < 0 || policy > 2) return MAGAT_ERR_UNSUPPORTED;
   if (policy != 0 && (!logits || !uniforms)) return MAGAT_ERR_NULL;
+  int threads = 64;
+  while (threads < N && threads < 1024) threads *= 2;
+  const long long map_stride = map_batched ? (long long)H * W : 0LL;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (wide) {
+    if (H > MOVE_WIDE_SIDE || W > MOVE_WIDE_SIDE || N > MOVE_WIDE_AGENTS) return MAGAT_ERR_UNSUPPORTED;
+    if (!workspace) return MAGAT_ERR_NULL;
+    if (workspace_bytes < magat_sim_move_wide_workspace_bytes(B, H, W, N)) return MAGAT_ERR_UNSUPPORTED;
+    if (reinterpret_cast<uintptr_t>(workspace) % sizeof(unsigned)) return MAGAT_ERR_WORKSPACE;
+    const size_t lds = (size_t)4 * N * sizeof(int);                  // <= 64 KB, next to the kernel's few static words
+    threads = 1024;                                                  // the three fills of the grid are global stores: all hands
+    if (lds > 60 * 1024 &&
+        magat_ensure_dyn_lds(reinterpret_cast<const void*>(&sim_move_kernel<true>), MAGAT_LDS_SIM_MOVE_WIDE, lds) != MAGAT_OK)
+      return MAGAT_ERR_LAUNCH;
+    hipLaunchKernelGGL(sim_move_kernel<true>, dim3(B), dim3(threads), lds, st, logits, actions_in, map, map_stride, H, W, pos, goal,
+                       actions_out, reinterpret_cast<signed char*>(moves_out), reached_out, flags_out, N, policy, uniforms, bk,
+                       static_cast<unsigned*>(workspace));
+    return magat_check_launch();
+  }
   const size_t lds = (size_t)H * W * sizeof(unsigned) + (size_t)4 * N * sizeof(int);
   if (lds > 160 * 1024) return MAGAT_ERR_UNSUPPORTED;
   if (lds > 64 * 1024 &&
-      magat_ensure_dyn_lds(reinterpret_cast<const void*>(&sim_move_kernel), MAGAT_LDS_SIM_MOVE, lds) != MAGAT_OK)
+      magat_ensure_dyn_lds(reinterpret_cast<const void*>(&sim_move_kernel<false>), MAGAT_LDS_SIM_MOVE, lds) != MAGAT_OK)
     return MAGAT_ERR_LAUNCH;
-  int threads = 64;
-  while (threads < N && threads < 1024) threads *= 2;
-  hipLaunchKernelGGL(sim_move_kernel, dim3(B), dim3(threads), lds, static_cast<hipStream_t>(stream), logits, actions_in,
-                     map, map_batched ? (long long)H * W : 0LL, H, W, pos, goal, actions_out,
-                     reinterpret_cast<signed char*>(moves_out), reached_out, flags_out, N, policy, uniforms, bk);
+  hipLaunchKernelGGL(sim_move_kernel<false>, dim3(B), dim3(threads), lds, st, logits, actions_in, map, map_stride, H, W, pos, goal,
+                     actions_out, reinterpret_cast<signed char*>(moves_out), reached_out, flags_out, N, policy, uniforms, bk,
+                     static_cast<unsigned*>(nullptr));
   return magat_check_launch();
 }
-}  // namespace
 
-extern "C" int magat_sim_move(const float* logits, const int32_t* actions_in, const uint8_t* map, int map_batched, int H,
-                              int W, int32_t* pos, const int32_t* goal, int32_t* actions_out, int8_t* moves_out,
-                              uint8_t* reached_out, int32_t* flags_out, int B, int N, void* stream) {
-  return sim_move_launch(logits, actions_in, map, map_batched, H, W, pos, goal, actions_out, moves_out, reached_out,
-                         flags_out, B, N, 0, nullptr, SimBook{}, stream);
-}
-
-extern "C" int magat_sim_step(const magat_sim_step_desc* d, void* stream) {
+int sim_step_launch(const magat_sim_step_desc* d, void* stream, bool wide, void* workspace, size_t workspace_bytes) {
   if (!d) return MAGAT_ERR_NULL;
   if (!d->goal || !d->reach_goal || !d->first_move || !d->end_step) return MAGAT_ERR_NULL;
   SimBook bk{};
@@ -832,5 +849,33 @@ extern "C" int magat_sim_step(const magat_sim_step_desc* d, void* stream) {
   bk.flowtime_out = d->flowtime_out;
   bk.makespan_out = d->makespan_out;
   return sim_move_launch(d->logits, d->actions_in, d->map, d->map_batched, d->H, d->W, d->pos, d->goal, d->actions_out,
-                         d->moves_out, nullptr, d->flags_out, d->B, d->N, d->policy, d->uniforms, bk, stream);
+                         d->moves_out, nullptr, d->flags_out, d->B, d->N, d->policy, d->uniforms, bk, stream, wide, workspace,
+                         workspace_bytes);
+}
+}  // namespace
+
+extern "C" int magat_sim_move(const float* logits, const int32_t* actions_in, const uint8_t* map, int map_batched, int H,
+                              int W, int32_t* pos, const int32_t* goal, int32_t* actions_out, int8_t* moves_out,
+                              uint8_t* reached_out, int32_t* flags_out, int B, int N, void* stream) {
+  return sim_move_launch(logits, actions_in, map, map_batched, H, W, pos, goal, actions_out, moves_out, reached_out,
+                         flags_out, B, N, 0, nullptr, SimBook{}, stream);
+}
+
+extern "C" int magat_sim_step(const magat_sim_step_desc* d, void* stream) { return sim_step_launch(d, stream, false, nullptr, 0); }
+
+extern "C" size_t magat_sim_move_wide_workspace_bytes(int B, int H, int W, int N) {
+  if (B <= 0 || H <= 0 || W <= 0 || N <= 0 || H > MOVE_WIDE_SIDE || W > MOVE_WIDE_SIDE || N > MOVE_WIDE_AGENTS) return 0;
+  return (size_t)B * H * W * sizeof(unsigned);
+}
+
+extern "C" int magat_sim_move_wide(const float* logits, const int32_t* actions_in, const uint8_t* map, int map_batched, int H,
+                                   int W, int32_t* pos, const int32_t* goal, int32_t* actions_out, int8_t* moves_out,
+                                   uint8_t* reached_out, int32_t* flags_out, int B, int N, void* workspace,
+                                   size_t workspace_bytes, void* stream) {
+  return sim_move_launch(logits, actions_in, map, map_batched, H, W, pos, goal, actions_out, moves_out, reached_out,
+                         flags_out, B, N, 0, nullptr, SimBook{}, stream, true, workspace, workspace_bytes);
+}
+
+extern "C" int magat_sim_step_wide(const magat_sim_step_desc* d, void* workspace, size_t workspace_bytes, void* stream) {
+  return sim_step_launch(d, stream, true, workspace, workspace_bytes);
 }

@@ -13,35 +13,12 @@
 #include <cstdint>
 
 #include "magat_common.h"
+#include "sim_guidance_parts.h"
 
 namespace {
 
 constexpr int GUIDE_MAX_CANVAS = 64;      // rows / columns of the search canvas: a row is one 64-bit mask, coordinates take 6 bits
-constexpr int GUIDE_MAX_WT = 32;          // FOV + 2: a window row is one 32-bit mask
 constexpr size_t GUIDE_LDS_HEAD = 3 * GUIDE_MAX_CANVAS * sizeof(unsigned long long) + 3 * GUIDE_MAX_WT * sizeof(unsigned);
-
-#define GUIDE_WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
-
-template <int CTRL>
-__device__ __forceinline__ unsigned long long guide_dpp_u64(unsigned long long v) {
-  const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)v, CTRL, 0xf, 0xf, true);
-  const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(v >> 32), CTRL, 0xf, 0xf, true);
-  return (unsigned long long)lo | ((unsigned long long)hi << 32);
-}
-__device__ __forceinline__ unsigned long long guide_lane_u64(unsigned long long v, int lane) {
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, lane);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), lane);
-  return (unsigned long long)lo | ((unsigned long long)hi << 32);
-}
-__device__ __forceinline__ unsigned long long guide_min(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
-// wave-uniform minimum (all 64 lanes active): the rotations inside each row of 16 lanes, then the four rows
-__device__ __forceinline__ unsigned long long guide_wave_min(unsigned long long v) {
-  v = guide_min(v, guide_dpp_u64<0x128>(v));
-  v = guide_min(v, guide_dpp_u64<0x124>(v));
-  v = guide_min(v, guide_dpp_u64<0x122>(v));
-  v = guide_min(v, guide_dpp_u64<0x121>(v));
-  return guide_min(guide_min(guide_lane_u64(v, 0), guide_lane_u64(v, 16)), guide_min(guide_lane_u64(v, 32), guide_lane_u64(v, 48)));
-}
 
 __global__ __launch_bounds__(64) void guided_states_kernel(const uint8_t* __restrict__ map, long long map_stride, int H, int Wm,
                                                            const int* __restrict__ pos, const int* __restrict__ goal,
@@ -69,43 +46,13 @@ __global__ __launch_bounds__(64) void guided_states_kernel(const uint8_t* __rest
   const bool local = mode == MAGAT_GUIDE_LOCAL, semi = mode == MAGAT_GUIDE_SEMI;
   const bool pos_in = cx >= 0 && cx < H && cy >= 0 && cy < Wm, goal_in = gx >= 0 && gx < H && gy >= 0 && gy < Wm;
   const bool search = pos_in && goal_in;
-  // the agents of this instance that stand inside the FOV (setPosAgents + the FOV crop, :88-99)
-  for (int n = lane; n < N; n += 64) {
-    const int px = pos[((long long)b * N + n) * 2], py = pos[((long long)b * N + n) * 2 + 1];
-    const int ax = px - cx + half, ay = py - cy + half;
-    if (px >= 0 && px < H && py >= 0 && py < Wm && ax >= 0 && ax < fov && ay >= 0 && ay < fov) atomicOr(&wocc[ax], 1u << ay);
-  }
-  // the obstacles inside the FOV (outside the map = obstacle); SemiLG writes this crop into the agent's remembered map BEFORE the
-  // search (:356-357) - here, so that the grid loop below only reads that map
+  // the agents and the obstacles inside the FOV; SemiLG writes the obstacle crop into the agent's remembered map (guide_window)
   const int Hp = H + 2 * half, Wp = Wm + 2 * half;
   uint8_t* vw = (semi && search) ? view + ag * (long long)Hp * Wp : nullptr;
-  for (int idx = lane; idx < fov * fov; idx += 64) {
-    const int a = idx / fov, q = idx - a * fov;
-    const int r = cx - half + a, c = cy - half + q;
-    const bool blocked = (r >= 0 && r < H && c >= 0 && c < Wm) ? mp[(long long)r * Wm + c] != 0 : true;
-    if (blocked) atomicOr(&wmap[a], 1u << q);
-    if (vw) vw[(long long)(r + half) * Wp + (c + half)] = blocked ? 1 : 0;      // pos inside the map: the crop lies inside the padded map
-  }
+  guide_window(mp, H, Wm, pos, b, N, cx, cy, fov, wmap, wocc, vw, lane);
   GUIDE_WAVE_SYNC();
-  // the goal marker of 'Project_G' (fov_states_kernel): the goal itself inside the FOV, else projectedgoal (:101-120)
   int grow, gcol;
-  {
-    const int dx = gx - cx, dy = gy - cy;
-    if (goal_in && dx >= -half && dx <= half && dy >= -half && dy <= half) {
-      grow = dx + half + 1;
-      gcol = dy + half + 1;
-    } else {
-      const int ady = dy < 0 ? -dy : dy, adx = dx < 0 ? -dx : dx;
-      const int sx = (dx > 0) - (dx < 0), sy = (dy > 0) - (dy < 0);
-      if (ady >= adx) {
-        gcol = dist * (sy + 1);
-        grow = (int)((double)dist + rint((double)dist * (double)dx / (double)ady));
-      } else {
-        grow = dist * (sx + 1);
-        gcol = (int)((double)dist + rint((double)dist * (double)dy / (double)adx));
-      }
-    }
-  }
+  guide_goal_marker(cx, cy, gx, gy, goal_in, fov, grow, gcol);
   const int Hc = local ? Wt : H + 2 * half + 2, Wc = local ? Wt : Wm + 2 * half + 2;
   const int sx = local ? dist : cx + half + 1, sy = local ? dist : cy + half + 1;      // start and goal on the canvas
   const int tx = local ? grow : gx + half + 1, ty = local ? gcol : gy + half + 1;
@@ -126,23 +73,9 @@ __global__ __launch_bounds__(64) void guided_states_kernel(const uint8_t* __rest
       if (lane == 0) unavail[r] = m;
     }
   } else if (search) {
-    // the map padded by FOV/2 obstacle cells (GlobalG) or the agent's remembered map with the current FOV crop written into
-    // it first (SemiLG, :356-357), plus the agents inside the FOV ('_SD'; SemiLG always, :359), inside a free one-cell ring;
-    // the goal cell is cleared when it holds exactly 1 (:372-374, :464-465)
-    const uint8_t* vr = vw;
-    const bool agents = semi || dyn;
+    // the padded map or the agent's remembered map, the agents in the FOV, the free ring, the cleared goal (guide_canvas_cell)
     for (int r = 0; r < Hc; ++r) {
-      int val = 0;
-      const int c = lane;
-      if (r >= 1 && r < Hc - 1 && c >= 1 && c < Wc - 1) {
-        const int pr = r - 1, pc = c - 1, mr = pr - half, mc = pc - half;
-        const int fa = mr - cx + half, fc = mc - cy + half;
-        const bool infov = fa >= 0 && fa < fov && fc >= 0 && fc < fov;
-        if (infov) val = (int)((wmap[fa] >> fc) & 1u) + (agents ? (int)((wocc[fa] >> fc) & 1u) : 0);
-        else if (semi) val = vr[(long long)pr * Wp + pc];
-        else val = (mr >= 0 && mr < H && mc >= 0 && mc < Wm) ? (mp[(long long)mr * Wm + mc] != 0 ? 1 : 0) : 1;
-        if (r == tx && c == ty && val == 1) val = 0;
-      }
+      const int val = guide_canvas_cell(r, lane, Hc, Wc, mp, H, Wm, cx, cy, fov, wmap, wocc, semi || dyn, semi, vw, tx, ty);
       const unsigned long long m = __ballot(val != 0);
       if (lane == 0) unavail[r] = m;
     }
@@ -216,16 +149,8 @@ __global__ __launch_bounds__(64) void guided_states_kernel(const uint8_t* __rest
     }
   }
   GUIDE_WAVE_SYNC();
-  float* xa = x + ag * (long long)(3 * Wt * Wt);
-  const bool agents_out = !(local && !dyn);                 // LocalG_S writes channel 2 as zeros (:265-266)
-  for (int idx = lane; idx < 3 * Wt * Wt; idx += 64) {
-    const int ch = idx / (Wt * Wt), pix = idx - ch * Wt * Wt;
-    const int a = pix / Wt, c = pix - a * Wt;
-    unsigned bit = 0u;
-    if (ch == 1) bit = (pmask[a] >> c) & 1u;
-    else if (a >= 1 && a <= fov && c >= 1 && c <= fov) bit = ch == 0 ? (wmap[a - 1] >> (c - 1)) & 1u : (agents_out ? (wocc[a - 1] >> (c - 1)) & 1u : 0u);
-    xa[idx] = bit ? 1.f : 0.f;
-  }
+  // LocalG_S writes channel 2 as zeros (:265-266)
+  guide_write_states(x + ag * (long long)(3 * Wt * Wt), fov, wmap, wocc, pmask, !(local && !dyn), lane);
 }
 
 }  // namespace

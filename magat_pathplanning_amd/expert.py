@@ -161,13 +161,14 @@ def expert_stats(target, start, goal, valid):
 
 def expert_samples(obstacle_map, paths, lengths, goal, makespan, comm_radius, dynamic_commR=False, symmetric_norm=False, FOV=9,
                    guidance="Project_G", gso_dtype=torch.float32, T=None, check=True, max_steps=64,
-                   max_agent_steps=MAX_AGENT_STEPS, start=None):
+                   max_agent_steps=MAX_AGENT_STEPS, start=None, wide=False):
     """DataTransformer.pathtransformer_RelativeCoordinate (:237-265) for C cases: obstacle_map (H,W) or (C,H,W), the padded
     schedule (pack_schedules) -> dict(inputTensor (C,T,N,3,FOV+2,FOV+2) float32, target (C,T,N,5), GSO (C,T,N,N) gso_dtype,
     pos (C,T,N,2), valid (C,T), radii (C,) float64, grow_steps (C,) int32, makespan (C,), bad (C,)).  Steps at or behind a case's
     makespan + 1 are zero in every tensor and not valid.
 
-    States are batched_fov_states of config.guidance, GSOs batched_gso with comm_radius
+    States are batched_fov_states of config.guidance (wide=True: its keyword, 'GlobalG_*' / 'SemiLG_*' on maps up to
+    256 x 256 - without it they stop at 54 x 54 at FOV 9), GSOs batched_gso with comm_radius
     (computeAdjacencyMatrix_fixedCommRadius) or, with dynamic_commR, the per-case radii of expert_radius; an instance still
     disconnected after max_steps growth steps raises MagatNativeError (BatchedEpisode.gso's rule).  check=True (default) raises
     ValueError for an illegal move.  Only the valid (case, step) pairs reach those kernels: they are compacted first, so cases
@@ -234,10 +235,10 @@ def expert_samples(obstacle_map, paths, lengths, goal, makespan, comm_radius, dy
             view = new_agent_view(c1 - c0, N, H, W, FOV, dev)
             for t, k in enumerate(live_cases):
                 mk = ms if ms.dim() == 2 else ms[:k]
-                x[order[:k], t] = batched_fov_states(mk, ps[:k, t], gs[:k], FOV, guidance, view[:k])
+                x[order[:k], t] = batched_fov_states(mk, ps[:k, t], gs[:k], FOV, guidance, view[:k], wide)
         else:
             mm = m if m.dim() == 2 else m.index_select(0, case)
-            xf.index_copy_(0, idx, batched_fov_states(mm, p, goal.index_select(0, case), FOV, guidance))
+            xf.index_copy_(0, idx, batched_fov_states(mm, p, goal.index_select(0, case), FOV, guidance, None, wide))
         r = radii.index_select(0, case) if dynamic_commR else float(comm_radius)
         Sf.index_copy_(0, idx, batched_gso(p, r, symmetric_norm=symmetric_norm, dtype=gso_dtype))
     return dict(inputTensor=x, target=target, GSO=S, pos=pos, valid=valid, radii=radii, grow_steps=grow,

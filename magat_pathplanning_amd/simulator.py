@@ -91,7 +91,45 @@ def new_agent_view(B, N, H, W, FOV=9, device="cuda"):
     return torch.zeros(B, N, H + 2 * half, W + 2 * half, dtype=torch.uint8, device=device)
 
 
-def batched_fov_states(obstacle_map, pos, goal, FOV=9, guidance="Project_G", agent_view=None):
+GUIDE_CANVAS = 64               # csrc/sim_guidance.hip: the narrow form's search canvas, H + 2 (FOV // 2) + 2 rows at most
+MOVE_LDS_BYTES = 160 * 1024     # csrc/sim_frontend.hip: the narrow move step keeps 4 H W + 16 N bytes in LDS
+
+
+class _Workspace:
+    """A cached device buffer for the wide kernels: reallocated only when a call needs more than it holds."""
+
+    def __init__(self):
+        self.buf = None
+
+    def get(self, nbytes, device):
+        if self.buf is None or self.buf.device != device or self.buf.numel() < nbytes:
+            self.buf = torch.empty(max(int(nbytes), 8), dtype=torch.uint8, device=device)
+        return self.buf
+
+
+_guide_workspaces = {}          # device -> _Workspace, for batched_fov_states calls that bring none
+
+
+def guided_needs_wide(H, W, FOV):
+    """True where GlobalG_* / SemiLG_* on an H x W map is beyond the narrow kernel's 64 x 64 canvas."""
+    return max(H, W) + 2 * (int(FOV) // 2) + 2 > GUIDE_CANVAS
+
+
+def guided_wide_geometry(B, N, H, W, FOV=9):
+    """(workgroups, agents the busiest workgroup walks) of magat_sim_guided_states_wide, from the library's own workspace
+    size: one slab of canvas rows * canvas columns * 8 bytes per workgroup."""
+    half = int(FOV) // 2
+    slab = (H + 2 * half + 2) * (W + 2 * half + 2) * 8
+    groups = int(nat.lib().magat_sim_guided_states_wide_workspace_bytes(B, N, H, W, int(FOV))) // slab
+    return groups, (-(-(B * N) // groups) if groups else 0)
+
+
+def move_needs_wide(H, W, N):
+    """True where the narrow move step's LDS limit refuses the shape."""
+    return 4 * H * W + 16 * N > MOVE_LDS_BYTES
+
+
+def batched_fov_states(obstacle_map, pos, goal, FOV=9, guidance="Project_G", agent_view=None, wide=False, workspace=None):
     """obstacle_map (H,W) or (B,H,W) uint8/bool device tensor (non-zero = obstacle), pos / goal (B,N,2) integer
     (row, col) -> x (B,N,3,FOV+2,FOV+2) float32, identical to stacking AgentState.toInputTensor over the instances.
 
@@ -100,9 +138,13 @@ def batched_fov_states(obstacle_map, pos, goal, FOV=9, guidance="Project_G", age
     launch): 'LocalG_S' / 'LocalG_SD' search the agent's own window, 'GlobalG_S' / 'GlobalG_SD' the whole padded map,
     'SemiLG_S' / 'SemiLG_SD' the map the agent has seen so far - `agent_view` (new_agent_view(...)), a caller-owned uint8
     tensor (B, N, H + 2 (FOV // 2), W + 2 (FOV // 2)) that the call updates IN PLACE.  '_SD' counts the agents inside the FOV
-    as obstacles.  GlobalG / SemiLG take maps up to 54 x 54 at FOV 9 (a 64 x 64 search canvas; larger maps raise
-    MagatNativeError, nothing is launched).  The whole path is drawn: the reference itself raises IndexError once a path is longer
-    than its max_localPath (4 (FOV + 2) cells for LocalG, rows + columns of the padded map otherwise)."""
+    as obstacles.  Without `wide`, GlobalG / SemiLG take maps up to 54 x 54 at FOV 9 (a 64 x 64 search canvas; larger maps
+    raise MagatNativeError, nothing is launched).  wide=True lifts that to 256 x 256: a map the narrow kernel takes still goes
+    to it, with the same bits; a larger one goes to magat_sim_guided_states_wide (csrc/sim_guidance_wide.hip, the same search
+    with its open list in a device workspace - cached per device and grown only when it must, or `workspace`, a _Workspace the
+    caller owns).  'Project_G' and 'LocalG_*' do not depend on the keyword.  The whole path is drawn: the reference itself
+    raises IndexError once a path is longer than its max_localPath (4 (FOV + 2) cells for LocalG, rows + columns of the padded
+    map otherwise)."""
     if guidance not in GUIDANCE_MODES:
         raise ValueError("guidance must be one of %s, got %r" % (sorted(GUIDANCE_MODES), guidance))
     pos, goal = _dev_i32(pos, "pos"), _dev_i32(goal, "goal")
@@ -129,6 +171,16 @@ def batched_fov_states(obstacle_map, pos, goal, FOV=9, guidance="Project_G", age
             nat.check(nat.lib().magat_sim_fov_states(nat.ptr(m), 1 if batched else 0, H, W, nat.ptr(pos), nat.ptr(goal),
                                                      nat.ptr(x), FOV, B, N, nat.current_stream(pos.device)),
                       "magat_sim_fov_states")
+        elif wide and guided[0] != nat.GUIDE_LOCAL and guided_needs_wide(H, W, FOV):
+            lib = nat.lib()
+            if workspace is None:
+                workspace = _guide_workspaces.setdefault(pos.device, _Workspace())
+            ws = workspace.get(lib.magat_sim_guided_states_wide_workspace_bytes(B, N, H, W, FOV), pos.device)
+            nat.check(lib.magat_sim_guided_states_wide(nat.ptr(m), 1 if batched else 0, H, W, nat.ptr(pos), nat.ptr(goal),
+                                                       nat.ptr(x), FOV, B, N, guided[0], guided[1],
+                                                       nat.ptr(agent_view) if guided[0] == nat.GUIDE_SEMI else None,
+                                                       nat.ptr(ws), ws.numel(), nat.current_stream(pos.device)),
+                      "magat_sim_guided_states_wide")
         else:
             nat.check(nat.lib().magat_sim_guided_states(nat.ptr(m), 1 if batched else 0, H, W, nat.ptr(pos), nat.ptr(goal),
                                                         nat.ptr(x), FOV, B, N, guided[0], guided[1],
@@ -137,11 +189,14 @@ def batched_fov_states(obstacle_map, pos, goal, FOV=9, guidance="Project_G", age
     return x
 
 
-def batched_move(obstacle_map, pos, logits=None, actions=None, goal=None):
+def batched_move(obstacle_map, pos, logits=None, actions=None, goal=None, wide=False, workspace=None):
     """One closed-loop step for B instances on the device (multiRobotSimNew.move, utils/new_simulator.py:471-520):
     decode the action keys from the model's logits (B*N,5) (or take `actions` (B,N)), shield the proposed moves exactly
     like check_collision (:334-454; lowest index instead of random.choice among moving claimants) and advance `pos`
-    IN PLACE.  Returns dict(actions (B,N) int32, moves (B,N,2) int8, reached (B,N) bool or None, flags (B,) int32)."""
+    IN PLACE.  Returns dict(actions (B,N) int32, moves (B,N,2) int8, reached (B,N) bool or None, flags (B,) int32).
+    The cell grid lives in LDS, 4 H W + 16 N bytes <= 160 KB (about 200 x 200); wide=True takes maps up to 256 x 256 with up to
+    4096 agents: a shape inside the LDS limit keeps its kernel, a larger one goes to magat_sim_move_wide, the same rules with the
+    grid in a device workspace of 4 B H W bytes (`workspace`, a _Workspace the caller keeps, or a fresh buffer)."""
     if pos.dtype != torch.int32 or not pos.is_cuda or not pos.is_contiguous():
         raise nat.MagatNativeError("pos must be a contiguous int32 device tensor (it is updated in place)")
     assert (logits is None) != (actions is None), "give logits or actions"
@@ -160,9 +215,16 @@ def batched_move(obstacle_map, pos, logits=None, actions=None, goal=None):
     reached = torch.empty(B, N, dtype=torch.uint8, device=dev) if gl is not None else None
     flags = torch.empty(B, dtype=torch.int32, device=dev)
     with torch.cuda.device(dev):
-        nat.check(nat.lib().magat_sim_move(nat.ptr(lg), nat.ptr(ac), nat.ptr(m), 1 if batched else 0, H, W, nat.ptr(pos),
-                                           nat.ptr(gl), nat.ptr(a_out), nat.ptr(mv), nat.ptr(reached), nat.ptr(flags), B, N,
-                                           nat.current_stream(dev)), "magat_sim_move")
+        if wide and move_needs_wide(H, W, N):
+            lib = nat.lib()
+            ws = (workspace or _Workspace()).get(lib.magat_sim_move_wide_workspace_bytes(B, H, W, N), dev)
+            nat.check(lib.magat_sim_move_wide(nat.ptr(lg), nat.ptr(ac), nat.ptr(m), 1 if batched else 0, H, W, nat.ptr(pos),
+                                              nat.ptr(gl), nat.ptr(a_out), nat.ptr(mv), nat.ptr(reached), nat.ptr(flags), B, N,
+                                              nat.ptr(ws), ws.numel(), nat.current_stream(dev)), "magat_sim_move_wide")
+        else:
+            nat.check(nat.lib().magat_sim_move(nat.ptr(lg), nat.ptr(ac), nat.ptr(m), 1 if batched else 0, H, W, nat.ptr(pos),
+                                               nat.ptr(gl), nat.ptr(a_out), nat.ptr(mv), nat.ptr(reached), nat.ptr(flags), B, N,
+                                               nat.current_stream(dev)), "magat_sim_move")
     return dict(actions=a_out, moves=mv, reached=None if reached is None else reached.bool(), flags=flags)
 
 
@@ -176,10 +238,14 @@ class BatchedEpisode:
 
     action_select: 'soft_max' | 'sum_multinorm' | 'exp_multinorm' (config.action_select; the reference's default outside
     'test_trainingSet' mode is exp_multinorm, :134-145).  The multinomial policies draw from `generator` (a device
-    torch.Generator; seeded runs repeat exactly) - one float64 uniform per agent and step, inverse CDF on the device."""
+    torch.Generator; seeded runs repeat exactly) - one float64 uniform per agent and step, inverse CDF on the device.
+
+    wide=True: maps up to 256 x 256 (batched_fov_states' and batched_move's keyword).  states() with 'GlobalG_*' / 'SemiLG_*'
+    and step() take the wide kernels where the narrow limits are exceeded, each with a workspace the episode owns; `moves`
+    (B,N,2) int8 holds the last step's shielded moves."""
 
     def __init__(self, obstacle_map, pos, goal, maxstep, comm_radius, action_select="soft_max", symmetric_norm=False,
-                 FOV=9, generator=None, guidance="Project_G"):
+                 FOV=9, generator=None, guidance="Project_G", wide=False):
         if action_select not in POLICIES:
             raise ValueError("action_select must be one of %s" % sorted(POLICIES))
         if guidance not in GUIDANCE_MODES:
@@ -197,6 +263,8 @@ class BatchedEpisode:
         self.comm_radius, self.symmetric_norm, self.FOV = float(comm_radius), bool(symmetric_norm), int(FOV)
         self.generator = generator
         self.guidance = guidance
+        self.wide = bool(wide)
+        self._guide_ws, self._move_ws = _Workspace(), _Workspace()
         # 'SemiLG_*': what every agent has seen so far, empty at the start of the episode (AgentState.setmap, once per episode in
         # multiRobotSimNew.setup) and owned by the episode
         self.agent_view = None
@@ -210,6 +278,7 @@ class BatchedEpisode:
         self.done = torch.zeros(B, dtype=torch.int32, device=dev)
         self.flags = torch.zeros(B, dtype=torch.int32, device=dev)
         self.actions = torch.empty(B, N, dtype=torch.int32, device=dev)
+        self.moves = torch.zeros(B, N, 2, dtype=torch.int8, device=dev)
         # makespanPredict / flowtimePredict start at maxstep and maxstep * N (:220-221)
         self.makespan = torch.full((B,), self.maxstep, dtype=torch.int32, device=dev)
         self.flowtime = torch.full((B,), self.maxstep * N, dtype=torch.int32, device=dev)
@@ -227,7 +296,8 @@ class BatchedEpisode:
         return batched_gso(self.pos, self.radii, symmetric_norm=self.symmetric_norm, dtype=dtype)
 
     def states(self):
-        return batched_fov_states(self.map, self.pos, self.goal, self.FOV, self.guidance, self.agent_view)
+        return batched_fov_states(self.map, self.pos, self.goal, self.FOV, self.guidance, self.agent_view, self.wide,
+                                  self._guide_ws)
 
     def step(self, logits=None, actions=None, uniforms=None):
         """move(actionVec, currentstep) for every instance; returns `done` (B,) int32 = allReachGoal as the reference
@@ -251,10 +321,16 @@ class BatchedEpisode:
         d.pos, d.goal = nat.ptr(self.pos), nat.ptr(self.goal)
         d.reach_goal, d.first_move, d.end_step = nat.ptr(self.reach_goal), nat.ptr(self.first_move), nat.ptr(self.end_step)
         d.currentstep, d.maxstep = self.currentstep, self.maxstep
-        d.actions_out, d.moves_out, d.flags_out = nat.ptr(self.actions), None, nat.ptr(self.flags)
+        d.actions_out, d.moves_out, d.flags_out = nat.ptr(self.actions), nat.ptr(self.moves), nat.ptr(self.flags)
         d.done_out, d.flowtime_out, d.makespan_out = nat.ptr(self.done), nat.ptr(self.flowtime), nat.ptr(self.makespan)
         import ctypes
         with torch.cuda.device(dev):
-            nat.check(nat.lib().magat_sim_step(ctypes.byref(d), nat.current_stream(dev)), "magat_sim_step")
+            if self.wide and move_needs_wide(d.H, d.W, N):
+                lib = nat.lib()
+                ws = self._move_ws.get(lib.magat_sim_move_wide_workspace_bytes(B, d.H, d.W, N), dev)
+                nat.check(lib.magat_sim_step_wide(ctypes.byref(d), nat.ptr(ws), ws.numel(), nat.current_stream(dev)),
+                          "magat_sim_step_wide")
+            else:
+                nat.check(nat.lib().magat_sim_step(ctypes.byref(d), nat.current_stream(dev)), "magat_sim_step")
         self.currentstep += 1
         return self.done
