@@ -834,6 +834,39 @@ int magat_sim_cases_generate_wide(int kind, const uint8_t* map_in /* NULL unless
                                   int32_t* free_cells, uint8_t* valid, int C, int N, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Improving the solver's schedules by neighbourhood re-planning (sim_mapf_lns.hip; added behind ABI 9, nothing above changes):
+ * MAPF-LNS with prioritized planning as its only building block, for C cases in one launch, one wavefront per case, no host
+ * round trip per iteration.  It is still NOT ECBS and bounds nothing: the flowtime of a case never rises from one iteration to
+ * the next, and a valid schedule stays valid.  Integer arithmetic only, no random numbers.  Device pointers, stream ordered,
+ * no allocation, no synchronisation; one kernel, one count in form "sim_mapf_lns", one span of its own profiling tag.
+ *
+ * paths (C,N,T,2), lengths (C,N), makespan (C,) int32: a result of magat_sim_mapf_plan, improved IN PLACE; solved (C,) uint8
+ * is read.  An agent's cell at t is paths[a][min(t, lengths[a] - 1)], its start the cell at 0, its goal the cell at
+ * lengths[a] - 1.  Per case: all N paths are reserved as the solver reserves them, and d0[a], the length of a's path on empty
+ * boards (the solver's search and backtrace), is computed once.  Iteration i = 0 .. iterations - 1: delay = lengths - d0; the
+ * seed is the (i mod N)-th agent by (-delay, index); the neighbourhood is the seed, then - walking the seed's free path at
+ * t = 0 .. d0 - 1 and the agents b in index order at each t - every b not yet in it whose cell at t is the free path's cell at
+ * t, or which swaps with it (t >= 1: b's cell at t is the free path's at t - 1 and b's at t - 1 the free path's at t), while it
+ * holds fewer than k; then seed + 1, seed + 2, ... (mod N) until it holds min(k, N).  Its paths are un-reserved, its agents
+ * planned again in list order, each against everything reserved at that moment; the new paths replace the old ones iff every
+ * agent arrived and the sum of the new lengths is STRICTLY below the old sum - else the reservations are put back.
+ * makespan = max lengths - 1; flowtime_before / flowtime_after (C,) int32 = sum(lengths - 1) going in and coming out;
+ * accepted (C,) int32: the iterations that were kept; status (C,) int32: 0 improved or unchanged; 1 skipped, solved == 0;
+ * 2 refused - a length outside 1..T, one of the T cells of a row off the map or on an obstacle, or a step between two of them
+ * that is none of the five moves.  A skipped or refused case keeps paths, lengths and makespan as they came, with both
+ * flowtimes and accepted 0.  Conflicts BETWEEN the agents of an input are not looked for: the result is then unspecified, but
+ * every access stays in bounds.  An agent that no accepted iteration re-planned keeps its row bit for bit.
+ * workspace: magat_sim_mapf_improve_workspace_bytes(C, N, T) = C * (T * 5 * 64 * 8 + 8 * ceil(N / 2)) bytes (the boards, then
+ * d0), 8-byte aligned, zeroed by the call itself.  Limits: H, W <= 64, 1 <= T <= 256, 1 <= k <= 8, 0 <= iterations <= 4096, a
+ * workspace of that size - otherwise MAGAT_ERR_UNSUPPORTED and nothing is launched; NULL pointers and non-positive sizes are
+ * answered first, as in magat_sim_mapf_plan. */
+size_t magat_sim_mapf_improve_workspace_bytes(int C, int N, int T);
+int magat_sim_mapf_improve(const uint8_t* map, int map_batched, int H, int W, const uint8_t* solved,
+                           int32_t* paths /* [C][N][T][2], in place */, int32_t* lengths, int32_t* makespan,
+                           int32_t* flowtime_before, int32_t* flowtime_after, int32_t* accepted, int32_t* status,
+                           void* workspace, size_t workspace_bytes, int C, int N, int T, int iterations, int k, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Planning cases made on the device (sim_cases.hip; added behind ABI 9, nothing above changes): the first step of the expert
  * pipeline, the reference's offlineExpert/CasesGenerator.py - an obstacle map, its largest free component, a start and a goal
  * per agent - for C cases in one launch; its outputs are what magat_sim_mapf_plan takes.  Device pointers, stream ordered, no

@@ -14,6 +14,14 @@ The online expert - re-solving the cases a running episode is failing at, from w
     ... ep.step(logits) ...
     res = solve_cases(ep.map, ep.pos, ep.goal)                            # schedules that start at the current positions
 
+Prioritized planning in index order never revisits a choice: agents early in the order get shortest paths, the late ones what
+is left.  improve_schedules (csrc/sim_mapf_lns.hip) repairs some of that by neighbourhood re-planning (MAPF-LNS): per
+iteration it takes the most delayed agents' turn, pulls the agents standing in its free path out of the reservation table
+with it, plans them again in that order and keeps the result only when their summed length drops.  solve_cases(...,
+improve=I) runs it on the final batch.  This is STILL not ECBS and bounds nothing - the flowtime never rises, that is all.
+
+    better = improve_schedules(obstacle_map, res, iterations=32, neighbourhood=4)      # the same keys, + flowtime_before / _after
+
 HIP only: CPU tensors raise MagatNativeError.  plan_prioritized is stream ordered and never waits for the device;
 solve_cases reads `solved` back once per round."""
 import torch
@@ -88,7 +96,51 @@ def promote(order, agent):
     return torch.gather(order, 1, rest)
 
 
-def solve_cases(obstacle_map, start, goal, horizon=None, retries=8, wide=False):
+def improve_schedules(obstacle_map, res, iterations=32, neighbourhood=4):
+    """One call of magat_sim_mapf_improve on a plan_prioritized / solve_cases result `res` (obstacle_map: the map it was planned
+    on, (H,W) or (C,H,W)): `iterations` rounds of neighbourhood re-planning per case with neighbourhoods of up to
+    `neighbourhood` (1..8) agents - the rule is in include/magat_hip.h and DESIGN 4.11; deterministic, no random numbers.
+    Returns a NEW dict with every key of `res` - paths, lengths and makespan are new tensors, the others are shared - plus
+    flowtime_before, flowtime_after (C,) int32 = sum(lengths - 1), accepted (C,) int32 and status (C,) int32: 0 improved or
+    unchanged; 1 skipped, the case is unsolved; 2 refused - a length outside 1..horizon, a cell off the map or on an obstacle,
+    a step that is none of the five moves.  Skipped and refused cases come back as they were.  The tensors of `res` are not
+    modified; a `T` key (solve_cases) is left out of the copy, since it would need a synchronisation - solved_pack computes it.
+    Not ECBS: no bound on the flowtime; it never rises, and a valid schedule stays valid.  Conflicts between the agents of
+    `res` are not looked for - the result is then unspecified.
+    Maps above 64 x 64 and horizons above 256 (results of wide=True at such shapes) raise MagatNativeError.
+    Stream ordered, no host synchronisation."""
+    paths = res["paths"]
+    if not isinstance(obstacle_map, torch.Tensor) or not obstacle_map.is_cuda or not paths.is_cuda:
+        raise nat.MagatNativeError("obstacle_map and the schedules must be device tensors (no CPU fallback)")
+    m = obstacle_map.to(torch.uint8).contiguous()
+    assert paths.dim() == 4 and paths.shape[3] == 2, "paths must be (C,N,T,2)"
+    C, N, T, _ = paths.shape
+    assert m.dim() in (2, 3) and (m.dim() == 2 or m.shape[0] == C), "obstacle_map must be (H,W) or (C,H,W)"
+    H, W = m.shape[-2], m.shape[-1]
+    if H > MAX_SIDE or W > MAX_SIDE or T > MAX_HORIZON:
+        raise nat.MagatNativeError("improve_schedules takes maps up to %d x %d and horizons up to %d, not %d x %d / %d "
+                                   "(there is no wide form of it)" % (MAX_SIDE, MAX_SIDE, MAX_HORIZON, H, W, T))
+    dev = paths.device
+    out = {key: value for key, value in res.items() if key != "T"}
+    out["paths"] = _dev_i32(paths, "paths").clone()
+    out["lengths"] = _dev_i32(res["lengths"], "lengths").clone()
+    out["makespan"] = _dev_i32(res["makespan"], "makespan").clone()
+    solved = res["solved"].to(torch.uint8).contiguous()
+    assert tuple(out["lengths"].shape) == (C, N) and out["makespan"].numel() == C and solved.numel() == C
+    extra = torch.empty(4, C, dtype=torch.int32, device=dev)
+    lib = nat.lib()
+    ws = torch.empty(max(int(lib.magat_sim_mapf_improve_workspace_bytes(C, N, T)), 8), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        nat.check(lib.magat_sim_mapf_improve(nat.ptr(m), 1 if m.dim() == 3 else 0, H, W, nat.ptr(solved), nat.ptr(out["paths"]),
+                                             nat.ptr(out["lengths"]), nat.ptr(out["makespan"]), nat.ptr(extra[0]),
+                                             nat.ptr(extra[1]), nat.ptr(extra[2]), nat.ptr(extra[3]), nat.ptr(ws), ws.numel(),
+                                             C, N, T, int(iterations), int(neighbourhood), nat.current_stream(dev)),
+                  "magat_sim_mapf_improve")
+    out.update(flowtime_before=extra[0], flowtime_after=extra[1], accepted=extra[2], status=extra[3])
+    return out
+
+
+def solve_cases(obstacle_map, start, goal, horizon=None, retries=8, wide=False, improve=0):
     """plan_prioritized in index order, then up to `retries` re-plans of the cases still unsolved, each with that case's
     failed_agent moved to the front of its order.  Returns plan_prioritized's dict (every case holds its LAST plan) plus order
     (C,N) int32 (the order of that plan), rounds (C,) int32 (the plans made for the case, 1 = solved at once) and T =
@@ -100,6 +152,9 @@ def solve_cases(obstacle_map, start, goal, horizon=None, retries=8, wide=False):
     the keys that expert_samples takes as **pack.
 
     wide: as in plan_prioritized, for the first plan and every re-plan.
+    improve=I > 0: improve_schedules(obstacle_map, res, iterations=I) on the final batch (its limits apply) - the returned dict
+    then also holds flowtime_before, flowtime_after, accepted and status, and T is taken from the improved makespans.  The
+    default 0 leaves the result and the calls made as they were.
     One host synchronisation per round (the read of `solved`), one more for T."""
     res = plan_prioritized(obstacle_map, start, goal, None, horizon, wide)
     C, N, _ = res["start"].shape
@@ -119,6 +174,8 @@ def solve_cases(obstacle_map, start, goal, horizon=None, retries=8, wide=False):
             res[key].index_copy_(0, idx, sub[key])
         order.index_copy_(0, idx, again)
         rounds.index_add_(0, idx, torch.ones_like(idx, dtype=torch.int32))
+    if int(improve) > 0:
+        res = improve_schedules(obstacle_map, res, iterations=int(improve))
     done = res["makespan"][res["solved"] != 0]
     res.update(order=order, rounds=rounds, T=int(done.max().item()) + 1 if done.numel() else 1)
     return res

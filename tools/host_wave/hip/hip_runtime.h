@@ -1,0 +1,131 @@
+// A stand-in for <hip/hip_runtime.h> that lets ONE wavefront-per-workgroup kernel of csrc/ compile for the host and run as 64
+// threads (tools/host_wave/mapf_lns_check.cpp): lane = thread, every cross-lane operation (ballot, DPP wave shift, readfirstlane,
+// shuffle) and __syncthreads is a rendezvous of all 64 threads, so the kernel must keep them in wave-uniform control flow - as
+// the hardware wants it too.  Between two rendezvous the lanes run in any order: a missing barrier between a store of one
+// lane and a load of another, which lock step would hide, is a data race here (run under a thread sanitizer to see it).
+// Workgroups run one after another; __shared__ variables are statics.  Only what the row-board kernels use is provided.
+#pragma once
+#include <math.h>
+#include <pthread.h>
+#include <stdint.h>
+#include <stdlib.h>
+#include <string.h>
+
+#define __device__
+#define __host__
+#define __global__
+#define __forceinline__ inline __attribute__((always_inline))
+#define __shared__ static
+#define __launch_bounds__(n)
+#define __align__(n) __attribute__((aligned(n)))
+#define HIP_DYNAMIC_SHARED(type, var) type* var = reinterpret_cast<type*>(host_wave::dyn_lds);
+
+struct dim3 {
+  unsigned x, y, z;
+  dim3(unsigned x_ = 1, unsigned y_ = 1, unsigned z_ = 1) : x(x_), y(y_), z(z_) {}
+};
+typedef void* hipStream_t;
+typedef int hipError_t;
+constexpr hipError_t hipSuccess = 0;
+inline hipError_t hipGetLastError() { return hipSuccess; }
+
+namespace host_wave {
+constexpr int kLanes = 64;
+inline thread_local int lane = 0;
+inline unsigned block = 0, blocks = 1;
+inline pthread_barrier_t barrier;
+inline unsigned long long slot[kLanes];
+inline void meet() { pthread_barrier_wait(&barrier); }
+// every lane posts a value; fn(slots) is evaluated by every lane between the two rendezvous
+template <typename F>
+inline auto exchange(unsigned long long mine, F fn) {
+  slot[lane] = mine;
+  meet();
+  auto r = fn(slot);
+  meet();
+  return r;
+}
+inline unsigned long long ballot(bool p) {
+  return exchange(p ? 1ull : 0ull, [](const unsigned long long* s) {
+    unsigned long long m = 0;
+    for (int i = 0; i < kLanes; ++i) m |= s[i] << i;
+    return m;
+  });
+}
+inline int update_dpp(int old, int src, int ctrl, int row_mask, int bank_mask, bool bound_ctrl) {
+  if (row_mask != 0xf || bank_mask != 0xf || !bound_ctrl || (ctrl != 0x130 && ctrl != 0x138)) abort();      // wave_shl:1, wave_shr:1 only
+  (void)old;
+  const int from = ctrl == 0x130 ? lane + 1 : lane - 1;
+  return exchange((unsigned)src, [from](const unsigned long long* s) { return from >= 0 && from < kLanes ? (int)(unsigned)s[from] : 0; });
+}
+inline int readlane(int v, int l) {
+  return exchange((unsigned)v, [l](const unsigned long long* s) { return (int)(unsigned)s[l]; });
+}
+inline int shfl_xor(int v, int mask) {
+  const int from = lane ^ mask;
+  return exchange((unsigned)v, [from](const unsigned long long* s) { return (int)(unsigned)s[from]; });
+}
+struct Idx {
+  struct X {
+    operator unsigned() const { return (unsigned)lane; }
+  } x;
+};
+struct BlockIdx {
+  struct X {
+    operator unsigned() const { return block; }
+  } x;
+  unsigned y = 0, z = 0;
+};
+inline unsigned long long dyn_lds[256 * 64];      // the dynamic LDS of a workgroup: 128 KB
+struct GridDim {
+  unsigned x = 1, y = 1, z = 1;
+};
+// runs kernel(args...) for every workgroup of the grid, 64 threads each
+template <typename K, typename... A>
+inline void launch(K kernel, dim3 grid, A... args) {
+  blocks = grid.x;
+  for (block = 0; block < grid.x; ++block) {
+    pthread_barrier_init(&barrier, nullptr, kLanes);
+    auto body = [&](int l) {
+      lane = l;
+      kernel(args...);
+    };
+    pthread_t th[kLanes];
+    struct Arg {
+      decltype(body)* b;
+      int l;
+    } arg[kLanes];
+    for (int l = 0; l < kLanes; ++l) {
+      arg[l] = {&body, l};
+      pthread_create(&th[l], nullptr, [](void* p) -> void* {
+        Arg* a = static_cast<Arg*>(p);
+        (*a->b)(a->l);
+        return nullptr;
+      }, &arg[l]);
+    }
+    for (int l = 0; l < kLanes; ++l) pthread_join(th[l], nullptr);
+    pthread_barrier_destroy(&barrier);
+  }
+}
+}  // namespace host_wave
+
+static host_wave::Idx threadIdx;
+static host_wave::BlockIdx blockIdx;
+static host_wave::GridDim gridDim;
+
+#define __syncthreads() host_wave::meet()
+#define __builtin_amdgcn_ballot_w64(p) host_wave::ballot(p)
+#define __builtin_amdgcn_update_dpp(o, s, c, r, b, bc) host_wave::update_dpp(o, s, c, r, b, bc)
+#define __builtin_amdgcn_readfirstlane(v) host_wave::readlane(v, 0)
+#define __builtin_amdgcn_readlane(v, l) host_wave::readlane(v, l)
+#define __shfl_xor(v, m, w) host_wave::shfl_xor(v, m)
+#define __popcll(v) __builtin_popcountll(v)
+#define __clzll(v) __builtin_clzll(v)
+inline unsigned long long __brevll(unsigned long long v) {
+  unsigned long long r = 0;
+  for (int i = 0; i < 64; ++i) r |= ((v >> i) & 1ull) << (63 - i);
+  return r;
+}
+#define __HIP_MEMORY_SCOPE_AGENT 0
+#define __hip_atomic_fetch_add(p, v, order, scope) __atomic_fetch_add(p, v, order)
+#define hipLaunchKernelGGL(kernel, grid, block, lds, stream, ...) host_wave::launch(kernel, grid, __VA_ARGS__)

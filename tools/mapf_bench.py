@@ -9,6 +9,11 @@ the median of 5, and the line says so in "calls"), the share of cases solved at 
 solve_cases' retries, and - with --restatement K - the CPU seconds that tests/mapf_restatement.py (a per-cell Python
 restatement, NOT ECBS; the only comparison there is) needs for the first K cases of each shape.  One JSON line per shape.
 
+The two 64 x 64-form shapes get a second line each, "<shape>_improve": improve_schedules (csrc/sim_mapf_lns.hip; iterations = 32,
+neighbourhood = 4) on solve_cases' result, timed the same way, with the total flowtime of the solved cases going in and coming
+out and the free-space lower bound sum(d0 - 1) - every agent planned alone on the empty map, one more plan_prioritized call
+with C N one-agent cases.  None of these figures is a gate.
+
     python tools/mapf_bench.py [--restatement K] [--no-device]"""
 import argparse
 import json
@@ -29,14 +34,58 @@ SHAPES = (dict(name="20x20_n10", C=512, size=20, N=10, T=64, density=0.1, seed=1
           dict(name="wide_200x200_n1000", C=8, size=200, N=1000, T=1024, density=0.1, seed=104, wide=True))
 
 
+IMPROVE = dict(iterations=32, neighbourhood=4)
+
+
+def timed(fn, warmup, calls):
+    """Device events around fn(): sorted milliseconds of `calls` calls after `warmup` warm-ups, and the last result."""
+    import torch
+    for _ in range(warmup):
+        res = fn()
+    torch.cuda.synchronize()
+    ms = []
+    for _ in range(calls):
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        res = fn()
+        e1.record()
+        e1.synchronize()
+        ms.append(e0.elapsed_time(e1))
+    return sorted(ms), res
+
+
+def improve_row(sh, d, full, args):
+    import torch
+    from magat_pathplanning_amd import improve_schedules, plan_prioritized
+    t0 = time.perf_counter()
+    improve_schedules(d[0], full, **IMPROVE)
+    torch.cuda.synchronize()
+    slow = time.perf_counter() - t0 > 1.0
+    warmup, calls = (1, min(args.calls, 5)) if slow else (args.warmup, args.calls)
+    ms, better = timed(lambda: improve_schedules(d[0], full, **IMPROVE), warmup, calls)
+    ok = better["status"] == 0
+    alone = plan_prioritized(d[0], d[1].reshape(-1, 1, 2), d[2].reshape(-1, 1, 2), horizon=sh["T"])      # every agent on the empty map
+    d0 = alone["lengths"].reshape(sh["C"], sh["N"])
+    assert bool(alone["solved"].all())
+    return dict(shape=sh["name"] + "_improve", cases=sh["C"], agents=sh["N"], T=sh["T"], warmup=warmup, calls=calls, **IMPROVE,
+                improve_ms_median=ms[len(ms) // 2], improve_ms_min=ms[0], improve_ms_max=ms[-1],
+                cases_improved_or_unchanged=int(ok.sum()), cases_with_an_accepted_iteration=int((better["accepted"] > 0).sum()),
+                accepted_iterations=int(better["accepted"].sum()), flowtime_before=int(better["flowtime_before"][ok].sum()),
+                flowtime_after=int(better["flowtime_after"][ok].sum()), flowtime_lower_bound=int((d0[ok] - 1).sum()),
+                makespan_max_before=int(full["makespan"][ok].max()), makespan_max_after=int(better["makespan"][ok].max()))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--restatement", type=int, default=0, help="time the Python restatement on this many cases per shape")
     ap.add_argument("--no-device", action="store_true")
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--calls", type=int, default=50)
+    ap.add_argument("--shapes", default="", help="comma-separated shape names (default: all)")
     args = ap.parse_args()
     for sh in SHAPES:
+        if args.shapes and sh["name"] not in args.shapes.split(","):
+            continue
         m, start, goal = mr.random_batch(sh["seed"], sh["C"], sh["size"], sh["size"], sh["N"], sh["density"])
         out = dict(shape=sh["name"], cases=sh["C"], agents=sh["N"], T=sh["T"])
         if not args.no_device:
@@ -51,18 +100,7 @@ def main():
             slow = time.perf_counter() - t0 > 1.0      # (the first call of a process also loads the code object)
             warmup, calls = (1, min(args.calls, 5)) if slow else (args.warmup, args.calls)
             out.update(warmup=warmup, calls=calls)
-            for _ in range(warmup):
-                res = plan_prioritized(*d, horizon=sh["T"], wide=wide)
-            torch.cuda.synchronize()
-            ms = []
-            for _ in range(calls):
-                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-                e0.record()
-                res = plan_prioritized(*d, horizon=sh["T"], wide=wide)
-                e1.record()
-                e1.synchronize()
-                ms.append(e0.elapsed_time(e1))
-            ms.sort()
+            ms, res = timed(lambda: plan_prioritized(*d, horizon=sh["T"], wide=wide), warmup, calls)
             t0 = time.perf_counter()
             full = solve_cases(*d, horizon=sh["T"], retries=8, wide=wide)
             torch.cuda.synchronize()
@@ -80,6 +118,8 @@ def main():
             out.update(restatement_cases=k, restatement_cpu_s=sec, restatement_cpu_s_per_case=sec / k,
                        restatement_solved_first_try=float(ref["solved"].mean()))
         print(json.dumps(out), flush=True)
+        if not args.no_device and not sh.get("wide", False):
+            print(json.dumps(improve_row(sh, d, full, args)), flush=True)
 
 
 if __name__ == "__main__":
