@@ -866,6 +866,23 @@ int magat_sim_mapf_improve(const uint8_t* map, int map_batched, int H, int W, co
                            int32_t* flowtime_before, int32_t* flowtime_after, int32_t* accepted, int32_t* status,
                            void* workspace, size_t workspace_bytes, int C, int N, int T, int iterations, int k, void* stream);
 
+/* The wide form of the improver (sim_mapf_lns_wide.hip; added behind ABI 9, nothing above changes): the same rule, cell for
+ * cell, on results of magat_sim_mapf_plan_wide - H, W <= 256, 1 <= T <= 1024 - with one workgroup of 64 * ceil(H / 64) threads per
+ * case, thread = map row, 1, 2 or 4 64-bit words per row.  The arguments, the outputs, the order of the checks and the codes are
+ * those of magat_sim_mapf_improve (NULL, non-positive sizes, then the limits: H, W > 256 or T > 1024, k outside 1..8,
+ * iterations outside 0..4096, a workspace too small - MAGAT_ERR_UNSUPPORTED, nothing launched and nothing counted - then
+ * MAGAT_ERR_WORKSPACE for a workspace that is not 8-byte aligned).  One launch, no synchronisation; it counts in form
+ * "sim_mapf_lns" and is one span of that profiling tag, as the wide planner shares the planner's.
+ * workspace: magat_sim_mapf_improve_wide_workspace_bytes(C, H, W, N, T) = C * (T * 6 * rows * words * 8 + 8 * ceil(N / 2)) bytes,
+ * rows = 64 * ceil(H / 64), words = 1 (W <= 64), 2 (W <= 128) or 4: per case the layers in the wide planner's order
+ * [t][V, A_up, A_left, A_down, A_right, R][row][word], then d0; 0 for a non-positive size or a side above 256. */
+size_t magat_sim_mapf_improve_wide_workspace_bytes(int C, int H, int W, int N, int T);
+int magat_sim_mapf_improve_wide(const uint8_t* map, int map_batched, int H, int W, const uint8_t* solved,
+                                int32_t* paths /* [C][N][T][2], in place */, int32_t* lengths, int32_t* makespan,
+                                int32_t* flowtime_before, int32_t* flowtime_after, int32_t* accepted, int32_t* status,
+                                void* workspace, size_t workspace_bytes, int C, int N, int T, int iterations, int k,
+                                void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Planning cases made on the device (sim_cases.hip; added behind ABI 9, nothing above changes): the first step of the expert
  * pipeline, the reference's offlineExpert/CasesGenerator.py - an obstacle map, its largest free component, a start and a goal

@@ -22,6 +22,10 @@ improve=I) runs it on the final batch.  This is STILL not ECBS and bounds nothin
 
     better = improve_schedules(obstacle_map, res, iterations=32, neighbourhood=4)      # the same keys, + flowtime_before / _after
 
+Maps above 64 x 64 and horizons above 256 are opt-in everywhere: plan_prioritized, solve_cases and improve_schedules take
+wide=True (csrc/sim_mapf_wide.hip, csrc/sim_mapf_lns_wide.hip: maps up to 256 x 256, horizons up to 1024), and
+solve_cases(..., wide=True, improve=I) hands it on; without it such shapes raise MagatNativeError as before.
+
 HIP only: CPU tensors raise MagatNativeError.  plan_prioritized is stream ordered and never waits for the device;
 solve_cases reads `solved` back once per round."""
 import torch
@@ -31,7 +35,8 @@ from .simulator import _dev_i32
 
 MAX_HORIZON = 256
 MAX_SIDE = 64
-WIDE_MAX_HORIZON = 1024      # the wide form (csrc/sim_mapf_wide.hip): maps up to 256 x 256
+WIDE_MAX_HORIZON = 1024      # the wide forms (csrc/sim_mapf_wide.hip, csrc/sim_mapf_lns_wide.hip): maps up to 256 x 256
+WIDE_MAX_SIDE = 256
 PACK_KEYS = ("paths", "lengths", "goal", "start", "makespan")
 
 
@@ -96,7 +101,7 @@ def promote(order, agent):
     return torch.gather(order, 1, rest)
 
 
-def improve_schedules(obstacle_map, res, iterations=32, neighbourhood=4):
+def improve_schedules(obstacle_map, res, iterations=32, neighbourhood=4, wide=False):
     """One call of magat_sim_mapf_improve on a plan_prioritized / solve_cases result `res` (obstacle_map: the map it was planned
     on, (H,W) or (C,H,W)): `iterations` rounds of neighbourhood re-planning per case with neighbourhoods of up to
     `neighbourhood` (1..8) agents - the rule is in include/magat_hip.h and DESIGN 4.11; deterministic, no random numbers.
@@ -107,7 +112,12 @@ def improve_schedules(obstacle_map, res, iterations=32, neighbourhood=4):
     modified; a `T` key (solve_cases) is left out of the copy, since it would need a synchronisation - solved_pack computes it.
     Not ECBS: no bound on the flowtime; it never rises, and a valid schedule stays valid.  Conflicts between the agents of
     `res` are not looked for - the result is then unspecified.
-    Maps above 64 x 64 and horizons above 256 (results of wide=True at such shapes) raise MagatNativeError.
+    wide=False: maps above 64 x 64 and horizons above 256 (results of wide=True at such shapes) raise MagatNativeError.
+    wide=True lifts the limits to H, W <= 256 and horizons up to 1024, by plan_prioritized's rule: a shape with H, W <= 64 and
+    horizon <= 256 still goes to magat_sim_mapf_improve, with the same result as wide=False; a larger one to
+    magat_sim_mapf_improve_wide (csrc/sim_mapf_lns_wide.hip) - the same rule, one workgroup per case, and a workspace of
+    horizon * 6 * 64 ceil(H / 64) * (1, 2 or 4 words >= W / 64) * 8 + 8 ceil(N / 2) bytes per case.  Beyond those limits it
+    raises MagatNativeError.
     Stream ordered, no host synchronisation."""
     paths = res["paths"]
     if not isinstance(obstacle_map, torch.Tensor) or not obstacle_map.is_cuda or not paths.is_cuda:
@@ -117,9 +127,14 @@ def improve_schedules(obstacle_map, res, iterations=32, neighbourhood=4):
     C, N, T, _ = paths.shape
     assert m.dim() in (2, 3) and (m.dim() == 2 or m.shape[0] == C), "obstacle_map must be (H,W) or (C,H,W)"
     H, W = m.shape[-2], m.shape[-1]
-    if H > MAX_SIDE or W > MAX_SIDE or T > MAX_HORIZON:
+    to_wide = H > MAX_SIDE or W > MAX_SIDE or T > MAX_HORIZON
+    if to_wide and not wide:
         raise nat.MagatNativeError("improve_schedules takes maps up to %d x %d and horizons up to %d, not %d x %d / %d "
-                                   "(there is no wide form of it)" % (MAX_SIDE, MAX_SIDE, MAX_HORIZON, H, W, T))
+                                   "(wide=True takes maps up to %d x %d and horizons up to %d)"
+                                   % (MAX_SIDE, MAX_SIDE, MAX_HORIZON, H, W, T, WIDE_MAX_SIDE, WIDE_MAX_SIDE, WIDE_MAX_HORIZON))
+    if H > WIDE_MAX_SIDE or W > WIDE_MAX_SIDE or T > WIDE_MAX_HORIZON:
+        raise nat.MagatNativeError("improve_schedules(wide=True) takes maps up to %d x %d and horizons up to %d, not %d x %d / %d"
+                                   % (WIDE_MAX_SIDE, WIDE_MAX_SIDE, WIDE_MAX_HORIZON, H, W, T))
     dev = paths.device
     out = {key: value for key, value in res.items() if key != "T"}
     out["paths"] = _dev_i32(paths, "paths").clone()
@@ -129,13 +144,15 @@ def improve_schedules(obstacle_map, res, iterations=32, neighbourhood=4):
     assert tuple(out["lengths"].shape) == (C, N) and out["makespan"].numel() == C and solved.numel() == C
     extra = torch.empty(4, C, dtype=torch.int32, device=dev)
     lib = nat.lib()
-    ws = torch.empty(max(int(lib.magat_sim_mapf_improve_workspace_bytes(C, N, T)), 8), dtype=torch.uint8, device=dev)
+    ws_bytes = (lib.magat_sim_mapf_improve_wide_workspace_bytes(C, H, W, N, T) if to_wide
+                else lib.magat_sim_mapf_improve_workspace_bytes(C, N, T))
+    ws = torch.empty(max(int(ws_bytes), 8), dtype=torch.uint8, device=dev)
+    entry = "magat_sim_mapf_improve_wide" if to_wide else "magat_sim_mapf_improve"
     with torch.cuda.device(dev):
-        nat.check(lib.magat_sim_mapf_improve(nat.ptr(m), 1 if m.dim() == 3 else 0, H, W, nat.ptr(solved), nat.ptr(out["paths"]),
-                                             nat.ptr(out["lengths"]), nat.ptr(out["makespan"]), nat.ptr(extra[0]),
-                                             nat.ptr(extra[1]), nat.ptr(extra[2]), nat.ptr(extra[3]), nat.ptr(ws), ws.numel(),
-                                             C, N, T, int(iterations), int(neighbourhood), nat.current_stream(dev)),
-                  "magat_sim_mapf_improve")
+        nat.check(getattr(lib, entry)(nat.ptr(m), 1 if m.dim() == 3 else 0, H, W, nat.ptr(solved), nat.ptr(out["paths"]),
+                                      nat.ptr(out["lengths"]), nat.ptr(out["makespan"]), nat.ptr(extra[0]), nat.ptr(extra[1]),
+                                      nat.ptr(extra[2]), nat.ptr(extra[3]), nat.ptr(ws), ws.numel(), C, N, T, int(iterations),
+                                      int(neighbourhood), nat.current_stream(dev)), entry)
     out.update(flowtime_before=extra[0], flowtime_after=extra[1], accepted=extra[2], status=extra[3])
     return out
 
@@ -152,7 +169,8 @@ def solve_cases(obstacle_map, start, goal, horizon=None, retries=8, wide=False, 
     the keys that expert_samples takes as **pack.
 
     wide: as in plan_prioritized, for the first plan and every re-plan.
-    improve=I > 0: improve_schedules(obstacle_map, res, iterations=I) on the final batch (its limits apply) - the returned dict
+    improve=I > 0: improve_schedules(obstacle_map, res, iterations=I, wide=wide) on the final batch (its limits apply; `wide` is
+    handed on, so a wide batch is improved by the wide form) - the returned dict
     then also holds flowtime_before, flowtime_after, accepted and status, and T is taken from the improved makespans.  The
     default 0 leaves the result and the calls made as they were.
     One host synchronisation per round (the read of `solved`), one more for T."""
@@ -175,7 +193,7 @@ def solve_cases(obstacle_map, start, goal, horizon=None, retries=8, wide=False, 
         order.index_copy_(0, idx, again)
         rounds.index_add_(0, idx, torch.ones_like(idx, dtype=torch.int32))
     if int(improve) > 0:
-        res = improve_schedules(obstacle_map, res, iterations=int(improve))
+        res = improve_schedules(obstacle_map, res, iterations=int(improve), wide=wide)
     done = res["makespan"][res["solved"] != 0]
     res.update(order=order, rounds=rounds, T=int(done.max().item()) + 1 if done.numel() else 1)
     return res

@@ -1,9 +1,11 @@
-// A stand-in for <hip/hip_runtime.h> that lets ONE wavefront-per-workgroup kernel of csrc/ compile for the host and run as 64
-// threads (tools/host_wave/mapf_lns_check.cpp): lane = thread, every cross-lane operation (ballot, DPP wave shift, readfirstlane,
-// shuffle) and __syncthreads is a rendezvous of all 64 threads, so the kernel must keep them in wave-uniform control flow - as
-// the hardware wants it too.  Between two rendezvous the lanes run in any order: a missing barrier between a store of one
-// lane and a load of another, which lock step would hide, is a data race here (run under a thread sanitizer to see it).
-// Workgroups run one after another; __shared__ variables are statics.  Only what the row-board kernels use is provided.
+// A stand-in for <hip/hip_runtime.h> that lets a row-board kernel of csrc/ - one workgroup of 1 to 4 wavefronts per case - compile
+// for the host and run as one thread per lane (tools/host_wave/mapf_lns_check.cpp, mapf_lns_wide_check.cpp): every cross-lane
+// operation (ballot, DPP wave shift, readfirstlane, shuffle) is a rendezvous of the 64 threads of ONE wavefront and exchanges
+// inside it, __syncthreads is a rendezvous of all threads of the workgroup, blockDim.x is what the launch asked for.  So the
+// kernel must keep a wavefront in wave-uniform control flow around the first and the workgroup in uniform control flow around
+// the second - as the hardware wants it too.  Between two rendezvous the threads run in any order: a missing barrier between a
+// store of one thread and a load of another, which lock step would hide, is a data race here (run under a thread sanitizer to
+// see it).  Workgroups run one after another; __shared__ variables are statics.  Only what the row-board kernels use is provided.
 #pragma once
 #include <math.h>
 #include <pthread.h>
@@ -30,19 +32,19 @@ constexpr hipError_t hipSuccess = 0;
 inline hipError_t hipGetLastError() { return hipSuccess; }
 
 namespace host_wave {
-constexpr int kLanes = 64;
-inline thread_local int lane = 0;
-inline unsigned block = 0, blocks = 1;
-inline pthread_barrier_t barrier;
-inline unsigned long long slot[kLanes];
-inline void meet() { pthread_barrier_wait(&barrier); }
-// every lane posts a value; fn(slots) is evaluated by every lane between the two rendezvous
+constexpr int kLanes = 64, kMaxWaves = 4;
+inline thread_local int tid = 0, lane = 0, wave = 0;
+inline unsigned block = 0, blocks = 1, threads = kLanes;
+inline pthread_barrier_t barrier, wave_barrier[kMaxWaves];
+inline unsigned long long slot[kMaxWaves][kLanes];
+inline void meet() { pthread_barrier_wait(&barrier); }      // the workgroup
+// every lane of a wavefront posts a value; fn(slots of the wavefront) is evaluated by every lane between the two rendezvous
 template <typename F>
 inline auto exchange(unsigned long long mine, F fn) {
-  slot[lane] = mine;
-  meet();
-  auto r = fn(slot);
-  meet();
+  slot[wave][lane] = mine;
+  pthread_barrier_wait(&wave_barrier[wave]);
+  auto r = fn(slot[wave]);
+  pthread_barrier_wait(&wave_barrier[wave]);
   return r;
 }
 inline unsigned long long ballot(bool p) {
@@ -67,7 +69,7 @@ inline int shfl_xor(int v, int mask) {
 }
 struct Idx {
   struct X {
-    operator unsigned() const { return (unsigned)lane; }
+    operator unsigned() const { return (unsigned)tid; }
   } x;
 };
 struct BlockIdx {
@@ -76,34 +78,47 @@ struct BlockIdx {
   } x;
   unsigned y = 0, z = 0;
 };
+struct BlockDim {
+  struct X {
+    operator unsigned() const { return threads; }
+  } x;
+  unsigned y = 1, z = 1;
+};
 inline unsigned long long dyn_lds[256 * 64];      // the dynamic LDS of a workgroup: 128 KB
 struct GridDim {
   unsigned x = 1, y = 1, z = 1;
 };
-// runs kernel(args...) for every workgroup of the grid, 64 threads each
+// runs kernel(args...) for every workgroup of the grid, block.x threads each: whole wavefronts, 1 to 4 of them
 template <typename K, typename... A>
-inline void launch(K kernel, dim3 grid, A... args) {
+inline void launch(K kernel, dim3 grid, dim3 block_dim, A... args) {
+  if (block_dim.x == 0 || block_dim.x % kLanes || block_dim.x > kLanes * kMaxWaves || block_dim.y != 1 || block_dim.z != 1) abort();
   blocks = grid.x;
+  threads = block_dim.x;
+  const int nt = (int)threads, nw = nt / kLanes;
   for (block = 0; block < grid.x; ++block) {
-    pthread_barrier_init(&barrier, nullptr, kLanes);
-    auto body = [&](int l) {
-      lane = l;
+    pthread_barrier_init(&barrier, nullptr, nt);
+    for (int w = 0; w < nw; ++w) pthread_barrier_init(&wave_barrier[w], nullptr, kLanes);
+    auto body = [&](int t) {
+      tid = t;
+      lane = t % kLanes;
+      wave = t / kLanes;
       kernel(args...);
     };
-    pthread_t th[kLanes];
+    pthread_t th[kLanes * kMaxWaves];
     struct Arg {
       decltype(body)* b;
-      int l;
-    } arg[kLanes];
-    for (int l = 0; l < kLanes; ++l) {
-      arg[l] = {&body, l};
-      pthread_create(&th[l], nullptr, [](void* p) -> void* {
+      int t;
+    } arg[kLanes * kMaxWaves];
+    for (int t = 0; t < nt; ++t) {
+      arg[t] = {&body, t};
+      if (pthread_create(&th[t], nullptr, [](void* p) -> void* {
         Arg* a = static_cast<Arg*>(p);
-        (*a->b)(a->l);
+        (*a->b)(a->t);
         return nullptr;
-      }, &arg[l]);
+      }, &arg[t]) != 0) abort();
     }
-    for (int l = 0; l < kLanes; ++l) pthread_join(th[l], nullptr);
+    for (int t = 0; t < nt; ++t) pthread_join(th[t], nullptr);
+    for (int w = 0; w < nw; ++w) pthread_barrier_destroy(&wave_barrier[w]);
     pthread_barrier_destroy(&barrier);
   }
 }
@@ -112,6 +127,7 @@ inline void launch(K kernel, dim3 grid, A... args) {
 static host_wave::Idx threadIdx;
 static host_wave::BlockIdx blockIdx;
 static host_wave::GridDim gridDim;
+static host_wave::BlockDim blockDim;
 
 #define __syncthreads() host_wave::meet()
 #define __builtin_amdgcn_ballot_w64(p) host_wave::ballot(p)
@@ -128,4 +144,4 @@ inline unsigned long long __brevll(unsigned long long v) {
 }
 #define __HIP_MEMORY_SCOPE_AGENT 0
 #define __hip_atomic_fetch_add(p, v, order, scope) __atomic_fetch_add(p, v, order)
-#define hipLaunchKernelGGL(kernel, grid, block, lds, stream, ...) host_wave::launch(kernel, grid, __VA_ARGS__)
+#define hipLaunchKernelGGL(kernel, grid, block, lds, stream, ...) host_wave::launch(kernel, grid, block, __VA_ARGS__)

@@ -9,10 +9,12 @@ the median of 5, and the line says so in "calls"), the share of cases solved at 
 solve_cases' retries, and - with --restatement K - the CPU seconds that tests/mapf_restatement.py (a per-cell Python
 restatement, NOT ECBS; the only comparison there is) needs for the first K cases of each shape.  One JSON line per shape.
 
-The two 64 x 64-form shapes get a second line each, "<shape>_improve": improve_schedules (csrc/sim_mapf_lns.hip; iterations = 32,
-neighbourhood = 4) on solve_cases' result, timed the same way, with the total flowtime of the solved cases going in and coming
-out and the free-space lower bound sum(d0 - 1) - every agent planned alone on the empty map, one more plan_prioritized call
-with C N one-agent cases.  None of these figures is a gate.
+Every shape gets a second line, "<shape>_improve": improve_schedules (csrc/sim_mapf_lns.hip, and for the two wide shapes
+csrc/sim_mapf_lns_wide.hip with wide=True on solve_cases(..., wide=True)'s result; iterations = 32, neighbourhood = 4) on
+solve_cases' result, timed the same way, with the total flowtime of the solved cases going in and coming out and the
+free-space lower bound sum(d0 - 1) - every agent planned alone on the empty map: one more plan_prioritized call with C N
+one-agent cases; at the wide shapes only the agents of the solved cases, with the longest solved path as the horizon, in
+chunks whose workspace stays below 1 GiB.  None of these figures is a gate.
 
     python tools/mapf_bench.py [--restatement K] [--no-device]"""
 import argparse
@@ -54,24 +56,49 @@ def timed(fn, warmup, calls):
     return sorted(ms), res
 
 
+def free_lengths_wide(d, ok, horizon):
+    """d0 (K,N) of the agents of the cases in `ok`: each planned alone by the wide planner, a chunk of one-agent cases per call."""
+    import torch
+    from magat_pathplanning_amd import _native as nat
+    from magat_pathplanning_amd import plan_prioritized
+    idx = torch.nonzero(ok).flatten()
+    s, g = d[1].index_select(0, idx).reshape(-1, 1, 2), d[2].index_select(0, idx).reshape(-1, 1, 2)
+    H, W = d[0].shape[-2], d[0].shape[-1]
+    chunk = max(1, (1 << 30) // max(1, int(nat.lib().magat_sim_mapf_wide_workspace_bytes(1, H, W, horizon))))
+    lengths = []
+    for i in range(0, len(s), chunk):
+        alone = plan_prioritized(d[0], s[i:i + chunk].contiguous(), g[i:i + chunk].contiguous(), horizon=horizon, wide=True)
+        assert bool(alone["solved"].all())
+        lengths.append(alone["lengths"])
+    return torch.cat(lengths).reshape(len(idx), -1)
+
+
 def improve_row(sh, d, full, args):
     import torch
     from magat_pathplanning_amd import improve_schedules, plan_prioritized
+    wide = sh.get("wide", False)
     t0 = time.perf_counter()
-    improve_schedules(d[0], full, **IMPROVE)
+    improve_schedules(d[0], full, wide=wide, **IMPROVE)
     torch.cuda.synchronize()
     slow = time.perf_counter() - t0 > 1.0
     warmup, calls = (1, min(args.calls, 5)) if slow else (args.warmup, args.calls)
-    ms, better = timed(lambda: improve_schedules(d[0], full, **IMPROVE), warmup, calls)
+    ms, better = timed(lambda: improve_schedules(d[0], full, wide=wide, **IMPROVE), warmup, calls)
     ok = better["status"] == 0
-    alone = plan_prioritized(d[0], d[1].reshape(-1, 1, 2), d[2].reshape(-1, 1, 2), horizon=sh["T"])      # every agent on the empty map
-    d0 = alone["lengths"].reshape(sh["C"], sh["N"])
-    assert bool(alone["solved"].all())
+    if not bool(ok.any()):
+        return dict(shape=sh["name"] + "_improve", cases=sh["C"], agents=sh["N"], T=sh["T"], warmup=warmup, calls=calls, **IMPROVE,
+                    improve_ms_median=ms[len(ms) // 2], improve_ms_min=ms[0], improve_ms_max=ms[-1], cases_improved_or_unchanged=0)
+    if wide:
+        lower = int((free_lengths_wide(d, ok, int(full["makespan"][ok].max()) + 1) - 1).sum())
+    else:
+        alone = plan_prioritized(d[0], d[1].reshape(-1, 1, 2), d[2].reshape(-1, 1, 2), horizon=sh["T"])      # every agent on the empty map
+        d0 = alone["lengths"].reshape(sh["C"], sh["N"])
+        assert bool(alone["solved"].all())
+        lower = int((d0[ok] - 1).sum())
     return dict(shape=sh["name"] + "_improve", cases=sh["C"], agents=sh["N"], T=sh["T"], warmup=warmup, calls=calls, **IMPROVE,
                 improve_ms_median=ms[len(ms) // 2], improve_ms_min=ms[0], improve_ms_max=ms[-1],
                 cases_improved_or_unchanged=int(ok.sum()), cases_with_an_accepted_iteration=int((better["accepted"] > 0).sum()),
                 accepted_iterations=int(better["accepted"].sum()), flowtime_before=int(better["flowtime_before"][ok].sum()),
-                flowtime_after=int(better["flowtime_after"][ok].sum()), flowtime_lower_bound=int((d0[ok] - 1).sum()),
+                flowtime_after=int(better["flowtime_after"][ok].sum()), flowtime_lower_bound=lower,
                 makespan_max_before=int(full["makespan"][ok].max()), makespan_max_after=int(better["makespan"][ok].max()))
 
 
@@ -118,7 +145,7 @@ def main():
             out.update(restatement_cases=k, restatement_cpu_s=sec, restatement_cpu_s_per_case=sec / k,
                        restatement_solved_first_try=float(ref["solved"].mean()))
         print(json.dumps(out), flush=True)
-        if not args.no_device and not sh.get("wide", False):
+        if not args.no_device:
             print(json.dumps(improve_row(sh, d, full, args)), flush=True)
 
 
