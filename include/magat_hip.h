@@ -884,6 +884,56 @@ int magat_sim_mapf_improve_wide(const uint8_t* map, int map_batched, int H, int 
                                 void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * Auditing schedules (sim_mapf_audit.hip, sim_mapf_audit_wide.hip; added behind ABI 9, nothing above changes): is a schedule a
+ * valid MAPF solution, where is its FIRST fault, and how far is its flowtime from the classic lower bound - for C cases in one
+ * launch, nothing is modified.  Integer arithmetic only.  Device pointers, stream ordered, no allocation, no synchronisation;
+ * one kernel, one count in form "sim_mapf_audit", one span of its own profiling tag.
+ *
+ * map (H,W) or (C,H,W) uint8 (non-zero: obstacle); paths (C,N,T,2), lengths (C,N), start / goal (C,N,2) int32: the layout of the
+ * expert entries; solved (C,) uint8 or NULL.  Outputs, all int32:
+ *   dist (C,N)      the shortest 4-connected distance over free cells from start[a] to goal[a], other agents ignored: 0 when they
+ *                   are equal; -1 when either cell is off the map or on an obstacle, or when the goal is unreachable.
+ *   flowtime_bound, makespan_bound (C,)   the sum and the maximum of the case's dist, both -1 when any dist of the case is -1.
+ *                   Computed for EVERY case, skipped and faulty ones included: they depend on map, start and goal alone.  No
+ *                   schedule of the case has a smaller flowtime / makespan.
+ *   status (C,)     0 valid; 1 skipped (solved given and solved[c] == 0); 2 a fault was found.
+ *   fault (C,4)     (kind, t, a, b) of the first fault, (0,-1,-1,-1) when there is none or the case is skipped.
+ *   flowtime, makespan (C,)   the sum and the maximum of lengths - 1 for status 0, otherwise -1.
+ * Stage 1, per agent: agents go in index order and the first agent with a fault decides; b = -1.  Within an agent, with
+ * L = lengths[a], in this order: kind 1 - L outside 1..T, reported with t = -1, the agent's other checks are skipped; kind 2 -
+ * paths[a,0] != start[a], t = 0; kind 3 - paths[a,L-1] != goal[a], t = L - 1; then for t = 0 .. T - 1 ascending, at each t in
+ * this order: kind 4 - the cell is off the map or on an obstacle; kind 5 - t >= L and the cell differs from the cell at L - 1;
+ * kind 6 - t > 0 and the step from t - 1 is none of the five moves.
+ * Stage 2, conflicts, only when stage 1 found nothing in the case: the smallest (t, a, b) with a < b, at the same (t, a, b)
+ * vertex before swap: kind 7, vertex - paths[a,t] == paths[b,t], t = 0 .. T - 1 (padding counts: an agent holds its goal);
+ * kind 8, swap, t >= 1 - paths[a,t] == paths[b,t-1], paths[b,t] == paths[a,t-1] and a moved.  O(N T) per case: two cell-owner
+ * grids for t - 1 and t, every agent takes atomicMin(owner[cell], a); only the cells that were set are cleared.
+ * Bad input never faults the kernel: every cell is screened before it indexes anything - negative rows or columns, values
+ * such as 2^30, a length of 0 or T + 1 are reported as above.
+ * magat_sim_mapf_audit: one wavefront per case, lane = map row, the owner grids in LDS.  Limits: H, W <= 64, 1 <= T <= 256,
+ * N <= 4096.  workspace: magat_sim_mapf_audit_workspace_bytes(C, N, T) = C * 2 * N * 4 bytes (the cell of every agent at t - 1
+ * and at t), 8-byte aligned; 0 for a non-positive size, N > 4096 or T > 256.
+ * magat_sim_mapf_audit_wide: one workgroup of 64 * ceil(H / 64) threads per case, thread = map row, 1, 2 or 4 words per row, the
+ * owner grids in the workspace.  Limits: H, W <= 256, 1 <= T <= 1024, N <= 4096.  workspace:
+ * magat_sim_mapf_audit_wide_workspace_bytes(C, H, W, N, T) = C * (2 * H * W + 2 * N) * 4 bytes (the two grids, then the cells),
+ * 8-byte aligned, initialised by the call itself; 0 for a non-positive size, a side above 256, N > 4096 or T > 1024.
+ * The checks come in the order and with the codes of magat_sim_mapf_improve: NULL pointers (solved may be NULL), non-positive
+ * sizes, then the limits and a workspace too small - MAGAT_ERR_UNSUPPORTED, nothing launched and nothing counted - then
+ * MAGAT_ERR_WORKSPACE for a workspace that is not 8-byte aligned. */
+size_t magat_sim_mapf_audit_workspace_bytes(int C, int N, int T);
+int magat_sim_mapf_audit(const uint8_t* map, int map_batched, int H, int W, const uint8_t* solved /* [C] or NULL */,
+                         const int32_t* paths /* [C][N][T][2] */, const int32_t* lengths, const int32_t* start,
+                         const int32_t* goal, int32_t* status, int32_t* fault /* [C][4] */, int32_t* dist /* [C][N] */,
+                         int32_t* flowtime_bound, int32_t* makespan_bound, int32_t* flowtime, int32_t* makespan, void* workspace,
+                         size_t workspace_bytes, int C, int N, int T, void* stream);
+size_t magat_sim_mapf_audit_wide_workspace_bytes(int C, int H, int W, int N, int T);
+int magat_sim_mapf_audit_wide(const uint8_t* map, int map_batched, int H, int W, const uint8_t* solved /* [C] or NULL */,
+                              const int32_t* paths /* [C][N][T][2] */, const int32_t* lengths, const int32_t* start,
+                              const int32_t* goal, int32_t* status, int32_t* fault /* [C][4] */, int32_t* dist /* [C][N] */,
+                              int32_t* flowtime_bound, int32_t* makespan_bound, int32_t* flowtime, int32_t* makespan,
+                              void* workspace, size_t workspace_bytes, int C, int N, int T, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Planning cases made on the device (sim_cases.hip; added behind ABI 9, nothing above changes): the first step of the expert
  * pipeline, the reference's offlineExpert/CasesGenerator.py - an obstacle map, its largest free component, a start and a goal
  * per agent - for C cases in one launch; its outputs are what magat_sim_mapf_plan takes.  Device pointers, stream ordered, no

@@ -22,9 +22,21 @@ improve=I) runs it on the final batch.  This is STILL not ECBS and bounds nothin
 
     better = improve_schedules(obstacle_map, res, iterations=32, neighbourhood=4)      # the same keys, + flowtime_before / _after
 
-Maps above 64 x 64 and horizons above 256 are opt-in everywhere: plan_prioritized, solve_cases and improve_schedules take
-wide=True (csrc/sim_mapf_wide.hip, csrc/sim_mapf_lns_wide.hip: maps up to 256 x 256, horizons up to 1024), and
-solve_cases(..., wide=True, improve=I) hands it on; without it such shapes raise MagatNativeError as before.
+What the solver does not promise can be checked after the fact, case by case: audit_schedules (csrc/sim_mapf_audit.hip)
+looks for the first fault of every schedule - a cell off the map, a step that is no move, a vertex conflict or a swap between
+two agents - and computes the classic lower bound of the optimal flowtime, the sum over the agents of the obstacle-avoiding
+shortest distance from start to goal.  A valid schedule with flowtime <= w * bound is certified w-suboptimal: ECBS(w)'s promise,
+given afterwards.  It takes any schedules in pack_schedules' layout, the solver's or somebody else's.
+
+    audit = audit_schedules(obstacle_map, res)              # status, fault, dist, flowtime_bound, makespan_bound, flowtime, makespan
+    keep = certified(audit, 1.05)                           # (C,) bool on the device
+    pack = certified_pack(res, audit, 1.05)                 # solved_pack restricted to the certified cases
+    res = solve_cases(obstacle_map, start, goal, certify=1.05)      # the audit's keys and `certified` in the result
+
+Maps above 64 x 64 and horizons above 256 are opt-in everywhere: plan_prioritized, solve_cases, improve_schedules and
+audit_schedules take wide=True (csrc/sim_mapf_wide.hip, csrc/sim_mapf_lns_wide.hip, csrc/sim_mapf_audit_wide.hip: maps up to
+256 x 256, horizons up to 1024), and solve_cases(..., wide=True, improve=I, certify=w) hands it on; without it such shapes raise
+MagatNativeError as before.
 
 HIP only: CPU tensors raise MagatNativeError.  plan_prioritized is stream ordered and never waits for the device;
 solve_cases reads `solved` back once per round."""
@@ -38,6 +50,8 @@ MAX_SIDE = 64
 WIDE_MAX_HORIZON = 1024      # the wide forms (csrc/sim_mapf_wide.hip, csrc/sim_mapf_lns_wide.hip): maps up to 256 x 256
 WIDE_MAX_SIDE = 256
 PACK_KEYS = ("paths", "lengths", "goal", "start", "makespan")
+MAX_AGENTS_AUDIT = 4096      # audit_schedules: agents per case
+AUDIT_KEYS = ("status", "fault", "dist", "flowtime_bound", "makespan_bound", "flowtime", "makespan")
 
 
 def default_horizon(H, W, N, wide=False):
@@ -111,7 +125,7 @@ def improve_schedules(obstacle_map, res, iterations=32, neighbourhood=4, wide=Fa
     a step that is none of the five moves.  Skipped and refused cases come back as they were.  The tensors of `res` are not
     modified; a `T` key (solve_cases) is left out of the copy, since it would need a synchronisation - solved_pack computes it.
     Not ECBS: no bound on the flowtime; it never rises, and a valid schedule stays valid.  Conflicts between the agents of
-    `res` are not looked for - the result is then unspecified.
+    `res` are not looked for - the result is then unspecified (audit_schedules looks for them).
     wide=False: maps above 64 x 64 and horizons above 256 (results of wide=True at such shapes) raise MagatNativeError.
     wide=True lifts the limits to H, W <= 256 and horizons up to 1024, by plan_prioritized's rule: a shape with H, W <= 64 and
     horizon <= 256 still goes to magat_sim_mapf_improve, with the same result as wide=False; a larger one to
@@ -157,7 +171,93 @@ def improve_schedules(obstacle_map, res, iterations=32, neighbourhood=4, wide=Fa
     return out
 
 
-def solve_cases(obstacle_map, start, goal, horizon=None, retries=8, wide=False, improve=0):
+def audit_schedules(obstacle_map, res, wide=False):
+    """One call of magat_sim_mapf_audit on schedules in pack_schedules' layout: `res` is any dict with paths (C,N,T,2), lengths
+    (C,N), start and goal (C,N,2) and optionally solved (C,) - a plan_prioritized, solve_cases or improve_schedules result or a
+    pack_schedules pack; a `T` or `makespan` key is ignored.  obstacle_map (H,W) or (C,H,W), non-zero: obstacle.  Returns a dict
+    of new int32 device tensors (the rule is in include/magat_hip.h and DESIGN 4.11):
+      status (C,)          0 valid; 1 skipped (`solved` given and zero); 2 a fault was found
+      fault (C,4)          (kind, t, a, b) of the FIRST fault, (0,-1,-1,-1) without one or when skipped.  Stage 1, agents in index
+                           order, per agent in this order: 1 a length outside 1..T (t = -1); 2 paths[a,0] != start[a]; 3
+                           paths[a,L-1] != goal[a]; then for t ascending 4 a cell off the map or on an obstacle, 5 t >= L and the
+                           cell differs from the one at L-1, 6 a step that is none of the five moves (b = -1).  Stage 2, only
+                           without a stage-1 fault: the smallest (t, a, b), a < b, vertex before swap - 7 both on one cell at t
+                           (padding counts: an agent holds its goal), 8 they exchange their cells between t-1 and t.
+      dist (C,N)           the shortest 4-connected distance over free cells from start[a] to goal[a], other agents ignored; -1
+                           when a cell is off the map or on an obstacle or there is no way
+      flowtime_bound, makespan_bound (C,)      sum and max of dist, -1 when a dist of the case is -1 - for EVERY case: the
+                           optimal flowtime / makespan of the case is at least this
+      flowtime, makespan (C,)                  sum and max of lengths - 1 for status 0, otherwise -1
+    Bad input is reported, never followed: no cell indexes anything before it was screened.  The inputs are not modified.
+    wide=False: maps above 64 x 64 and horizons above 256 raise MagatNativeError.  wide=True lifts the limits to H, W <= 256
+    and horizons up to 1024, by plan_prioritized's rule: a shape inside the 64 limits still goes to magat_sim_mapf_audit, a
+    larger one to magat_sim_mapf_audit_wide (csrc/sim_mapf_audit_wide.hip) - the same rule, one workgroup per case.  At most
+    4096 agents per case.  Stream ordered, no host synchronisation."""
+    paths = res["paths"]
+    if not isinstance(obstacle_map, torch.Tensor) or not obstacle_map.is_cuda or not paths.is_cuda:
+        raise nat.MagatNativeError("obstacle_map and the schedules must be device tensors (no CPU fallback)")
+    m = obstacle_map.to(torch.uint8).contiguous()
+    assert paths.dim() == 4 and paths.shape[3] == 2, "paths must be (C,N,T,2)"
+    C, N, T, _ = paths.shape
+    assert m.dim() in (2, 3) and (m.dim() == 2 or m.shape[0] == C), "obstacle_map must be (H,W) or (C,H,W)"
+    H, W = m.shape[-2], m.shape[-1]
+    to_wide = H > MAX_SIDE or W > MAX_SIDE or T > MAX_HORIZON
+    if to_wide and not wide:
+        raise nat.MagatNativeError("audit_schedules takes maps up to %d x %d and horizons up to %d, not %d x %d / %d "
+                                   "(wide=True takes maps up to %d x %d and horizons up to %d)"
+                                   % (MAX_SIDE, MAX_SIDE, MAX_HORIZON, H, W, T, WIDE_MAX_SIDE, WIDE_MAX_SIDE, WIDE_MAX_HORIZON))
+    if H > WIDE_MAX_SIDE or W > WIDE_MAX_SIDE or T > WIDE_MAX_HORIZON:
+        raise nat.MagatNativeError("audit_schedules(wide=True) takes maps up to %d x %d and horizons up to %d, not %d x %d / %d"
+                                   % (WIDE_MAX_SIDE, WIDE_MAX_SIDE, WIDE_MAX_HORIZON, H, W, T))
+    if N > MAX_AGENTS_AUDIT:
+        raise nat.MagatNativeError("audit_schedules takes at most %d agents per case, not %d" % (MAX_AGENTS_AUDIT, N))
+    paths = _dev_i32(paths, "paths")
+    lengths, start, goal = _dev_i32(res["lengths"], "lengths"), _dev_i32(res["start"], "start"), _dev_i32(res["goal"], "goal")
+    assert tuple(lengths.shape) == (C, N) and tuple(start.shape) == (C, N, 2) and tuple(goal.shape) == (C, N, 2)
+    solved = res["solved"].to(torch.uint8).contiguous() if res.get("solved") is not None else None
+    assert solved is None or solved.numel() == C
+    dev = paths.device
+    status = torch.empty(C, dtype=torch.int32, device=dev)
+    fault = torch.empty(C, 4, dtype=torch.int32, device=dev)
+    dist = torch.empty(C, N, dtype=torch.int32, device=dev)
+    extra = torch.empty(4, C, dtype=torch.int32, device=dev)
+    lib = nat.lib()
+    ws_bytes = (lib.magat_sim_mapf_audit_wide_workspace_bytes(C, H, W, N, T) if to_wide
+                else lib.magat_sim_mapf_audit_workspace_bytes(C, N, T))
+    ws = torch.empty(max(int(ws_bytes), 8), dtype=torch.uint8, device=dev)
+    entry = "magat_sim_mapf_audit_wide" if to_wide else "magat_sim_mapf_audit"
+    with torch.cuda.device(dev):
+        nat.check(getattr(lib, entry)(nat.ptr(m), 1 if m.dim() == 3 else 0, H, W, nat.ptr(solved), nat.ptr(paths), nat.ptr(lengths),
+                                      nat.ptr(start), nat.ptr(goal), nat.ptr(status), nat.ptr(fault), nat.ptr(dist),
+                                      nat.ptr(extra[0]), nat.ptr(extra[1]), nat.ptr(extra[2]), nat.ptr(extra[3]), nat.ptr(ws),
+                                      ws.numel(), C, N, T, nat.current_stream(dev)), entry)
+    return dict(status=status, fault=fault, dist=dist, flowtime_bound=extra[0], makespan_bound=extra[1], flowtime=extra[2],
+                makespan=extra[3])
+
+
+def certified(audit, w):
+    """(C,) bool device tensor: the cases of an audit_schedules result whose schedule is valid and provably within the factor w
+    of the optimal flowtime - status == 0 and flowtime_bound >= 0 and flowtime <= w * flowtime_bound, compared in float64 (a
+    case with bound 0 and flowtime 0 is certified).  w < 1 raises ValueError.  No host synchronisation."""
+    w = float(w)
+    if not w >= 1.0:
+        raise ValueError("certified: w must be at least 1, not %r" % (w,))
+    bound = audit["flowtime_bound"]
+    return (audit["status"] == 0) & (bound >= 0) & (audit["flowtime"].to(torch.float64) <= w * bound.to(torch.float64))
+
+
+def certified_pack(res, audit, w):
+    """solved_pack restricted to the cases certified(audit, w): the same keys, for expert_schedule / expert_samples (**pack).
+    Raises ValueError when no case is left.  (Synchronises.)"""
+    idx = torch.nonzero(certified(audit, w)).flatten()
+    if idx.numel() == 0:
+        raise ValueError("certified_pack: no case of the batch is certified at w = %r" % (w,))
+    pack = {key: res[key].index_select(0, idx) for key in PACK_KEYS}
+    pack["T"] = int(pack["makespan"].max().item()) + 1
+    return pack
+
+
+def solve_cases(obstacle_map, start, goal, horizon=None, retries=8, wide=False, improve=0, certify=None):
     """plan_prioritized in index order, then up to `retries` re-plans of the cases still unsolved, each with that case's
     failed_agent moved to the front of its order.  Returns plan_prioritized's dict (every case holds its LAST plan) plus order
     (C,N) int32 (the order of that plan), rounds (C,) int32 (the plans made for the case, 1 = solved at once) and T =
@@ -173,7 +273,14 @@ def solve_cases(obstacle_map, start, goal, horizon=None, retries=8, wide=False, 
     handed on, so a wide batch is improved by the wide form) - the returned dict
     then also holds flowtime_before, flowtime_after, accepted and status, and T is taken from the improved makespans.  The
     default 0 leaves the result and the calls made as they were.
+    certify=w (a number >= 1): audit_schedules(obstacle_map, res, wide=wide) on the final batch, behind the last plan and
+    behind `improve` - the returned dict then also holds the audit's keys (status, fault, dist, flowtime_bound, makespan_bound,
+    flowtime; the audit's makespan equals the result's where status is 0 and is not copied) and certified = certified(audit, w),
+    (C,) bool; it adds no host synchronisation.  With improve > 0 as well, `status` is the AUDIT's (the improver's is 0 on every
+    solved case the audit calls valid).  The default None leaves the result and the calls made as they were.
     One host synchronisation per round (the read of `solved`), one more for T."""
+    if certify is not None and not float(certify) >= 1.0:
+        raise ValueError("solve_cases: certify must be at least 1, not %r" % (certify,))
     res = plan_prioritized(obstacle_map, start, goal, None, horizon, wide)
     C, N, _ = res["start"].shape
     dev = res["start"].device
@@ -194,6 +301,9 @@ def solve_cases(obstacle_map, start, goal, horizon=None, retries=8, wide=False, 
         rounds.index_add_(0, idx, torch.ones_like(idx, dtype=torch.int32))
     if int(improve) > 0:
         res = improve_schedules(obstacle_map, res, iterations=int(improve), wide=wide)
+    if certify is not None:
+        audit = audit_schedules(obstacle_map, res, wide=wide)
+        res.update({key: audit[key] for key in AUDIT_KEYS if key != "makespan"}, certified=certified(audit, certify))
     done = res["makespan"][res["solved"] != 0]
     res.update(order=order, rounds=rounds, T=int(done.max().item()) + 1 if done.numel() else 1)
     return res

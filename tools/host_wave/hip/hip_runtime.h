@@ -142,6 +142,12 @@ inline unsigned long long __brevll(unsigned long long v) {
   for (int i = 0; i < 64; ++i) r |= ((v >> i) & 1ull) << (63 - i);
   return r;
 }
+inline int atomicMin(int* p, int v) {
+  int old = __atomic_load_n(p, __ATOMIC_RELAXED);
+  while (v < old && !__atomic_compare_exchange_n(p, &old, v, true, __ATOMIC_RELAXED, __ATOMIC_RELAXED)) {
+  }
+  return old;
+}
 #define __HIP_MEMORY_SCOPE_AGENT 0
 #define __hip_atomic_fetch_add(p, v, order, scope) __atomic_fetch_add(p, v, order)
 #define hipLaunchKernelGGL(kernel, grid, block, lds, stream, ...) host_wave::launch(kernel, grid, block, __VA_ARGS__)

@@ -14,7 +14,11 @@ csrc/sim_mapf_lns_wide.hip with wide=True on solve_cases(..., wide=True)'s resul
 solve_cases' result, timed the same way, with the total flowtime of the solved cases going in and coming out and the
 free-space lower bound sum(d0 - 1) - every agent planned alone on the empty map: one more plan_prioritized call with C N
 one-agent cases; at the wide shapes only the agents of the solved cases, with the longest solved path as the horizon, in
-chunks whose workspace stays below 1 GiB.  None of these figures is a gate.
+chunks whose workspace stays below 1 GiB.
+
+And a third one, "<shape>_audit": audit_schedules (csrc/sim_mapf_audit.hip, for the two wide shapes csrc/sim_mapf_audit_wide.hip
+with wide=True) on solve_cases' result, timed the same way, with what it found: the cases valid / skipped / faulty, the cases
+certified at w = 1, 1.05 and 1.25, and the largest flowtime / bound ratio of the valid ones.  None of these figures is a gate.
 
     python tools/mapf_bench.py [--restatement K] [--no-device]"""
 import argparse
@@ -102,6 +106,27 @@ def improve_row(sh, d, full, args):
                 makespan_max_before=int(full["makespan"][ok].max()), makespan_max_after=int(better["makespan"][ok].max()))
 
 
+def audit_row(sh, d, full, args):
+    import torch
+    from magat_pathplanning_amd import audit_schedules, certified
+    wide = sh.get("wide", False)
+    t0 = time.perf_counter()
+    audit_schedules(d[0], full, wide=wide)
+    torch.cuda.synchronize()
+    slow = time.perf_counter() - t0 > 1.0
+    warmup, calls = (1, min(args.calls, 5)) if slow else (args.warmup, args.calls)
+    ms, audit = timed(lambda: audit_schedules(d[0], full, wide=wide), warmup, calls)
+    ok = (audit["status"] == 0) & (audit["flowtime_bound"] > 0)
+    ratio = (audit["flowtime"][ok].double() / audit["flowtime_bound"][ok].double()) if bool(ok.any()) else None
+    return dict(shape=sh["name"] + "_audit", cases=sh["C"], agents=sh["N"], T=sh["T"], warmup=warmup, calls=calls,
+                audit_ms_median=ms[len(ms) // 2], audit_ms_min=ms[0], audit_ms_max=ms[-1],
+                audit_us_per_case=ms[len(ms) // 2] * 1e3 / sh["C"], cases_valid=int((audit["status"] == 0).sum()),
+                cases_skipped=int((audit["status"] == 1).sum()), cases_faulty=int((audit["status"] == 2).sum()),
+                certified_1=int(certified(audit, 1).sum()), certified_1_05=int(certified(audit, 1.05).sum()),
+                certified_1_25=int(certified(audit, 1.25).sum()), ratio_max=None if ratio is None else float(ratio.max()),
+                flowtime=int(audit["flowtime"][ok].sum()), flowtime_bound=int(audit["flowtime_bound"][ok].sum()))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--restatement", type=int, default=0, help="time the Python restatement on this many cases per shape")
@@ -147,6 +172,7 @@ def main():
         print(json.dumps(out), flush=True)
         if not args.no_device:
             print(json.dumps(improve_row(sh, d, full, args)), flush=True)
+            print(json.dumps(audit_row(sh, d, full, args)), flush=True)
 
 
 if __name__ == "__main__":
