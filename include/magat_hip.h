@@ -934,6 +934,55 @@ int magat_sim_mapf_audit_wide(const uint8_t* map, int map_batched, int H, int W,
                               void* workspace, size_t workspace_bytes, int C, int N, int T, void* stream);
 
 /* ------------------------------------------------------------------------------------------
+ * An optimal expert: conflict-based search (sim_mapf_cbs.hip; added behind ABI 9, nothing above changes).  CBS (Sharon et al.
+ * 2015) for C cases in one launch, one wavefront per case, every node and every search inside it: optimal in the flowtime and
+ * complete up to a budget of nodes, and its open list gives a lower bound of the optimal flowtime.  Deterministic, integer
+ * arithmetic only.  Device pointers, stream ordered, no allocation, no synchronisation; one kernel, one count in form
+ * "sim_mapf_cbs", one span of its own profiling tag.  No focal search (it is not ECBS), no pruning by an incumbent, no disjoint
+ * splitting, no conflict prioritisation.
+ *
+ * map, start, goal, T, paths, lengths, makespan, solved: as in magat_sim_mapf_plan.  The other outputs are (C,) int32.
+ * Screening, before any cell indexes anything: a start or goal off the map or on an obstacle, or a start (a goal) that an agent
+ * of a lower index has too - status 3.  Then the root: every agent's FREE path, the planner's search and backtrace on empty
+ * boards, agents in index order; an agent without an arrival inside T - status 2 with horizon_hit 1.  Neither makes a node.
+ * Node: its parent, the agent it planned again, ONE constraint, its cost - the flowtime sum(lengths - 1) of its schedule - and
+ * that agent's new path and length; node 0, the root, holds N paths.  The schedule of a node is, per agent, the path of the
+ * nearest node on the chain to the root (itself first) that planned it, else the root's; the constraints of an agent are those
+ * of the nodes on that chain that planned it.  A constraint is a bit of the planner's reservation boards: "agent x is not on
+ * cell u at t" is bit u of V[t]; "x does not step from u in direction d, arriving at t" is bit u of A_opp(d)[t] - what the search
+ * reads as a swap.  The search returns the earliest arrival behind the last t at which V[t] holds the goal, so a constraint on an
+ * agent parked at its goal sends it away and back.
+ * Loop: take the open node with the smallest (cost, index).  Its first conflict is the audit's stage 2 on its schedule: the
+ * smallest (t, a, b), a < b, vertex before swap.  None - status 0, this schedule is the answer.  Otherwise, nodes + 2 >
+ * max_nodes - status 1.  Otherwise the node counts as expanded and gets two children, for a, then for b: a vertex conflict
+ * forbids the agent's cell at t (its last cell when it is parked), a swap its own step at t; the agent is searched again under
+ * all its constraints, cost = the parent's - its old length + its new one.  A child whose search finds no arrival (the
+ * reachable set ran empty, or t reached T - 1) keeps its slot, never enters the open list, and sets horizon_hit.  An empty open
+ * list - status 2.
+ *   status        0 solved, optimal among the schedules of at most T cells per path; 1 the budget ran out; 2 no schedule inside
+ *                 T (or none at all); 3 screened out
+ *   paths, lengths, makespan     status 0: the schedule, padded with each path's last cell; otherwise every agent's start cell
+ *                 with length 1, makespan 0.  solved = (status == 0)
+ *   flowtime      status 0: sum(lengths - 1); otherwise -1
+ *   lower_bound   status 0: the flowtime; status 1: the cost of the node the search stopped at, the minimum over the open list;
+ *                 status 2, 3: -1.  With horizon_hit == 0 no schedule of the case has a smaller flowtime; otherwise none of at
+ *                 most T cells per path has.
+ *   nodes         nodes created, the root included (0 for a case that got none); expanded: nodes that got their children
+ *   horizon_hit   1 when a child was dropped for lack of an arrival (or the root had none), else 0
+ * workspace: magat_sim_mapf_cbs_workspace_bytes(C, N, T, max_nodes) = C * 8 * (T * 5 * 64 + ceil(N * T / 4) + ceil(max_nodes *
+ * T / 4) + 2 * max_nodes + ceil(N / 2) + N) bytes - per case the five constraint boards, the root's paths and the nodes' paths
+ * (a cell is 16 bits, row << 8 | col), 16 bytes per node, the root's lengths, the conflict scan's two cell rows - 8-byte aligned;
+ * the call zeroes and initialises what it reads; 0 for a non-positive size or one above the limits.
+ * Limits: H, W <= 64, 1 <= T <= 256, N <= 4096, 1 <= max_nodes <= 4096, a workspace of that size - otherwise
+ * MAGAT_ERR_UNSUPPORTED, nothing launched and nothing counted.  The checks come in the planner's order: NULL pointers, non-positive
+ * sizes (max_nodes too), the limits and the workspace's size, then MAGAT_ERR_WORKSPACE for one that is not 8-byte aligned. */
+size_t magat_sim_mapf_cbs_workspace_bytes(int C, int N, int T, int max_nodes);
+int magat_sim_mapf_cbs(const uint8_t* map, int map_batched, int H, int W, const int32_t* start, const int32_t* goal,
+                       int32_t* paths /* [C][N][T][2] */, int32_t* lengths, int32_t* makespan, uint8_t* solved, int32_t* status,
+                       int32_t* flowtime, int32_t* lower_bound, int32_t* nodes, int32_t* expanded, int32_t* horizon_hit,
+                       void* workspace, size_t workspace_bytes, int C, int N, int T, int max_nodes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
  * Planning cases made on the device (sim_cases.hip; added behind ABI 9, nothing above changes): the first step of the expert
  * pipeline, the reference's offlineExpert/CasesGenerator.py - an obstacle map, its largest free component, a start and a goal
  * per agent - for C cases in one launch; its outputs are what magat_sim_mapf_plan takes.  Device pointers, stream ordered, no

@@ -1,8 +1,9 @@
 """A multi-agent path-finding expert on the device: the solver at the head of the expert pipeline (expert.py turns ITS
 schedules into training samples), for C cases at once.  The reference calls pre-built ecbs / cbs / sipp binaries, one
 subprocess per case (onlineExpert/ECBS_onlineExpert.py:81-104); this is prioritized planning with an exact space-time search
-per agent (csrc/sim_mapf.hip).  It is NOT ECBS: it gives no bound on the flowtime, and it is incomplete - a case
-can fail in one priority order and succeed in another, or stay unsolved.
+per agent (csrc/sim_mapf.hip).  The planner is NOT ECBS: it gives no bound on the flowtime, and it is incomplete - a
+case can fail in one priority order and succeed in another, or stay unsolved.  Behind it stands an optimal solver that is
+complete up to a node budget, conflict-based search (cbs_cases, csrc/sim_mapf_cbs.hip; solve_cases(..., optimal=K)) - see below.
 
     res = solve_cases(obstacle_map, start, goal)                          # plans, re-plans the unsolved cases in a new order
     pack = solved_pack(res)                                               # the solved cases, as pack_schedules lays them out
@@ -33,10 +34,19 @@ given afterwards.  It takes any schedules in pack_schedules' layout, the solver'
     pack = certified_pack(res, audit, 1.05)                 # solved_pack restricted to the certified cases
     res = solve_cases(obstacle_map, start, goal, certify=1.05)      # the audit's keys and `certified` in the result
 
+What the planner cannot do at all - two agents that must pass each other in a corridor with one pocket fail in EVERY priority
+order - conflict-based search does: cbs_cases (csrc/sim_mapf_cbs.hip) branches on the first conflict of a schedule, re-plans one
+agent per child under that agent's constraints with the planner's own search, and takes nodes best-first.  It is optimal in the
+flowtime, deterministic and complete up to max_nodes; where the budget runs out, the cost of the node it stopped at is still a
+lower bound of the optimal flowtime - a much tighter denominator for `certified` than the sum of the free distances.
+
+    opt = cbs_cases(obstacle_map, start, goal, max_nodes=256)             # status, flowtime, lower_bound, nodes, expanded, horizon_hit
+    res = solve_cases(obstacle_map, start, goal, optimal=256, certify=1.0)      # the planner's schedule unless CBS proved an optimum
+
 Maps above 64 x 64 and horizons above 256 are opt-in everywhere: plan_prioritized, solve_cases, improve_schedules and
 audit_schedules take wide=True (csrc/sim_mapf_wide.hip, csrc/sim_mapf_lns_wide.hip, csrc/sim_mapf_audit_wide.hip: maps up to
 256 x 256, horizons up to 1024), and solve_cases(..., wide=True, improve=I, certify=w) hands it on; without it such shapes raise
-MagatNativeError as before.
+MagatNativeError as before.  cbs_cases has no wide form yet: it refuses such shapes with or without wide=True.
 
 HIP only: CPU tensors raise MagatNativeError.  plan_prioritized is stream ordered and never waits for the device;
 solve_cases reads `solved` back once per round."""
@@ -52,6 +62,7 @@ WIDE_MAX_SIDE = 256
 PACK_KEYS = ("paths", "lengths", "goal", "start", "makespan")
 MAX_AGENTS_AUDIT = 4096      # audit_schedules: agents per case
 AUDIT_KEYS = ("status", "fault", "dist", "flowtime_bound", "makespan_bound", "flowtime", "makespan")
+MAX_NODES_CBS = 4096         # cbs_cases: nodes per case
 
 
 def default_horizon(H, W, N, wide=False):
@@ -257,7 +268,61 @@ def certified_pack(res, audit, w):
     return pack
 
 
-def solve_cases(obstacle_map, start, goal, horizon=None, retries=8, wide=False, improve=0, certify=None):
+def _cbs_limits(H, W, T, N, max_nodes):
+    if H > MAX_SIDE or W > MAX_SIDE or T > MAX_HORIZON or N > MAX_AGENTS_AUDIT or not 1 <= max_nodes <= MAX_NODES_CBS:
+        raise nat.MagatNativeError("cbs_cases takes maps up to %d x %d, horizons up to %d, %d agents and 1..%d nodes per case, not "
+                                   "%d x %d / %d / %d / %d (it has no wide form)"
+                                   % (MAX_SIDE, MAX_SIDE, MAX_HORIZON, MAX_AGENTS_AUDIT, MAX_NODES_CBS, H, W, T, N, max_nodes))
+
+
+def cbs_cases(obstacle_map, start, goal, horizon=None, max_nodes=256):
+    """One call of magat_sim_mapf_cbs: conflict-based search on every case, one wavefront per case, all nodes and searches in one
+    launch (the rule is in include/magat_hip.h and DESIGN 4.11).  obstacle_map (H,W) or (C,H,W), start / goal (C,N,2) as in
+    plan_prioritized; horizon: the most cells a path may have (default default_horizon(H, W, N)); max_nodes: the budget of tree
+    nodes per case, 1..4096.  Returns a dict of device tensors in plan_prioritized's layout - paths (C,N,horizon,2) int32 padded
+    with each path's last cell, lengths (C,N), goal, start, makespan (C,), solved (C,) uint8 - so that solved_pack,
+    audit_schedules and improve_schedules take it as it is, plus, all (C,) int32:
+      status        0 solved: the schedule is optimal in the flowtime among schedules of at most `horizon` cells per path;
+                    1 the budget ran out; 2 no schedule inside the horizon (or none at all); 3 a start or goal off the map, on an
+                    obstacle or shared by two agents
+      flowtime      sum(lengths - 1) for status 0, otherwise -1
+      lower_bound   status 0: the flowtime; status 1: the cost of the node the search stopped at, the minimum over the open
+                    list; status 2, 3: -1.  A bound of the optimal flowtime where horizon_hit == 0, otherwise of the optimum
+                    over schedules of at most `horizon` cells per path
+      nodes, expanded      tree nodes created (the root included) and nodes that got their two children
+      horizon_hit   1 when a child was dropped because its agent had no arrival inside the horizon, else 0
+    A case that is not solved gets every agent's start cell with length 1, as the planner's failing agents do.
+    Not ECBS: no focal search, and no pruning by an incumbent, disjoint splitting or conflict prioritisation either.
+    Limits: H, W <= 64, horizon <= 256, N <= 4096 - anything else raises MagatNativeError; there is no wide form yet.
+    Stream ordered, no host synchronisation."""
+    start, goal = _dev_i32(start, "start"), _dev_i32(goal, "goal")
+    if not isinstance(obstacle_map, torch.Tensor) or not obstacle_map.is_cuda:
+        raise nat.MagatNativeError("obstacle_map must be a device tensor (no CPU fallback)")
+    m = obstacle_map.to(torch.uint8).contiguous()
+    assert start.dim() == 3 and start.shape[2] == 2 and goal.shape == start.shape, "start and goal must be (C,N,2)"
+    C, N, _ = start.shape
+    assert m.dim() in (2, 3) and (m.dim() == 2 or m.shape[0] == C), "obstacle_map must be (H,W) or (C,H,W)"
+    H, W = m.shape[-2], m.shape[-1]
+    T = default_horizon(H, W, N) if horizon is None else int(horizon)
+    max_nodes = int(max_nodes)
+    _cbs_limits(H, W, T, N, max_nodes)
+    dev = start.device
+    paths = torch.empty(C, N, T, 2, dtype=torch.int32, device=dev)
+    lengths = torch.empty(C, N, dtype=torch.int32, device=dev)
+    solved = torch.empty(C, dtype=torch.uint8, device=dev)
+    extra = torch.empty(7, C, dtype=torch.int32, device=dev)
+    lib = nat.lib()
+    ws = torch.empty(max(int(lib.magat_sim_mapf_cbs_workspace_bytes(C, N, T, max_nodes)), 8), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        nat.check(lib.magat_sim_mapf_cbs(nat.ptr(m), 1 if m.dim() == 3 else 0, H, W, nat.ptr(start), nat.ptr(goal), nat.ptr(paths),
+                                         nat.ptr(lengths), nat.ptr(extra[0]), nat.ptr(solved), nat.ptr(extra[1]), nat.ptr(extra[2]),
+                                         nat.ptr(extra[3]), nat.ptr(extra[4]), nat.ptr(extra[5]), nat.ptr(extra[6]), nat.ptr(ws),
+                                         ws.numel(), C, N, T, max_nodes, nat.current_stream(dev)), "magat_sim_mapf_cbs")
+    return dict(paths=paths, lengths=lengths, goal=goal, start=start, makespan=extra[0], solved=solved, status=extra[1],
+                flowtime=extra[2], lower_bound=extra[3], nodes=extra[4], expanded=extra[5], horizon_hit=extra[6])
+
+
+def solve_cases(obstacle_map, start, goal, horizon=None, retries=8, wide=False, improve=0, optimal=None, certify=None):
     """plan_prioritized in index order, then up to `retries` re-plans of the cases still unsolved, each with that case's
     failed_agent moved to the front of its order.  Returns plan_prioritized's dict (every case holds its LAST plan) plus order
     (C,N) int32 (the order of that plan), rounds (C,) int32 (the plans made for the case, 1 = solved at once) and T =
@@ -273,6 +338,13 @@ def solve_cases(obstacle_map, start, goal, horizon=None, retries=8, wide=False, 
     handed on, so a wide batch is improved by the wide form) - the returned dict
     then also holds flowtime_before, flowtime_after, accepted and status, and T is taken from the improved makespans.  The
     default 0 leaves the result and the calls made as they were.
+    optimal=K (1..4096): cbs_cases(obstacle_map, start, goal, horizon=T, max_nodes=K) on the whole batch, behind the last plan and
+    behind `improve`, before `certify`'s audit.  Where it ends with status 0 its paths, lengths and makespan replace the case's and
+    solved becomes 1 (failed_agent -1); every other case stays as it was.  The returned dict then also holds cbs_status, cbs_bound (the search's
+    lower_bound where horizon_hit == 0, else -1), cbs_nodes (C,) int32 and optimal (C,) bool.  With certify=w as well, certified is
+    taken against max(the audit's flowtime_bound, cbs_bound), and flowtime_bound in the result is that maximum.  Tensor ops only,
+    no added synchronisation; cbs_cases' limits apply (no wide form).  The default None leaves the result and the calls made as
+    they were.  (It stands in front of `certify` in the signature, as in the pipeline.)
     certify=w (a number >= 1): audit_schedules(obstacle_map, res, wide=wide) on the final batch, behind the last plan and
     behind `improve` - the returned dict then also holds the audit's keys (status, fault, dist, flowtime_bound, makespan_bound,
     flowtime; the audit's makespan equals the result's where status is 0 and is not copied) and certified = certified(audit, w),
@@ -281,6 +353,9 @@ def solve_cases(obstacle_map, start, goal, horizon=None, retries=8, wide=False, 
     One host synchronisation per round (the read of `solved`), one more for T."""
     if certify is not None and not float(certify) >= 1.0:
         raise ValueError("solve_cases: certify must be at least 1, not %r" % (certify,))
+    if optimal is not None and isinstance(obstacle_map, torch.Tensor) and obstacle_map.dim() >= 2 and getattr(start, "ndim", 0) == 3:
+        H, W, N = obstacle_map.shape[-2], obstacle_map.shape[-1], start.shape[1]      # refused before anything is planned
+        _cbs_limits(H, W, default_horizon(H, W, N, wide) if horizon is None else int(horizon), N, int(optimal))
     res = plan_prioritized(obstacle_map, start, goal, None, horizon, wide)
     C, N, _ = res["start"].shape
     dev = res["start"].device
@@ -301,8 +376,21 @@ def solve_cases(obstacle_map, start, goal, horizon=None, retries=8, wide=False, 
         rounds.index_add_(0, idx, torch.ones_like(idx, dtype=torch.int32))
     if int(improve) > 0:
         res = improve_schedules(obstacle_map, res, iterations=int(improve), wide=wide)
+    cbs_bound = None
+    if optimal is not None:
+        opt = cbs_cases(obstacle_map, res["start"], res["goal"], horizon=T, max_nodes=int(optimal))
+        done = opt["status"] == 0
+        res = dict(res, paths=torch.where(done[:, None, None, None], opt["paths"], res["paths"]),
+                   lengths=torch.where(done[:, None], opt["lengths"], res["lengths"]),
+                   makespan=torch.where(done, opt["makespan"], res["makespan"]),
+                   solved=torch.where(done, torch.ones_like(res["solved"]), res["solved"]),
+                   failed_agent=torch.where(done, torch.full_like(res["failed_agent"], -1), res["failed_agent"]))
+        cbs_bound = torch.where(opt["horizon_hit"] == 0, opt["lower_bound"], torch.full_like(opt["lower_bound"], -1))
+        res.update(cbs_status=opt["status"], cbs_bound=cbs_bound, cbs_nodes=opt["nodes"], optimal=done)
     if certify is not None:
         audit = audit_schedules(obstacle_map, res, wide=wide)
+        if cbs_bound is not None:
+            audit["flowtime_bound"] = torch.maximum(audit["flowtime_bound"], cbs_bound)
         res.update({key: audit[key] for key in AUDIT_KEYS if key != "makespan"}, certified=certified(audit, certify))
     done = res["makespan"][res["solved"] != 0]
     res.update(order=order, rounds=rounds, T=int(done.max().item()) + 1 if done.numel() else 1)

@@ -18,7 +18,12 @@ chunks whose workspace stays below 1 GiB.
 
 And a third one, "<shape>_audit": audit_schedules (csrc/sim_mapf_audit.hip, for the two wide shapes csrc/sim_mapf_audit_wide.hip
 with wide=True) on solve_cases' result, timed the same way, with what it found: the cases valid / skipped / faulty, the cases
-certified at w = 1, 1.05 and 1.25, and the largest flowtime / bound ratio of the valid ones.  None of these figures is a gate.
+certified at w = 1, 1.05 and 1.25, and the largest flowtime / bound ratio of the valid ones.
+
+The two 64 x 64-form shapes get a fourth one, "<shape>_cbs": cbs_cases (csrc/sim_mapf_cbs.hip, conflict-based search, max_nodes
+= 256) on the same batch, timed the same way, with the share of cases proven optimal, the share that ended at the budget, the
+mean of flowtime / lower_bound - CBS's flowtime where it proved the optimum, else solve_cases' - over the cases that have both,
+and, over the cases CBS proved optimal and solve_cases solved, both total flowtimes.  None of these figures is a gate.
 
     python tools/mapf_bench.py [--restatement K] [--no-device]"""
 import argparse
@@ -127,6 +132,33 @@ def audit_row(sh, d, full, args):
                 flowtime=int(audit["flowtime"][ok].sum()), flowtime_bound=int(audit["flowtime_bound"][ok].sum()))
 
 
+CBS_NODES = 256
+
+
+def cbs_row(sh, d, full, args):
+    import torch
+    from magat_pathplanning_amd import cbs_cases
+    run = lambda: cbs_cases(*d, horizon=sh["T"], max_nodes=CBS_NODES)      # noqa: E731
+    t0 = time.perf_counter()
+    run()
+    torch.cuda.synchronize()
+    slow = time.perf_counter() - t0 > 1.0
+    warmup, calls = (1, min(args.calls, 5)) if slow else (args.warmup, args.calls)
+    ms, opt = timed(run, warmup, calls)
+    proven, solved = opt["status"] == 0, full["solved"] != 0
+    flow = (full["lengths"] - 1).sum(1)
+    both = proven & solved
+    have = (proven | solved) & (opt["lower_bound"] > 0)
+    ratio = torch.where(proven, opt["flowtime"], flow)[have].double() / opt["lower_bound"][have].double()
+    return dict(shape=sh["name"] + "_cbs", cases=sh["C"], agents=sh["N"], T=sh["T"], warmup=warmup, calls=calls, max_nodes=CBS_NODES,
+                cbs_ms_median=ms[len(ms) // 2], cbs_ms_min=ms[0], cbs_ms_max=ms[-1], cbs_us_per_case=ms[len(ms) // 2] * 1e3 / sh["C"],
+                proven_optimal=float(proven.float().mean()), at_budget=float((opt["status"] == 1).float().mean()),
+                no_schedule=float((opt["status"] >= 2).float().mean()), horizon_hit=int((opt["horizon_hit"] != 0).sum()),
+                nodes_mean=float(opt["nodes"].float().mean()), ratio_mean=float(ratio.mean()) if have.any() else None,
+                ratio_cases=int(have.sum()), flowtime_cbs=int(opt["flowtime"][both].sum()), flowtime_solve_cases=int(flow[both].sum()),
+                solved_only_by_cbs=int((proven & ~solved).sum()))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--restatement", type=int, default=0, help="time the Python restatement on this many cases per shape")
@@ -173,6 +205,8 @@ def main():
         if not args.no_device:
             print(json.dumps(improve_row(sh, d, full, args)), flush=True)
             print(json.dumps(audit_row(sh, d, full, args)), flush=True)
+            if not sh.get("wide", False):
+                print(json.dumps(cbs_row(sh, d, full, args)), flush=True)
 
 
 if __name__ == "__main__":
