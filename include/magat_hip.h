@@ -938,8 +938,8 @@ int magat_sim_mapf_audit_wide(const uint8_t* map, int map_batched, int H, int W,
  * 2015) for C cases in one launch, one wavefront per case, every node and every search inside it: optimal in the flowtime and
  * complete up to a budget of nodes, and its open list gives a lower bound of the optimal flowtime.  Deterministic, integer
  * arithmetic only.  Device pointers, stream ordered, no allocation, no synchronisation; one kernel, one count in form
- * "sim_mapf_cbs", one span of its own profiling tag.  No focal search (it is not ECBS), no pruning by an incumbent, no disjoint
- * splitting, no conflict prioritisation.
+ * "sim_mapf_cbs", one span of its own profiling tag.  No focal search (that is magat_sim_mapf_ecbs, below), no pruning by an
+ * incumbent, no disjoint splitting, no conflict prioritisation.
  *
  * map, start, goal, T, paths, lengths, makespan, solved: as in magat_sim_mapf_plan.  The other outputs are (C,) int32.
  * Screening, before any cell indexes anything: a start or goal off the map or on an obstacle, or a start (a goal) that an agent
@@ -981,6 +981,50 @@ int magat_sim_mapf_cbs(const uint8_t* map, int map_batched, int H, int W, const 
                        int32_t* paths /* [C][N][T][2] */, int32_t* lengths, int32_t* makespan, uint8_t* solved, int32_t* status,
                        int32_t* flowtime, int32_t* lower_bound, int32_t* nodes, int32_t* expanded, int32_t* horizon_hit,
                        void* workspace, size_t workspace_bytes, int C, int N, int T, int max_nodes, void* stream);
+
+/* ------------------------------------------------------------------------------------------
+ * A bounded-suboptimal expert: ECBS (Barer et al. 2014), conflict-based search with a focal search on both levels
+ * (sim_mapf_ecbs.hip; added behind ABI 9, nothing above changes).  C cases in one launch, one wavefront per case, as
+ * magat_sim_mapf_cbs; one kernel, one count in form "sim_mapf_ecbs", one span of its own profiling tag.  Deterministic, integer
+ * arithmetic only: w >= 1 comes as w_milli = round(1000 w), every comparison is made in 64 bits.
+ *
+ * Arguments, screening, constraints, outputs and statuses are magat_sim_mapf_cbs's, except that status 0 promises
+ * 1000 * flowtime <= w_milli * lower_bound <= w_milli * optimum, not optimality.  levels = K, 1..4.
+ * Boards.  HARD boards hold the searched agent's constraints, as in CBS.  SOFT boards, a second [T][5][64] set per case, hold the
+ * planner's reservation (V[t] for every t < T, the parked cell included; A_d[t] at the entered cell of a real move) of every
+ * OTHER agent of the schedule the search runs against; they are set before a search and cleared after it.  A step arriving at
+ * t + 1 is DIRTY when its destination is in soft V[t + 1], or it is a real move from u in direction d with u in soft
+ * A_opp(d)[t + 1]; a step that honours the hard and the soft boards is CLEAN.
+ * Low level: K planes P^0 .. P^(K-1) of reachable cells, hard(X) the planner's step on the hard boards, clean(X) the same step on
+ * (hard | soft).  P^k_0 = {start}; P^(K-1)_(t+1) = hard(P^(K-1)_t), the planner's R; P^0_(t+1) = clean(P^0_t); P^k_(t+1) =
+ * clean(P^k_t) | hard(P^(k-1)_t) for 1 <= k <= K - 2: at most k dirty steps.  `last` and t* are the planner's, on plane K - 1 (no
+ * arrival: as there).  The flood goes on to b = min(w_milli * t* / 1000, T - 1), integer division; the arrival is the smallest k
+ * with the goal in P^k_t for a t in [t*, b], then the smallest such t.  The path has t + 1 cells, the agent's bound is t*.
+ * Backtrace from (t, goal, k), candidates up, left, down, right, stop: in plane K - 1 any hard-allowed source in P^(K-1)_(t-1);
+ * in a plane k below it first a source in P^k_(t-1) whose step is clean - none when the cell is in soft V[t], where it can only
+ * stand by a drop - else a hard-allowed source in P^(k-1)_(t-1), and on in plane k - 1.
+ * Root: the agents in index order, agent a against soft boards of agents 0 .. a - 1 and empty hard boards.
+ * Node: parent, cost = sum(lengths - 1), lb = sum(t*), hc, the agent, ONE constraint, that agent's path and t*; a child's cost
+ * and lb are the parent's minus the agent's old length / t* plus its new ones.  hc counts the conflicts of the node's own
+ * schedule over t < max(lengths), own_t[cell] being the smallest agent on a cell at t: the agents a with own_t[cell_a(t)] < a,
+ * and for t >= 1 the agents a that moved, with b = own_(t-1)[cell_a(t)] existing, b > a and cell_b(t) == cell_a(t-1).
+ * Loop: LBmin = the smallest lb over the open list; among the open nodes with 1000 * cost <= w_milli * LBmin (never none) take the
+ * smallest (hc, cost, index).  Its first conflict is the audit's stage 2.  None - status 0, flowtime = cost, lower_bound =
+ * LBmin.  nodes + 2 > max_nodes - status 1, lower_bound = LBmin.  Otherwise two children as in CBS, each searched against soft
+ * boards of the popped node's other agents; a dead child keeps its slot and sets horizon_hit.  An empty open list - status 2.
+ * lower_bound bounds the optimum under CBS's horizon caveat.
+ * workspace: magat_sim_mapf_ecbs_workspace_bytes(C, N, T, max_nodes, levels) = C * 8 * (T * 64 * (10 + levels) + ceil(N * T / 4)
+ * + ceil(max_nodes * T / 4) + 4 * max_nodes + ceil(5 * N / 2)) bytes - per case both sets of boards, the planes, the root's and
+ * the nodes' paths, 32 bytes per node, five int rows of N - 8-byte aligned; the call initialises what it reads.
+ * Limits: those of magat_sim_mapf_cbs, 1 <= levels <= 4 and 1000 <= w_milli <= 2^20.  The checks come in its order: NULL
+ * pointers; non-positive sizes, levels < 1 or w_milli < 1000 (MAGAT_ERR_BAD_SHAPE); the limits, levels > 4, w_milli > 2^20 and
+ * the workspace's size (MAGAT_ERR_UNSUPPORTED); then its alignment.  A refused call launches and counts nothing. */
+size_t magat_sim_mapf_ecbs_workspace_bytes(int C, int N, int T, int max_nodes, int levels);
+int magat_sim_mapf_ecbs(const uint8_t* map, int map_batched, int H, int W, const int32_t* start, const int32_t* goal,
+                        int32_t* paths /* [C][N][T][2] */, int32_t* lengths, int32_t* makespan, uint8_t* solved, int32_t* status,
+                        int32_t* flowtime, int32_t* lower_bound, int32_t* nodes, int32_t* expanded, int32_t* horizon_hit,
+                        void* workspace, size_t workspace_bytes, int C, int N, int T, int max_nodes, int w_milli, int levels,
+                        void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * Planning cases made on the device (sim_cases.hip; added behind ABI 9, nothing above changes): the first step of the expert

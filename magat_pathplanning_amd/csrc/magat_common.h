@@ -46,19 +46,21 @@ void magat_form_note(int id);      // which form a launch took (MAGAT_FORM_*; pr
 #define MAGAT_FORM_SIM_MAPF 18      // magat_sim_mapf_plan launched its one-wave-per-case planning kernel, or magat_sim_cases_generate its generator
 #define MAGAT_FORMS_ALL 19
 // (the two *_ALL counts above end with the solver and stay as they are: host tests pin them.)  Behind them, with a tag and a form
-// of its own each, the schedule improver, the schedule audit and the conflict-based search; the library's tables are sized by the
-// *_TABLE counts.
+// of its own each, the schedule improver, the schedule audit, the conflict-based search and its bounded-suboptimal form; the
+// library's tables are sized by the *_TABLE counts.
 #define MAGAT_TAG_SIM_MAPF_LNS 29   // neighbourhood re-planning of solved schedules (sim_mapf_lns.hip)
 #define MAGAT_TAG_SIM_MAPF_AUDIT 30 // the audit of schedules: conflicts and the flowtime bound (sim_mapf_audit.hip, sim_mapf_audit_wide.hip)
 #define MAGAT_TAG_SIM_MAPF_CBS 31   // conflict-based search: the optimal expert (sim_mapf_cbs.hip)
-#define MAGAT_PROF_TAGS_TABLE 32
+#define MAGAT_TAG_SIM_MAPF_ECBS 32  // bounded-suboptimal conflict-based search: focal search on both levels (sim_mapf_ecbs.hip)
+#define MAGAT_PROF_TAGS_TABLE 33
 #define MAGAT_FORM_SIM_MAPF_LNS 19  // magat_sim_mapf_improve launched its one-wave-per-case kernel
 #define MAGAT_FORM_SIM_MAPF_AUDIT 20  // magat_sim_mapf_audit or its wide form launched (one count per call)
 #define MAGAT_FORM_SIM_MAPF_CBS 21    // magat_sim_mapf_cbs launched its one-wave-per-case kernel
-#define MAGAT_FORMS_TABLE 22
+#define MAGAT_FORM_SIM_MAPF_ECBS 22   // magat_sim_mapf_ecbs launched its one-wave-per-case kernel
+#define MAGAT_FORMS_TABLE 23
 static_assert(MAGAT_PROF_TAGS_ALL >= MAGAT_PROF_TAGS && MAGAT_FORMS_ALL >= MAGAT_FORMS, "internal tag / form tables");
-static_assert(MAGAT_PROF_TAGS_TABLE > MAGAT_TAG_SIM_MAPF_CBS && MAGAT_PROF_TAGS_TABLE >= MAGAT_PROF_TAGS_ALL &&
-              MAGAT_FORMS_TABLE > MAGAT_FORM_SIM_MAPF_CBS && MAGAT_FORMS_TABLE >= MAGAT_FORMS_ALL, "internal tag / form tables");
+static_assert(MAGAT_PROF_TAGS_TABLE > MAGAT_TAG_SIM_MAPF_ECBS && MAGAT_PROF_TAGS_TABLE >= MAGAT_PROF_TAGS_ALL &&
+              MAGAT_FORMS_TABLE > MAGAT_FORM_SIM_MAPF_ECBS && MAGAT_FORMS_TABLE >= MAGAT_FORMS_ALL, "internal tag / form tables");
 
 // bf16x6 split-MFMA GEMM (conv_gemm_bf16x6.hip), reached through magat_conv_gemm_f32 when desc->in_fmt == 1
 int magat_conv_gemm_bf16x6(const magat_conv_gemm_desc* d, hipStream_t st);

@@ -2,8 +2,9 @@
 schedules into training samples), for C cases at once.  The reference calls pre-built ecbs / cbs / sipp binaries, one
 subprocess per case (onlineExpert/ECBS_onlineExpert.py:81-104); this is prioritized planning with an exact space-time search
 per agent (csrc/sim_mapf.hip).  The planner is NOT ECBS: it gives no bound on the flowtime, and it is incomplete - a
-case can fail in one priority order and succeed in another, or stay unsolved.  Behind it stands an optimal solver that is
-complete up to a node budget, conflict-based search (cbs_cases, csrc/sim_mapf_cbs.hip; solve_cases(..., optimal=K)) - see below.
+case can fail in one priority order and succeed in another, or stay unsolved.  Behind it stand an optimal solver that is
+complete up to a node budget, conflict-based search (cbs_cases, csrc/sim_mapf_cbs.hip; solve_cases(..., optimal=K)), and ECBS
+itself, its bounded-suboptimal form (ecbs_cases, csrc/sim_mapf_ecbs.hip; solve_cases(..., bounded=w)) - see below.
 
     res = solve_cases(obstacle_map, start, goal)                          # plans, re-plans the unsolved cases in a new order
     pack = solved_pack(res)                                               # the solved cases, as pack_schedules lays them out
@@ -43,10 +44,18 @@ lower bound of the optimal flowtime - a much tighter denominator for `certified`
     opt = cbs_cases(obstacle_map, start, goal, max_nodes=256)             # status, flowtime, lower_bound, nodes, expanded, horizon_hit
     res = solve_cases(obstacle_map, start, goal, optimal=256, certify=1.0)      # the planner's schedule unless CBS proved an optimum
 
+CBS proves optima and therefore runs out of its budget on anything crowded.  ecbs_cases (csrc/sim_mapf_ecbs.hip) is ECBS(w): the
+same tree with a focal search on both levels - the low level prefers paths that break few of the other agents' reservations among
+those at most w times the shortest, the high level takes the node with the fewest conflicts among those whose cost is within w of
+the smallest bound of the open list.  A solved case promises flowtime <= w * lower_bound <= w * optimum.
+
+    sub = ecbs_cases(obstacle_map, start, goal, w=1.5, max_nodes=256)           # cbs_cases' keys
+    res = solve_cases(obstacle_map, start, goal, bounded=1.5, certify=1.5)      # ECBS's schedule where it is the better one
+
 Maps above 64 x 64 and horizons above 256 are opt-in everywhere: plan_prioritized, solve_cases, improve_schedules and
 audit_schedules take wide=True (csrc/sim_mapf_wide.hip, csrc/sim_mapf_lns_wide.hip, csrc/sim_mapf_audit_wide.hip: maps up to
 256 x 256, horizons up to 1024), and solve_cases(..., wide=True, improve=I, certify=w) hands it on; without it such shapes raise
-MagatNativeError as before.  cbs_cases has no wide form yet: it refuses such shapes with or without wide=True.
+MagatNativeError as before.  cbs_cases and ecbs_cases have no wide form yet: they refuse such shapes with or without wide=True.
 
 HIP only: CPU tensors raise MagatNativeError.  plan_prioritized is stream ordered and never waits for the device;
 solve_cases reads `solved` back once per round."""
@@ -62,7 +71,9 @@ WIDE_MAX_SIDE = 256
 PACK_KEYS = ("paths", "lengths", "goal", "start", "makespan")
 MAX_AGENTS_AUDIT = 4096      # audit_schedules: agents per case
 AUDIT_KEYS = ("status", "fault", "dist", "flowtime_bound", "makespan_bound", "flowtime", "makespan")
-MAX_NODES_CBS = 4096         # cbs_cases: nodes per case
+MAX_NODES_CBS = 4096         # cbs_cases, ecbs_cases: nodes per case
+MAX_LEVELS_ECBS = 4          # ecbs_cases: planes of the low-level focal search
+MAX_W_MILLI_ECBS = 1 << 20   # ecbs_cases: round(1000 w)
 
 
 def default_horizon(H, W, N, wide=False):
@@ -292,7 +303,7 @@ def cbs_cases(obstacle_map, start, goal, horizon=None, max_nodes=256):
       nodes, expanded      tree nodes created (the root included) and nodes that got their two children
       horizon_hit   1 when a child was dropped because its agent had no arrival inside the horizon, else 0
     A case that is not solved gets every agent's start cell with length 1, as the planner's failing agents do.
-    Not ECBS: no focal search, and no pruning by an incumbent, disjoint splitting or conflict prioritisation either.
+    No focal search (that is ecbs_cases), and no pruning by an incumbent, disjoint splitting or conflict prioritisation either.
     Limits: H, W <= 64, horizon <= 256, N <= 4096 - anything else raises MagatNativeError; there is no wide form yet.
     Stream ordered, no host synchronisation."""
     start, goal = _dev_i32(start, "start"), _dev_i32(goal, "goal")
@@ -322,7 +333,69 @@ def cbs_cases(obstacle_map, start, goal, horizon=None, max_nodes=256):
                 flowtime=extra[2], lower_bound=extra[3], nodes=extra[4], expanded=extra[5], horizon_hit=extra[6])
 
 
-def solve_cases(obstacle_map, start, goal, horizon=None, retries=8, wide=False, improve=0, optimal=None, certify=None):
+def _w_milli(w, who):
+    if not float(w) >= 1.0:
+        raise ValueError("%s: w must be at least 1, not %r" % (who, w))
+    w_milli = int(round(1000.0 * float(w)))
+    if w_milli > MAX_W_MILLI_ECBS:
+        raise ValueError("%s: w must be at most %g, not %r" % (who, MAX_W_MILLI_ECBS / 1000.0, w))
+    return w_milli
+
+
+def _ecbs_limits(H, W, T, N, max_nodes, levels):
+    if (H > MAX_SIDE or W > MAX_SIDE or T > MAX_HORIZON or N > MAX_AGENTS_AUDIT or not 1 <= max_nodes <= MAX_NODES_CBS
+            or not 1 <= levels <= MAX_LEVELS_ECBS):
+        raise nat.MagatNativeError("ecbs_cases takes maps up to %d x %d, horizons up to %d, %d agents, 1..%d nodes per case and 1..%d "
+                                   "levels, not %d x %d / %d / %d / %d / %d (it has no wide form)"
+                                   % (MAX_SIDE, MAX_SIDE, MAX_HORIZON, MAX_AGENTS_AUDIT, MAX_NODES_CBS, MAX_LEVELS_ECBS, H, W, T, N,
+                                      max_nodes, levels))
+
+
+def ecbs_cases(obstacle_map, start, goal, w=1.5, horizon=None, max_nodes=256, levels=4):
+    """One call of magat_sim_mapf_ecbs: ECBS(w) - conflict-based search with a focal search on both levels - on every case, one
+    wavefront per case, all nodes and searches in one launch (the rule is in include/magat_hip.h and DESIGN 4.11).  Arguments as
+    cbs_cases, plus w >= 1, the suboptimality factor (handed to the device as round(1000 w); every comparison is integer
+    arithmetic), and levels, 1..4: the planes of the low-level focal search - the last one is the planner's own search, plane k
+    below it holds the cells reached with at most k steps that break another agent's reservation; levels=1 leaves the focal
+    choice to the high level alone.  Returns cbs_cases' dict, the same keys with the same meanings, except
+      status 0      the schedule is valid and flowtime <= w * lower_bound <= w * optimum (1000 * flowtime <= w_milli *
+                    lower_bound on the device) - it is not proven optimal unless w == 1
+      lower_bound   status 0 and 1: the smallest bound over the open list, a lower bound of the optimal flowtime under
+                    cbs_cases' horizon caveat; status 2, 3: -1
+    so solved_pack, audit_schedules and improve_schedules take it as it is.
+    Limits: H, W <= 64, horizon <= 256, N <= 4096, max_nodes and levels as above - anything else raises MagatNativeError, a w
+    below 1 or above 1048.576 ValueError; there is no wide form yet.  Stream ordered, no host synchronisation."""
+    w_milli = _w_milli(w, "ecbs_cases")
+    start, goal = _dev_i32(start, "start"), _dev_i32(goal, "goal")
+    if not isinstance(obstacle_map, torch.Tensor) or not obstacle_map.is_cuda:
+        raise nat.MagatNativeError("obstacle_map must be a device tensor (no CPU fallback)")
+    m = obstacle_map.to(torch.uint8).contiguous()
+    assert start.dim() == 3 and start.shape[2] == 2 and goal.shape == start.shape, "start and goal must be (C,N,2)"
+    C, N, _ = start.shape
+    assert m.dim() in (2, 3) and (m.dim() == 2 or m.shape[0] == C), "obstacle_map must be (H,W) or (C,H,W)"
+    H, W = m.shape[-2], m.shape[-1]
+    T = default_horizon(H, W, N) if horizon is None else int(horizon)
+    max_nodes, levels = int(max_nodes), int(levels)
+    _ecbs_limits(H, W, T, N, max_nodes, levels)
+    dev = start.device
+    paths = torch.empty(C, N, T, 2, dtype=torch.int32, device=dev)
+    lengths = torch.empty(C, N, dtype=torch.int32, device=dev)
+    solved = torch.empty(C, dtype=torch.uint8, device=dev)
+    extra = torch.empty(7, C, dtype=torch.int32, device=dev)
+    lib = nat.lib()
+    ws = torch.empty(max(int(lib.magat_sim_mapf_ecbs_workspace_bytes(C, N, T, max_nodes, levels)), 8), dtype=torch.uint8, device=dev)
+    with torch.cuda.device(dev):
+        nat.check(lib.magat_sim_mapf_ecbs(nat.ptr(m), 1 if m.dim() == 3 else 0, H, W, nat.ptr(start), nat.ptr(goal), nat.ptr(paths),
+                                          nat.ptr(lengths), nat.ptr(extra[0]), nat.ptr(solved), nat.ptr(extra[1]), nat.ptr(extra[2]),
+                                          nat.ptr(extra[3]), nat.ptr(extra[4]), nat.ptr(extra[5]), nat.ptr(extra[6]), nat.ptr(ws),
+                                          ws.numel(), C, N, T, max_nodes, w_milli, levels, nat.current_stream(dev)),
+                  "magat_sim_mapf_ecbs")
+    return dict(paths=paths, lengths=lengths, goal=goal, start=start, makespan=extra[0], solved=solved, status=extra[1],
+                flowtime=extra[2], lower_bound=extra[3], nodes=extra[4], expanded=extra[5], horizon_hit=extra[6])
+
+
+def solve_cases(obstacle_map, start, goal, horizon=None, retries=8, wide=False, improve=0, optimal=None, bounded=None, bounded_nodes=256,
+                certify=None):
     """plan_prioritized in index order, then up to `retries` re-plans of the cases still unsolved, each with that case's
     failed_agent moved to the front of its order.  Returns plan_prioritized's dict (every case holds its LAST plan) plus order
     (C,N) int32 (the order of that plan), rounds (C,) int32 (the plans made for the case, 1 = solved at once) and T =
@@ -345,6 +418,13 @@ def solve_cases(obstacle_map, start, goal, horizon=None, retries=8, wide=False, 
     taken against max(the audit's flowtime_bound, cbs_bound), and flowtime_bound in the result is that maximum.  Tensor ops only,
     no added synchronisation; cbs_cases' limits apply (no wide form).  The default None leaves the result and the calls made as
     they were.  (It stands in front of `certify` in the signature, as in the pipeline.)
+    bounded=w (a number >= 1; not together with `optimal`: ValueError): ecbs_cases(obstacle_map, start, goal, w, horizon=T,
+    max_nodes=bounded_nodes) where `optimal` would run cbs_cases.  Where it ends with status 0 AND the case's plan is unsolved or
+    has a larger flowtime, its paths, lengths and makespan replace the case's and solved becomes 1 (failed_agent -1).  The returned
+    dict then also holds ecbs_status, ecbs_bound (the search's lower_bound where horizon_hit == 0, else -1), ecbs_nodes (C,) int32
+    and bounded (C,) bool (status 0: flowtime <= w * ecbs_bound holds for the case's schedule).  With certify as well,
+    flowtime_bound = max(the audit's bound, ecbs_bound).  ecbs_cases' limits apply and are checked before anything is planned.
+    The default None leaves the result and the calls made as they were.
     certify=w (a number >= 1): audit_schedules(obstacle_map, res, wide=wide) on the final batch, behind the last plan and
     behind `improve` - the returned dict then also holds the audit's keys (status, fault, dist, flowtime_bound, makespan_bound,
     flowtime; the audit's makespan equals the result's where status is 0 and is not copied) and certified = certified(audit, w),
@@ -353,6 +433,13 @@ def solve_cases(obstacle_map, start, goal, horizon=None, retries=8, wide=False, 
     One host synchronisation per round (the read of `solved`), one more for T."""
     if certify is not None and not float(certify) >= 1.0:
         raise ValueError("solve_cases: certify must be at least 1, not %r" % (certify,))
+    if bounded is not None:
+        if optimal is not None:
+            raise ValueError("solve_cases: bounded and optimal exclude each other")
+        _w_milli(bounded, "solve_cases(bounded=)")
+        if isinstance(obstacle_map, torch.Tensor) and obstacle_map.dim() >= 2 and getattr(start, "ndim", 0) == 3:
+            H, W, N = obstacle_map.shape[-2], obstacle_map.shape[-1], start.shape[1]      # refused before anything is planned
+            _ecbs_limits(H, W, default_horizon(H, W, N, wide) if horizon is None else int(horizon), N, int(bounded_nodes), MAX_LEVELS_ECBS)
     if optimal is not None and isinstance(obstacle_map, torch.Tensor) and obstacle_map.dim() >= 2 and getattr(start, "ndim", 0) == 3:
         H, W, N = obstacle_map.shape[-2], obstacle_map.shape[-1], start.shape[1]      # refused before anything is planned
         _cbs_limits(H, W, default_horizon(H, W, N, wide) if horizon is None else int(horizon), N, int(optimal))
@@ -387,6 +474,17 @@ def solve_cases(obstacle_map, start, goal, horizon=None, retries=8, wide=False, 
                    failed_agent=torch.where(done, torch.full_like(res["failed_agent"], -1), res["failed_agent"]))
         cbs_bound = torch.where(opt["horizon_hit"] == 0, opt["lower_bound"], torch.full_like(opt["lower_bound"], -1))
         res.update(cbs_status=opt["status"], cbs_bound=cbs_bound, cbs_nodes=opt["nodes"], optimal=done)
+    if bounded is not None:
+        sub = ecbs_cases(obstacle_map, res["start"], res["goal"], w=bounded, horizon=T, max_nodes=int(bounded_nodes))
+        done = sub["status"] == 0
+        take = done & ((res["solved"] == 0) | ((res["lengths"] - 1).sum(1) > sub["flowtime"]))
+        res = dict(res, paths=torch.where(take[:, None, None, None], sub["paths"], res["paths"]),
+                   lengths=torch.where(take[:, None], sub["lengths"], res["lengths"]),
+                   makespan=torch.where(take, sub["makespan"], res["makespan"]),
+                   solved=torch.where(take, torch.ones_like(res["solved"]), res["solved"]),
+                   failed_agent=torch.where(take, torch.full_like(res["failed_agent"], -1), res["failed_agent"]))
+        cbs_bound = torch.where(sub["horizon_hit"] == 0, sub["lower_bound"], torch.full_like(sub["lower_bound"], -1))
+        res.update(ecbs_status=sub["status"], ecbs_bound=cbs_bound, ecbs_nodes=sub["nodes"], bounded=done)
     if certify is not None:
         audit = audit_schedules(obstacle_map, res, wide=wide)
         if cbs_bound is not None:

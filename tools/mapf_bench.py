@@ -23,7 +23,10 @@ certified at w = 1, 1.05 and 1.25, and the largest flowtime / bound ratio of the
 The two 64 x 64-form shapes get a fourth one, "<shape>_cbs": cbs_cases (csrc/sim_mapf_cbs.hip, conflict-based search, max_nodes
 = 256) on the same batch, timed the same way, with the share of cases proven optimal, the share that ended at the budget, the
 mean of flowtime / lower_bound - CBS's flowtime where it proved the optimum, else solve_cases' - over the cases that have both,
-and, over the cases CBS proved optimal and solve_cases solved, both total flowtimes.  None of these figures is a gate.
+and, over the cases CBS proved optimal and solve_cases solved, both total flowtimes.  Beside it stands "<shape>_ecbs": ecbs_cases
+(csrc/sim_mapf_ecbs.hip, ECBS with w = 1.5, max_nodes = 256, 4 levels) on the same batch, timed the same way: the time per call,
+the share of cases solved, the mean of flowtime / lower_bound over them, and its total flowtime against solve_cases' (over the cases
+both solved) and against CBS's (over the cases CBS proved optimal).  None of these figures is a gate.
 
     python tools/mapf_bench.py [--restatement K] [--no-device]"""
 import argparse
@@ -159,6 +162,35 @@ def cbs_row(sh, d, full, args):
                 solved_only_by_cbs=int((proven & ~solved).sum()))
 
 
+ECBS = dict(w=1.5, max_nodes=256, levels=4)
+
+
+def ecbs_row(sh, d, full, args):
+    import torch
+    from magat_pathplanning_amd import cbs_cases, ecbs_cases
+    run = lambda: ecbs_cases(*d, horizon=sh["T"], **ECBS)      # noqa: E731
+    t0 = time.perf_counter()
+    run()
+    torch.cuda.synchronize()
+    slow = time.perf_counter() - t0 > 1.0
+    warmup, calls = (1, min(args.calls, 5)) if slow else (args.warmup, args.calls)
+    ms, sub = timed(run, warmup, calls)
+    opt = cbs_cases(*d, horizon=sh["T"], max_nodes=CBS_NODES)      # (not timed here: the _cbs row does)
+    done, solved, proven = sub["status"] == 0, full["solved"] != 0, opt["status"] == 0
+    flow = (full["lengths"] - 1).sum(1)
+    have = done & (sub["lower_bound"] > 0)
+    ratio = sub["flowtime"][have].double() / sub["lower_bound"][have].double()
+    return dict(shape=sh["name"] + "_ecbs", cases=sh["C"], agents=sh["N"], T=sh["T"], warmup=warmup, calls=calls, **ECBS,
+                ecbs_ms_median=ms[len(ms) // 2], ecbs_ms_min=ms[0], ecbs_ms_max=ms[-1], ecbs_us_per_case=ms[len(ms) // 2] * 1e3 / sh["C"],
+                solved=float(done.float().mean()), at_budget=float((sub["status"] == 1).float().mean()),
+                no_schedule=float((sub["status"] >= 2).float().mean()), horizon_hit=int((sub["horizon_hit"] != 0).sum()),
+                nodes_mean=float(sub["nodes"].float().mean()), ratio_mean=float(ratio.mean()) if have.any() else None,
+                ratio_max=float(ratio.max()) if have.any() else None,
+                flowtime_ecbs_vs_solve_cases=[int(sub["flowtime"][done & solved].sum()), int(flow[done & solved].sum())],
+                flowtime_ecbs_vs_cbs=[int(sub["flowtime"][done & proven].sum()), int(opt["flowtime"][done & proven].sum())],
+                solved_only_by_ecbs=int((done & ~solved).sum()), solved_by_ecbs_not_proven_by_cbs=int((done & ~proven).sum()))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--restatement", type=int, default=0, help="time the Python restatement on this many cases per shape")
@@ -207,6 +239,7 @@ def main():
             print(json.dumps(audit_row(sh, d, full, args)), flush=True)
             if not sh.get("wide", False):
                 print(json.dumps(cbs_row(sh, d, full, args)), flush=True)
+                print(json.dumps(ecbs_row(sh, d, full, args)), flush=True)
 
 
 if __name__ == "__main__":
