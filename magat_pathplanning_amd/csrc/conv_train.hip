@@ -130,7 +130,8 @@ static void wgrad_chunks(int M, int Cin, int Cout, int kH, int kW, int npix, int
 }
 
 size_t magat_conv_wgrad_workspace_floats(int M, int Cin, int cin_w, int Cout, int kH, int kW, int npix) {
-  if (M <= 0 || Cin <= 0 || Cout <= 0 || kH <= 0 || kW <= 0 || npix <= 0 || cin_w <= 0) return 0;
+  // (the shapes magat_conv_wgrad_f32 refuses need no workspace; Cout < 32 would leave wgrad_chunks without a single wave)
+  if (M <= 0 || Cin <= 0 || Cout <= 0 || Cout % 32 || kH <= 0 || kW <= 0 || npix <= 0 || cin_w <= 0 || cin_w > Cin) return 0;
   int cm, mc, cpix, pc;
   wgrad_chunks(M, Cin, Cout, kH, kW, npix, &cm, &mc, &cpix, &pc);
   return (size_t)cm * cpix * Cout * kH * kW * cin_w;

@@ -1,7 +1,9 @@
 """Training of the per-agent CNN on the HIP convolution kernels (train_cnn.py, csrc/conv_train.hip) against torch's own
 float64 autograd of the same layers on the CPU: convolution forward / input gradient / weight gradient at every geometry the
 ResNet trunks use, the whole trunk in training mode (batch-statistics BatchNorm, running-stat updates), and a training step of
-the planner with either convolution backend."""
+the planner with either convolution backend.  At these shapes (37 ... 150 agents, BatchNorm inputs up to 23 040 x 128) the weight
+gradient takes one output pixel per wave and no BatchNorm grid is capped; the splits of training-size batches are in
+tests/test_gpu_train_cnn_shapes.py."""
 import copy
 
 import numpy as np
