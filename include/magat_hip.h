@@ -233,7 +233,9 @@ int magat_gnn_backward_csr_f32(const float* dY, const int* rowptr, const int* co
  *   getGSO :301-321): pos [B][N][2] int32 (row, col) -> S [B][N][N] float32|float64,  W = (euclidean distance < R) with zero
  *   diagonal, optional D^-1/2 W D^-1/2 (config.symmetric_norm), then W / lambda_max(W) when `normalize` (an edgeless
  *   instance stays zero).  Edge structure is bit-exact; lambda_max (-> lambda_out [B], may be NULL) comes from Lanczos +
- *   Sturm bisection in float64 (the reference: numpy.linalg.eigvalsh on the host), values agree to ~1e-12 relative.
+ *   Sturm bisection in float64 (the reference: numpy.linalg.eigvalsh on the host), values agree to ~1e-12 relative: the walk
+ *   takes up to N steps, until the largest Ritz value stands still.  N <= 2048 (otherwise MAGAT_ERR_UNSUPPORTED, nothing is
+ *   launched); up to 960 agents the rows of W sit in LDS as bit masks, above that the distance test is evaluated on the fly.
  *   magat_sim_gso_radii: the same with one radius per instance (radii [B] float64 on the device).
  * magat_sim_connect_radius: the step-0 branch of computeAdjacencyMatrix (:759-768): r = R / 1.1, then r *= 1.1 until the
  *   graph (distance < r) is connected - the radius the episode keeps.  radii_out [B] float64 (the same float64 products as

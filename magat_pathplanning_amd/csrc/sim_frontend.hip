@@ -204,8 +204,13 @@ __device__ double gso_lambda_wave(const unsigned* rows, int words, const double*
   return lam;
 }
 
-// rows of W as bit masks in LDS while they fit (N <= ~1000: 128 KB); larger instances evaluate the distance test on
-// the fly (N <= 2048)
+// Lanczos steps an instance may take: as many as it has agents (T is then complete in exact arithmetic, as on the one-wave path),
+// and never fewer than the 160 rows the one-wave path's alpha / b2 are laid out for.  Storage: alpha [cap], beta [cap + 2].
+constexpr int GSO_LMIN = 160;
+__host__ __device__ inline int gso_lanczos_cap(int N) { return N > GSO_LMIN ? N : GSO_LMIN; }
+
+// rows of W as bit masks in LDS while they fit (N <= 960: 48 N bytes of vectors and tridiagonal, 4 N ceil(N / 32) of rows); larger
+// instances evaluate the distance test on the fly (N <= 2048)
 template <bool MASK>
 __global__ __launch_bounds__(SIM_THREADS) void gso_kernel(const int* __restrict__ pos, double Rscalar,
                                                           const double* __restrict__ radii, int symmetric_norm,
@@ -220,8 +225,9 @@ __global__ __launch_bounds__(SIM_THREADS) void gso_kernel(const int* __restrict_
   double* v = reinterpret_cast<double*>(py + N + ((2 * N) & 1));      // 8-byte aligned
   double* y = v + N;
   double* inv = y + N;
-  double* red = inv + N;                                             // [16] wave partials, then [160] alpha, [161] beta
-  unsigned* rows = reinterpret_cast<unsigned*>(red + 16 + 160 + 162);   // [N][words]   (MASK only)
+  const int cap = gso_lanczos_cap(N);
+  double* red = inv + N;                                             // [16] wave partials, then [cap] alpha, [cap + 2] beta
+  unsigned* rows = reinterpret_cast<unsigned*>(red + 16 + 2 * cap + 2);   // [N][words]   (MASK only)
   __shared__ int any_edge;
   if (t == 0) any_edge = 0;
   for (int n = t; n < N; n += nt) {
@@ -269,7 +275,7 @@ __global__ __launch_bounds__(SIM_THREADS) void gso_kernel(const int* __restrict_
   if (has_edges && normalize && MASK && N <= 128) {
     // small graphs: the whole eigenvalue problem inside wave 0 (gso_lambda_wave), the other waves wait at the barrier
     double* alpha = red + 16;
-    double* b2 = alpha + 160;
+    double* b2 = alpha + GSO_LMIN;      // (cap == GSO_LMIN here)
     double* u = reinterpret_cast<double*>(rows + ((N * words + 1) & ~1));      // [N + 1]
     unsigned* nbr = reinterpret_cast<unsigned*>(u + N + 1);                    // [N][gso_nbr_words(N)]
     if (t < 64) lam = gso_lambda_wave(rows, words, inv, u, nbr, alpha, b2, N, t);
@@ -281,7 +287,12 @@ __global__ __launch_bounds__(SIM_THREADS) void gso_kernel(const int* __restrict_
     // converges first and stays put).  The all-ones start has a component along the Perron vector of every connected
     // component, so the largest Ritz value tends to lambda_max(W) = max over components.  Every LCHK steps the largest
     // eigenvalue of the tridiagonal T_k is located by Sturm bisection; stop when it no longer moves.
-    constexpr int LMAX = 160, LCHK = 8;
+    // The walk goes on until that rule is met, up to N steps: 160 steps left 3e-6 of lambda_max on a path of 1000 agents and 7e-10 on
+    // 960 uniform random agents under the symmetric normalisation (the gate is 1e-9; tests/gso_lanczos_restatement.py is this
+    // rule in numpy).  A location costs O(steps), so past 160 steps they thin out: every 32 steps, then every eighth of the
+    // largest power of two below the step count.
+    constexpr int LCHK = 8;
+    const int LMAX = cap;
     double* alpha = red + 16;            // [LMAX]
     double* beta = alpha + LMAX;         // [LMAX + 1]   beta[k] couples v_{k-1} and v_k
     // v = ones / sqrt(N), v_prev = 0   (y holds v_prev, inv stays the D^-1/2 scaling)
@@ -338,7 +349,12 @@ __global__ __launch_bounds__(SIM_THREADS) void gso_kernel(const int* __restrict_
       if (!breakdown)
         for (int i = t; i < N; i += nt, ++q) v[i] = wloc[q] / bn;
       __syncthreads();
-      if (breakdown || (steps % LCHK) == 0 || steps == LMAX || steps >= N) {
+      int chk = LCHK;
+      if (steps > GSO_LMIN) {
+        chk = (1 << (31 - __clz(steps))) >> 3;
+        if (chk < 32) chk = 32;
+      }
+      if (breakdown || (steps % chk) == 0 || steps == LMAX || steps >= N) {
         // largest eigenvalue of T_steps (alpha[0..steps), beta[1..steps)) by multisection on the Sturm count: every
         // thread probes its own abscissa inside [lo, hi], the interval shrinks (nt + 1)-fold per pass
         double lo = alpha[0], hi = alpha[0];
@@ -396,7 +412,7 @@ __global__ __launch_bounds__(SIM_THREADS) void gso_kernel(const int* __restrict_
 }
 
 size_t gso_lds_bytes(int N, bool mask) {
-  size_t b = (size_t)2 * N * sizeof(int) + 8 + (size_t)3 * N * sizeof(double) + (16 + 160 + 162) * sizeof(double);
+  size_t b = (size_t)2 * N * sizeof(int) + 8 + (size_t)3 * N * sizeof(double) + (16 + 2 * (size_t)gso_lanczos_cap(N) + 2) * sizeof(double);
   if (mask) b += (size_t)N * ((N + 31) / 32) * sizeof(unsigned);
   if (mask && N <= 128)      // the one-wave eigenvalue path: u [N + 1] doubles and the neighbour lists
     b += sizeof(unsigned) + (size_t)(N + 1) * sizeof(double) + (size_t)N * gso_nbr_words(N) * sizeof(unsigned);
@@ -739,7 +755,7 @@ int sim_gso_launch(const int32_t* pos, double comm_radius, const double* radii, 
   if (!pos || !S) return MAGAT_ERR_NULL;
   if (B <= 0 || N <= 0 || (!radii && !(comm_radius > 0.0))) return MAGAT_ERR_BAD_SHAPE;
   if (N > 2048) return MAGAT_ERR_UNSUPPORTED;
-  const bool mask = gso_lds_bytes(N, true) <= 160 * 1024;          // bit rows of W in LDS (N <= ~1000), else on the fly
+  const bool mask = gso_lds_bytes(N, true) <= 160 * 1024;          // bit rows of W in LDS (N <= 960), else on the fly
   const size_t lds = gso_lds_bytes(N, mask);
   if (lds > 160 * 1024) return MAGAT_ERR_UNSUPPORTED;
   hipStream_t st = static_cast<hipStream_t>(stream);

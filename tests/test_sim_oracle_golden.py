@@ -13,7 +13,7 @@ SIM = sorted(glob.glob(os.path.join(GOLDEN, "sim_*.npz")))
 
 
 def test_sim_fixture_inventory():
-    assert len(SIM) == 5
+    assert len(SIM) == 11      # five at the reference's default shape; four non-square maps at FOV 5 / 7 / 9 / 11; the goal rose at FOV 9 and 13
 
 
 @pytest.mark.parametrize("path", SIM, ids=[os.path.basename(p)[:-4] for p in SIM])
