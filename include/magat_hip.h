@@ -1028,6 +1028,25 @@ int magat_sim_mapf_ecbs(const uint8_t* map, int map_batched, int H, int W, const
                         void* workspace, size_t workspace_bytes, int C, int N, int T, int max_nodes, int w_milli, int levels,
                         void* stream);
 
+/* The wide form of magat_sim_mapf_ecbs (sim_mapf_ecbs_wide.hip; added behind ABI 9, nothing above changes): the same rule, cell
+ * for cell and node for node, the same arguments, outputs and statuses, on maps up to 256 x 256 with horizons up to 1024.  One
+ * workgroup of rows = 64 * ceil(H / 64) threads per case, thread = map row, words = 1, 2 or 4 64-bit words per row (the smallest
+ * with 64 * words >= W), as magat_sim_mapf_plan_wide; one kernel, counted in the narrow form's "sim_mapf_ecbs" and one span of its
+ * profiling tag.  The cell-owner grids of the conflict scan and the conflict count live in the workspace, not in LDS.
+ * workspace: magat_sim_mapf_ecbs_wide_workspace_bytes(C, H, W, N, T, max_nodes, levels) = C * 8 * (T * rows * words * (10 + levels)
+ * + ceil(N * T / 4) + ceil(max_nodes * T / 4) + 4 * max_nodes + ceil(5 * N / 2) + H * W) bytes - per case both sets of boards
+ * [T][5][rows][words], the planes [levels][T][rows][words], the root's and the nodes' paths, 32 bytes per node, five int rows of N
+ * and the two grids of H * W ints - 8-byte aligned; the call initialises what it reads.  0 outside the limits.
+ * Limits: H, W <= 256, T <= 1024, N <= 4096, max_nodes <= 4096, 1 <= levels <= 4, 1000 <= w_milli <= 2^20.  The checks come in
+ * magat_sim_mapf_ecbs's order: NULL pointers; non-positive sizes, levels < 1 or w_milli < 1000 (MAGAT_ERR_BAD_SHAPE); the limits
+ * and the workspace's size (MAGAT_ERR_UNSUPPORTED); then its alignment.  A refused call launches and counts nothing. */
+size_t magat_sim_mapf_ecbs_wide_workspace_bytes(int C, int H, int W, int N, int T, int max_nodes, int levels);
+int magat_sim_mapf_ecbs_wide(const uint8_t* map, int map_batched, int H, int W, const int32_t* start, const int32_t* goal,
+                             int32_t* paths /* [C][N][T][2] */, int32_t* lengths, int32_t* makespan, uint8_t* solved, int32_t* status,
+                             int32_t* flowtime, int32_t* lower_bound, int32_t* nodes, int32_t* expanded, int32_t* horizon_hit,
+                             void* workspace, size_t workspace_bytes, int C, int N, int T, int max_nodes, int w_milli, int levels,
+                             void* stream);
+
 /* ------------------------------------------------------------------------------------------
  * Planning cases made on the device (sim_cases.hip; added behind ABI 9, nothing above changes): the first step of the expert
  * pipeline, the reference's offlineExpert/CasesGenerator.py - an obstacle map, its largest free component, a start and a goal

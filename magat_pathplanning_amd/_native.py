@@ -174,6 +174,8 @@ _SIGNATURES = {
     "magat_sim_mapf_cbs": (_I, [_P, _I, _I, _I] + [_P] * 13 + [_Z, _I, _I, _I, _I, _P]),
     "magat_sim_mapf_ecbs_workspace_bytes": (_Z, [_I, _I, _I, _I, _I]),
     "magat_sim_mapf_ecbs": (_I, [_P, _I, _I, _I] + [_P] * 13 + [_Z, _I, _I, _I, _I, _I, _I, _P]),
+    "magat_sim_mapf_ecbs_wide_workspace_bytes": (_Z, [_I, _I, _I, _I, _I, _I, _I]),
+    "magat_sim_mapf_ecbs_wide": (_I, [_P, _I, _I, _I] + [_P] * 13 + [_Z, _I, _I, _I, _I, _I, _I, _P]),
     "magat_sim_cases_generate_wide": (_I, [_I, _P, _I, _I, _I, _I, _I, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64] + [_P] * 5 + [_I, _I, _P]),
     "magat_conv_first_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "magat_conv_first_tiled_f32": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),

@@ -21,26 +21,12 @@
 #include "row_board.h"
 #include "sim_mapf_audit_parts.h"      // AUDIT_MAX_N, AUDIT_NONE, audit_stage2
 #include "sim_mapf_cbs_parts.h"        // cbs_wave_min / _max, cbs_mark, cbs_mark_chain, cbs_place
+#include "sim_mapf_ecbs_parts.h"       // ECBS_*, ecbs_node, ecbs_wave_sum, ecbs_count
 #include "sim_mapf_parts.h"            // MAPF_*, board_row
 
 namespace {
 
-constexpr int ECBS_MAX_NODES = 4096;
-constexpr int ECBS_MAX_LEVELS = 4;
-constexpr int ECBS_MAX_W_MILLI = 1 << 20;
-constexpr int ECBS_OPEN = 1 << 15;
 constexpr int ECBS_GRID = MAPF_SIDE * MAPF_SIDE;
-
-struct ecbs_node {
-  int parent;
-  int cost;      // the flowtime of the node's schedule; -1: the child found no arrival
-  int lb;        // the sum of the agents' t*
-  int hc;        // the conflicts of the node's schedule
-  int who;       // agent | board << 12 | open << 15 | (length - 1) << 16
-  int what;      // the constraint: t | row << 16 | col << 24
-  int tstar;     // the re-planned agent's bound
-  int pad;
-};
 
 // per case, in 64-bit words: hard boards | soft boards | planes | root paths | node paths | nodes | rlen, rts, src, the two cell rows
 struct ecbs_layout {
@@ -56,11 +42,6 @@ __host__ __device__ inline ecbs_layout ecbs_case_layout(int N, int T, int M, int
   l.ints = l.nodes + (long long)M * 4;
   l.words = l.ints + (5LL * N + 1) / 2;
   return l;
-}
-
-__device__ __forceinline__ int ecbs_wave_sum(int v) {
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
 }
 
 // the planner's reservation of one row of the schedule (padded with its last cell) on the soft boards, or its removal: V[t] at the
@@ -220,43 +201,6 @@ __device__ void ecbs_backtrace(const u64* hard, const u64* soft, const u64* P, i
   }
 }
 
-// hc of the schedule in `rows`, over t < span: own_t[cell] is the smallest agent on a cell at t (audit_stage2's grids, all
-// AUDIT_NONE going in and coming out).  Counted: the agents a with own_t[cell_a(t)] < a, and for t >= 1 the agents a that moved,
-// with b = own_(t-1)[cell_a(t)] existing, b > a and cell_b(t) == cell_a(t-1).  The same value for every lane.
-__device__ int ecbs_count(const int* rows, int N, int T, int W, int span, int* own0, int* own1, int* at0, int* at1, int lane) {
-  int *own_cur = own0, *own_prv = own1, *at_cur = at0, *at_prv = at1;
-  int n = 0;
-  for (int t = 0; t < span; ++t) {
-    for (int a = lane; a < N; a += 64) {
-      const int* p = rows + ((long long)a * T + t) * 2;
-      const int cell = p[0] * W + p[1];
-      at_cur[a] = cell;
-      atomicMin(&own_cur[cell], a);
-    }
-    __syncthreads();
-    for (int a = lane; a < N; a += 64) {
-      const int cell = at_cur[a];
-      if (own_cur[cell] < a) ++n;
-      if (t >= 1) {
-        const int from = at_prv[a], b = own_prv[cell];
-        if (from != cell && b != AUDIT_NONE && b > a && at_cur[b] == from) ++n;
-      }
-    }
-    __syncthreads();      // every read of own_prv lies behind
-    if (t >= 1)
-      for (int a = lane; a < N; a += 64) own_prv[at_prv[a]] = AUDIT_NONE;
-    __syncthreads();
-    int* g = own_cur;
-    own_cur = own_prv, own_prv = g;
-    g = at_cur;
-    at_cur = at_prv, at_prv = g;
-  }
-  if (span >= 1)
-    for (int a = lane; a < N; a += 64) own_prv[at_prv[a]] = AUDIT_NONE;
-  __syncthreads();
-  return ecbs_wave_sum(n);
-}
-
 template <int K>
 __global__ __launch_bounds__(64) void mapf_ecbs_kernel(const uint8_t* __restrict__ map, long long map_stride, int H, int W,
                                                        const int* __restrict__ start, const int* __restrict__ goal, int* paths,
@@ -340,7 +284,7 @@ __global__ __launch_bounds__(64) void mapf_ecbs_kernel(const uint8_t* __restrict
       span = l > span ? l : span;
     }
     span = cbs_wave_max(span);
-    const int hc = ecbs_count(rows, N, T, W, span, own, own + ECBS_GRID, at, at + N, lane);
+    const int hc = ecbs_count(rows, N, T, W, span, own, own + ECBS_GRID, at, at + N, lane, 64, ecbs_wave_sum);
     if (lane == 0) nodes[0] = ecbs_node{-1, cost, lb, hc, ECBS_OPEN, 0, 0, 0};
     count = 1;
   }
@@ -461,7 +405,7 @@ __global__ __launch_bounds__(64) void mapf_ecbs_kernel(const uint8_t* __restrict
           span = l > span ? l : span;
         }
         span = cbs_wave_max(span);
-        hc = ecbs_count(rows, N, T, W, span, own, own + ECBS_GRID, at, at + N, lane);
+        hc = ecbs_count(rows, N, T, W, span, own, own + ECBS_GRID, at, at + N, lane, 64, ecbs_wave_sum);
         cbs_place(px, from ? npath + (long long)from * T : root + (long long)x * T, lx, T, lane);
         if (lane == 0) len[x] = lx;
       }

@@ -16,12 +16,13 @@ constexpr int WMAPF_AHEAD = 4;       // layers of boards in flight
 __host__ __device__ constexpr int wide_rows(int H) { return 64 * ((H + 63) / 64); }
 __host__ __device__ constexpr int wide_words(int W) { return W <= 64 ? 1 : W <= 128 ? 2 : 4; }
 
-// the layers of one case: every thread touches its own row of a board, but for the reservations of a path
-template <int NW>
+// the layers of one case, NB boards each (the wide ECBS keeps sets of 5, and its planes as layers of one board): every thread
+// touches its own row of a board, but for the reservations of a path
+template <int NW, int NB = WMAPF_BOARDS>
 struct wide_layers {
   u64* base;
   int rows;
-  __device__ __forceinline__ u64* at(int t, int b, int row) const { return base + (((long long)t * WMAPF_BOARDS + b) * rows + row) * NW; }
+  __device__ __forceinline__ u64* at(int t, int b, int row) const { return base + (((long long)t * NB + b) * rows + row) * NW; }
   __device__ __forceinline__ wboard<NW> load(int t, int b, int row) const {
     wboard<NW> r;
     const u64* p = at(t, b, row);

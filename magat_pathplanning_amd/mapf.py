@@ -55,7 +55,17 @@ the smallest bound of the open list.  A solved case promises flowtime <= w * low
 Maps above 64 x 64 and horizons above 256 are opt-in everywhere: plan_prioritized, solve_cases, improve_schedules and
 audit_schedules take wide=True (csrc/sim_mapf_wide.hip, csrc/sim_mapf_lns_wide.hip, csrc/sim_mapf_audit_wide.hip: maps up to
 256 x 256, horizons up to 1024), and solve_cases(..., wide=True, improve=I, certify=w) hands it on; without it such shapes raise
-MagatNativeError as before.  cbs_cases and ecbs_cases have no wide form yet: they refuse such shapes with or without wide=True.
+MagatNativeError as before.  ECBS's wide form comes under a name of its own, ecbs_cases_wide (csrc/sim_mapf_ecbs_wide.hip: the
+same rule on maps up to 256 x 256 with horizons up to 1024), with adopt_bounded - solve_cases(bounded=)'s replacement rule as a
+function - to put its schedules into a result:
+
+    res = solve_cases(obstacle_map, start, goal, wide=True, improve=32)
+    sub = ecbs_cases_wide(obstacle_map, start, goal, 1.5, horizon=res["paths"].shape[2])
+    res = adopt_bounded(res, sub)                           # + ecbs_status, ecbs_bound, ecbs_nodes, bounded
+    audit = audit_schedules(obstacle_map, res, wide=True)
+
+ecbs_cases and solve_cases(bounded=) themselves refuse such shapes with or without wide=True, as before.  cbs_cases has no wide
+form yet (ecbs_cases_wide at w = 1 gives the optimal flowtime).
 
 HIP only: CPU tensors raise MagatNativeError.  plan_prioritized is stream ordered and never waits for the device;
 solve_cases reads `solved` back once per round."""
@@ -364,7 +374,7 @@ def ecbs_cases(obstacle_map, start, goal, w=1.5, horizon=None, max_nodes=256, le
                     cbs_cases' horizon caveat; status 2, 3: -1
     so solved_pack, audit_schedules and improve_schedules take it as it is.
     Limits: H, W <= 64, horizon <= 256, N <= 4096, max_nodes and levels as above - anything else raises MagatNativeError, a w
-    below 1 or above 1048.576 ValueError; there is no wide form yet.  Stream ordered, no host synchronisation."""
+    below 1 or above 1048.576 ValueError; the wide form is ecbs_cases_wide.  Stream ordered, no host synchronisation."""
     w_milli = _w_milli(w, "ecbs_cases")
     start, goal = _dev_i32(start, "start"), _dev_i32(goal, "goal")
     if not isinstance(obstacle_map, torch.Tensor) or not obstacle_map.is_cuda:
@@ -392,6 +402,88 @@ def ecbs_cases(obstacle_map, start, goal, w=1.5, horizon=None, max_nodes=256, le
                   "magat_sim_mapf_ecbs")
     return dict(paths=paths, lengths=lengths, goal=goal, start=start, makespan=extra[0], solved=solved, status=extra[1],
                 flowtime=extra[2], lower_bound=extra[3], nodes=extra[4], expanded=extra[5], horizon_hit=extra[6])
+
+
+def _ecbs_wide_limits(H, W, T, N, max_nodes, levels):
+    if (H > WIDE_MAX_SIDE or W > WIDE_MAX_SIDE or T > WIDE_MAX_HORIZON or N > MAX_AGENTS_AUDIT or not 1 <= max_nodes <= MAX_NODES_CBS
+            or not 1 <= levels <= MAX_LEVELS_ECBS):
+        raise nat.MagatNativeError("ecbs_cases_wide takes maps up to %d x %d, horizons up to %d, %d agents, 1..%d nodes per case and "
+                                   "1..%d levels, not %d x %d / %d / %d / %d / %d"
+                                   % (WIDE_MAX_SIDE, WIDE_MAX_SIDE, WIDE_MAX_HORIZON, MAX_AGENTS_AUDIT, MAX_NODES_CBS, MAX_LEVELS_ECBS, H,
+                                      W, T, N, max_nodes, levels))
+
+
+def ecbs_cases_wide(obstacle_map, start, goal, w=1.5, horizon=None, max_nodes=256, levels=4):
+    """ecbs_cases on maps up to 256 x 256 with horizons up to 1024: the same arguments, the same rule cell for cell and node for
+    node, the same dict - so solved_pack, audit_schedules(wide=True), improve_schedules(wide=True) and expert_samples(wide=True)
+    take it as it is.  horizon defaults to default_horizon(H, W, N, wide=True).  By plan_prioritized's rule a shape with H, W <= 64
+    and horizon <= 256 goes to magat_sim_mapf_ecbs and gives ecbs_cases' bits; a larger one goes to magat_sim_mapf_ecbs_wide
+    (csrc/sim_mapf_ecbs_wide.hip): one workgroup of rows = 64 ceil(H / 64) threads per case, words = 1, 2 or 4 64-bit words >= W / 64
+    per row, and a workspace of
+      8 * (horizon * rows * words * (10 + levels) + ceil(N * horizon / 4) + ceil(max_nodes * horizon / 4) + 4 * max_nodes
+           + ceil(5 * N / 2) + H * W) bytes per case
+    - 10.6 MB at 65 x 65 / 100 agents / horizon 360, 91 MB at 160 x 160 / 1000 agents / horizon 1024, with 256 nodes and 4 levels.
+    The search is sequential in the tree and in the steps of a flood: one run on one MI355X took 54 ms for 32 such 65 x 65 cases
+    and 4.6 s for 4 such 160 x 160 cases, which all ended at the node budget (tools/mapf_bench.py, the _ecbs_wide rows).  w = 1 gives the optimal flowtime, as cbs_cases would.
+    Limits: H, W <= 256, horizon <= 1024, N <= 4096, max_nodes 1..4096, levels 1..4 - anything else raises MagatNativeError with a
+    message that names them, a w below 1 or above 1048.576 ValueError, CPU tensors MagatNativeError.
+    Stream ordered, no host synchronisation; one launch."""
+    w_milli = _w_milli(w, "ecbs_cases_wide")
+    start, goal = _dev_i32(start, "start"), _dev_i32(goal, "goal")
+    if not isinstance(obstacle_map, torch.Tensor) or not obstacle_map.is_cuda:
+        raise nat.MagatNativeError("obstacle_map must be a device tensor (no CPU fallback)")
+    m = obstacle_map.to(torch.uint8).contiguous()
+    assert start.dim() == 3 and start.shape[2] == 2 and goal.shape == start.shape, "start and goal must be (C,N,2)"
+    C, N, _ = start.shape
+    assert m.dim() in (2, 3) and (m.dim() == 2 or m.shape[0] == C), "obstacle_map must be (H,W) or (C,H,W)"
+    H, W = m.shape[-2], m.shape[-1]
+    T = default_horizon(H, W, N, wide=True) if horizon is None else int(horizon)
+    max_nodes, levels = int(max_nodes), int(levels)
+    _ecbs_wide_limits(H, W, T, N, max_nodes, levels)
+    if H <= MAX_SIDE and W <= MAX_SIDE and T <= MAX_HORIZON:
+        return ecbs_cases(m, start, goal, w=w, horizon=T, max_nodes=max_nodes, levels=levels)
+    dev = start.device
+    paths = torch.empty(C, N, T, 2, dtype=torch.int32, device=dev)
+    lengths = torch.empty(C, N, dtype=torch.int32, device=dev)
+    solved = torch.empty(C, dtype=torch.uint8, device=dev)
+    extra = torch.empty(7, C, dtype=torch.int32, device=dev)
+    lib = nat.lib()
+    ws = torch.empty(max(int(lib.magat_sim_mapf_ecbs_wide_workspace_bytes(C, H, W, N, T, max_nodes, levels)), 8), dtype=torch.uint8,
+                     device=dev)
+    with torch.cuda.device(dev):
+        nat.check(lib.magat_sim_mapf_ecbs_wide(nat.ptr(m), 1 if m.dim() == 3 else 0, H, W, nat.ptr(start), nat.ptr(goal),
+                                               nat.ptr(paths), nat.ptr(lengths), nat.ptr(extra[0]), nat.ptr(solved), nat.ptr(extra[1]),
+                                               nat.ptr(extra[2]), nat.ptr(extra[3]), nat.ptr(extra[4]), nat.ptr(extra[5]),
+                                               nat.ptr(extra[6]), nat.ptr(ws), ws.numel(), C, N, T, max_nodes, w_milli, levels,
+                                               nat.current_stream(dev)), "magat_sim_mapf_ecbs_wide")
+    return dict(paths=paths, lengths=lengths, goal=goal, start=start, makespan=extra[0], solved=solved, status=extra[1],
+                flowtime=extra[2], lower_bound=extra[3], nodes=extra[4], expanded=extra[5], horizon_hit=extra[6])
+
+
+def adopt_bounded(res, sub):
+    """solve_cases(bounded=)'s replacement rule as a function: `res` a plan_prioritized / solve_cases / improve_schedules result,
+    `sub` an ecbs_cases / ecbs_cases_wide result on the same cases with the same horizon (otherwise ValueError).  Where
+    sub["status"] == 0 AND the case in `res` is unsolved or has a larger flowtime, sub's paths, lengths and makespan replace the
+    case's, solved becomes 1 and failed_agent -1 (where `res` has that key).  Returns a NEW dict with every key of `res` but `T`
+    (solved_pack computes it), plus ecbs_status, ecbs_bound (sub's lower_bound where horizon_hit == 0, else -1), ecbs_nodes (C,) int32
+    and bounded (C,) bool (status 0: flowtime <= w * ecbs_bound holds for the case's schedule).  For `certified`, take the audit's
+    flowtime_bound to torch.maximum(audit["flowtime_bound"], res["ecbs_bound"]).  Tensor ops only: no launch of the package's own,
+    no host synchronisation; neither input is modified."""
+    if tuple(res["paths"].shape) != tuple(sub["paths"].shape):
+        raise ValueError("adopt_bounded: res and sub must hold the same cases with the same horizon, not paths of %s and %s"
+                         % (tuple(res["paths"].shape), tuple(sub["paths"].shape)))
+    done = sub["status"] == 0
+    take = done & ((res["solved"] == 0) | ((res["lengths"] - 1).sum(1) > sub["flowtime"]))
+    out = {key: value for key, value in res.items() if key != "T"}
+    out.update(paths=torch.where(take[:, None, None, None], sub["paths"], res["paths"]),
+               lengths=torch.where(take[:, None], sub["lengths"], res["lengths"]),
+               makespan=torch.where(take, sub["makespan"], res["makespan"]),
+               solved=torch.where(take, torch.ones_like(res["solved"]), res["solved"]))
+    if "failed_agent" in res:
+        out["failed_agent"] = torch.where(take, torch.full_like(res["failed_agent"], -1), res["failed_agent"])
+    bound = torch.where(sub["horizon_hit"] == 0, sub["lower_bound"], torch.full_like(sub["lower_bound"], -1))
+    out.update(ecbs_status=sub["status"], ecbs_bound=bound, ecbs_nodes=sub["nodes"], bounded=done)
+    return out
 
 
 def solve_cases(obstacle_map, start, goal, horizon=None, retries=8, wide=False, improve=0, optimal=None, bounded=None, bounded_nodes=256,

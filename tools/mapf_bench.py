@@ -28,6 +28,12 @@ and, over the cases CBS proved optimal and solve_cases solved, both total flowti
 the share of cases solved, the mean of flowtime / lower_bound over them, and its total flowtime against solve_cases' (over the cases
 both solved) and against CBS's (over the cases CBS proved optimal).  None of these figures is a gate.
 
+Last come two rows of the wide ECBS (csrc/sim_mapf_ecbs_wide.hip, ecbs_cases_wide with w = 1.5, max_nodes = 256, 4 levels), on
+batches of their own - 32 cases of 65 x 65 / 100 agents and 4 cases of 160 x 160 / 1000 agents, "<shape>_ecbs_wide" - at the
+horizon solve_cases(wide=True) used: the time per call, the cases solved, the mean of flowtime / lower_bound over them, and its
+total flowtime next to that of solve_cases(wide=True, improve=32) over the cases both solved.  A row whose workspace does not fit
+the free device memory says so and times nothing.
+
     python tools/mapf_bench.py [--restatement K] [--no-device]"""
 import argparse
 import json
@@ -191,6 +197,48 @@ def ecbs_row(sh, d, full, args):
                 solved_only_by_ecbs=int((done & ~solved).sum()), solved_by_ecbs_not_proven_by_cbs=int((done & ~proven).sum()))
 
 
+ECBS_WIDE_SHAPES = (dict(name="wide_65x65_n100", C=32, size=65, N=100, density=0.1, seed=105),
+                    dict(name="wide_160x160_n1000", C=4, size=160, N=1000, density=0.1, seed=106))
+
+
+def ecbs_wide_row(sh, args):
+    import torch
+    from magat_pathplanning_amd import _native as nat
+    from magat_pathplanning_amd import ecbs_cases_wide, solve_cases
+    m, start, goal = mr.random_batch(sh["seed"], sh["C"], sh["size"], sh["size"], sh["N"], sh["density"])
+    d = [torch.from_numpy(np.ascontiguousarray(a)).cuda() for a in (m, start, goal)]
+    full = solve_cases(*d, retries=8, wide=True, improve=IMPROVE["iterations"])
+    T = full["paths"].shape[2]
+    out = dict(shape=sh["name"] + "_ecbs_wide", cases=sh["C"], agents=sh["N"], T=T, **ECBS)
+    need = int(nat.lib().magat_sim_mapf_ecbs_wide_workspace_bytes(sh["C"], sh["size"], sh["size"], sh["N"], T, ECBS["max_nodes"], ECBS["levels"]))
+    out.update(workspace_bytes=need)
+    if need > torch.cuda.mem_get_info()[0] * 9 // 10:
+        out.update(measured=False, why="the workspace does not fit the free device memory")
+        return out
+    run = lambda: ecbs_cases_wide(*d, horizon=T, **ECBS)      # noqa: E731
+    t0 = time.perf_counter()
+    sub = run()
+    torch.cuda.synchronize()
+    first_s = time.perf_counter() - t0
+    if first_s > 20.0:      # one call is all there is time for: the host clock around it, the code object's load included
+        out.update(warmup=0, calls=1, ecbs_ms_median=first_s * 1e3, ecbs_ms_min=first_s * 1e3, ecbs_ms_max=first_s * 1e3)
+    else:
+        warmup, calls = (0, min(args.calls, 3)) if first_s > 1.0 else (args.warmup, args.calls)
+        ms, sub = timed(run, warmup, calls)
+        out.update(warmup=warmup, calls=calls, ecbs_ms_median=ms[len(ms) // 2], ecbs_ms_min=ms[0], ecbs_ms_max=ms[-1])
+    done, solved = sub["status"] == 0, full["solved"] != 0
+    flow = (full["lengths"] - 1).sum(1)
+    have = done & (sub["lower_bound"] > 0)
+    ratio = sub["flowtime"][have].double() / sub["lower_bound"][have].double()
+    out.update(measured=True, solved=int(done.sum()), at_budget=int((sub["status"] == 1).sum()), no_schedule=int((sub["status"] >= 2).sum()),
+               horizon_hit=int((sub["horizon_hit"] != 0).sum()), nodes_mean=float(sub["nodes"].float().mean()),
+               ratio_mean=float(ratio.mean()) if have.any() else None, ratio_max=float(ratio.max()) if have.any() else None,
+               solved_by_solve_cases=int(solved.sum()),
+               flowtime_ecbs_vs_solve_cases_improved=[int(sub["flowtime"][done & solved].sum()), int(flow[done & solved].sum())],
+               solved_only_by_ecbs=int((done & ~solved).sum()))
+    return out
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--restatement", type=int, default=0, help="time the Python restatement on this many cases per shape")
@@ -240,6 +288,10 @@ def main():
             if not sh.get("wide", False):
                 print(json.dumps(cbs_row(sh, d, full, args)), flush=True)
                 print(json.dumps(ecbs_row(sh, d, full, args)), flush=True)
+    for sh in ECBS_WIDE_SHAPES:
+        if args.no_device or (args.shapes and sh["name"] + "_ecbs_wide" not in args.shapes.split(",")):
+            continue
+        print(json.dumps(ecbs_wide_row(sh, args)), flush=True)
 
 
 if __name__ == "__main__":
