@@ -784,6 +784,25 @@ int magat_sim_expert_radius(const int32_t* pos, const uint8_t* valid, double com
 int magat_sim_expert_stats(const float* target, const int32_t* start, const int32_t* goal, const uint8_t* valid,
                            int32_t* expert_first_move, int32_t* expert_end_step, int32_t* makespan_target,
                            int32_t* flowtime_target, int32_t* expert_pos, int C, int T, int N, void* stream);
+/* magat_sim_expert_pick: the gather of a device-resident training set (memory.py: ExpertMemory).  The store holds `count`
+ * cases of N agents as packed schedules - cells (count,N,Lcap) uint16 = row << 8 | col (maps up to 256 x 256), padded behind
+ * lengths (count,N) with the path's last cell; goal (count,N,2); makespan (count,); radii (count,) float64; cum (count,) int64,
+ * the inclusive prefix sums of makespan + 1; maps (count,H,W) uint8, or NULL when every case lives on one shared map.  A sample
+ * is one (case, step) pair, numbered case by case: sample j belongs to the first case c with cum[c] > j (binary search), at
+ * step t = j - cum[c - 1] (j itself for c = 0).  For each of the M entries of indices (M,) int64 and each agent, exactly
+ * magat_sim_expert_schedule's rule: pos = cell[t] (t < L) or the goal, next = cell[t + 1] (t < L - 1) or the goal, target =
+ * one-hot index of next - pos in the order up, left, down, right, stop.  Outputs: case_out, step_out (M,) int32; pos (M,N,2)
+ * int32; target (M,N,5) float32; action (M,N) int64 = target.argmax(-1); goal_out (M,N,2) int32; radii_out (M,) float64; with
+ * per-case maps map_out (M,H,W) uint8.  An index outside [0, cum[count - 1]) is clamped into it - the row is still a real
+ * sample - and flag[0] = min(flag[0], m): the caller sets the int32 flag to INT32_MAX once and reads it when it likes.
+ * Checks, in the siblings' order: NULL pointers (-5); non-positive sizes (-1); H, W > 256, M * N or M * H * W above 2^31 - 1,
+ * maps and map_out not both set or both NULL (-2).  A refused call launches and counts nothing; a launched one is one kernel,
+ * one count in form "sim_expert" and one span of its profiling tag. */
+int magat_sim_expert_pick(const uint16_t* cells, const int32_t* lengths, const int32_t* goal, const int32_t* makespan,
+                          const double* radii, const int64_t* cum, const uint8_t* maps /* NULL: shared map */,
+                          const int64_t* indices, int32_t* case_out, int32_t* step_out, int32_t* pos, float* target,
+                          int64_t* action, int32_t* goal_out, double* radii_out, uint8_t* map_out /* NULL iff maps is */,
+                          int32_t* flag, int count, int N, int Lcap, int H, int W, int M, void* stream);
 
 /* ------------------------------------------------------------------------------------------
  * A multi-agent path-finding expert (sim_mapf.hip; added behind ABI 9, nothing above changes): prioritized planning with an

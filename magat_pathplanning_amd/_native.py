@@ -157,6 +157,7 @@ _SIGNATURES = {
     "magat_sim_expert_schedule": (_I, [_P] * 8 + [_I] * 4 + [_P]),
     "magat_sim_expert_radius": (_I, [_P, _P, ctypes.c_double, _P, _P, _P, _I, _I, _I, _I, _P]),
     "magat_sim_expert_stats": (_I, [_P] * 9 + [_I] * 3 + [_P]),
+    "magat_sim_expert_pick": (_I, [_P] * 17 + [_I] * 6 + [_P]),
     "magat_sim_mapf_workspace_bytes": (_Z, [_I, _I]),
     "magat_sim_mapf_plan": (_I, [_P, _I, _I, _I] + [_P] * 9 + [_Z, _I, _I, _I, _P]),
     "magat_sim_cases_generate": (_I, [_I, _P, _I, _I, _I, _I, _I, ctypes.c_uint64, ctypes.c_uint64, ctypes.c_int64] + [_P] * 5 + [_I, _I, _P]),

@@ -8,12 +8,16 @@
 //                                maximum and repeats the multiplications)
 //   magat_sim_expert_stats      first move, arrival step, makespan, flowtime and the expert's positions from the targets
 //                               (one wavefront per case, lanes over agents, the scan over steps is sequential)
+//   magat_sim_expert_pick       the expert memory's gather: sample numbers -> (case, step), positions, targets, actions, goals,
+//                               radii and maps of a minibatch, decoded from the stored schedules (sim_expert_pick.h: one thread
+//                               per (sample, agent))
 // State tensors and GSOs of the samples come from the existing kernels (sim_frontend.hip, sim_guidance.hip) on the decoded
 // positions.  Every output is written by per-thread (vector) stores.
 #include <cstdint>
 
 #include "magat_common.h"
 #include "sim_connect.h"
+#include "sim_expert_pick.h"
 
 namespace {
 
@@ -216,6 +220,35 @@ extern "C" int magat_sim_expert_stats(const float* target, const int32_t* start,
   const int pid = magat_prof_begin(MAGAT_TAG_SIM_EXPERT, st);
   hipLaunchKernelGGL(expert_stats_kernel, dim3((unsigned)C), dim3(64), 0, st, target, start, goal, valid, expert_first_move,
                      expert_end_step, makespan_target, flowtime_target, expert_pos, T, N);
+  magat_prof_end(pid, st);
+  return magat_check_launch();
+}
+
+extern "C" int magat_sim_expert_pick(const uint16_t* cells, const int32_t* lengths, const int32_t* goal, const int32_t* makespan,
+                                     const double* radii, const int64_t* cum, const uint8_t* maps, const int64_t* indices,
+                                     int32_t* case_out, int32_t* step_out, int32_t* pos, float* target, int64_t* action,
+                                     int32_t* goal_out, double* radii_out, uint8_t* map_out, int32_t* flag, int count, int N, int Lcap,
+                                     int H, int W, int M, void* stream) {
+  if (!cells || !lengths || !goal || !makespan || !radii || !cum || !indices || !case_out || !step_out || !pos || !target || !action ||
+      !goal_out || !radii_out || !flag)
+    return MAGAT_ERR_NULL;
+  if (count <= 0 || N <= 0 || Lcap <= 0 || H <= 0 || W <= 0 || M <= 0) return MAGAT_ERR_BAD_SHAPE;
+  if (H > 256 || W > 256) return MAGAT_ERR_UNSUPPORTED;            // a cell is row << 8 | col
+  const long long items = (long long)M * N, HW = (long long)H * W;
+  if (items > 0x7fffffffLL || (long long)M * HW > 0x7fffffffLL) return MAGAT_ERR_UNSUPPORTED;
+  if ((maps == nullptr) != (map_out == nullptr)) return MAGAT_ERR_UNSUPPORTED;
+  ExpertPickArgs a;
+  a.cells = cells; a.lengths = lengths; a.goal = goal; a.makespan = makespan; a.radii = radii;
+  a.cum = reinterpret_cast<const long long*>(cum); a.maps = maps; a.indices = reinterpret_cast<const long long*>(indices);
+  a.case_out = case_out; a.step_out = step_out; a.pos = pos; a.target = target; a.action = reinterpret_cast<long long*>(action);
+  a.goal_out = goal_out; a.radii_out = radii_out; a.map_out = map_out; a.flag = flag;
+  a.count = count; a.N = N; a.Lcap = Lcap; a.HW = (int)HW; a.M = M;
+  a.map_words = maps && HW % 4 == 0 && (reinterpret_cast<uintptr_t>(maps) | reinterpret_cast<uintptr_t>(map_out)) % 4 == 0;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  magat_form_note(MAGAT_FORM_SIM_EXPERT);
+  const int pid = magat_prof_begin(MAGAT_TAG_SIM_EXPERT, st);
+  hipLaunchKernelGGL(expert_pick_kernel, dim3((unsigned)((items + EXPERT_PICK_THREADS - 1) / EXPERT_PICK_THREADS)), dim3(EXPERT_PICK_THREADS),
+                     0, st, a);
   magat_prof_end(pid, st);
   return magat_check_launch();
 }

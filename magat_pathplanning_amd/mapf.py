@@ -15,6 +15,7 @@ The online expert - re-solving the cases a running episode is failing at, from w
     ep = BatchedEpisode(obstacle_map, pos, goal, maxstep, comm_radius=config.commR)
     ... ep.step(logits) ...
     res = solve_cases(ep.map, ep.pos, ep.goal)                            # schedules that start at the current positions
+    online_expert(ep, mem)                                                # memory.py: the failed cases only, ECBS(1.1), appended to mem
 
 Prioritized planning in index order never revisits a choice: agents early in the order get shortest paths, the late ones what
 is left.  improve_schedules (csrc/sim_mapf_lns.hip) repairs some of that by neighbourhood re-planning (MAPF-LNS): per
