@@ -50,8 +50,10 @@ const char* magat_error_string(int code);
 
 /* Options.  Every tunable of the library lives in one table that is seeded from the environment (MAGAT_<NAME>) ONCE, at
  * first use, and is read / changed through these calls afterwards; nothing on the launch path calls getenv.  `name` with
- * or without the MAGAT_ prefix.  All twenty (round 5: the A/B switches of kernel forms that lost their measurements are gone
- * with those forms; round 6: + CSR_FUSED, LAT_AGENTS, GAT_WIDE_FROM; csrc/options.hip holds the table):
+ * or without the MAGAT_ prefix.  All twenty-one (round 5: the A/B switches of kernel forms that lost their measurements are gone
+ * with those forms; round 6: + CSR_FUSED, LAT_AGENTS, GAT_WIDE_FROM; then CHAIN_TILE16; csrc/options.hip holds the table):
+ *   CHAIN_TILE16 (2) one-launch chain kernel: layer3.conv2 on 16-row tiles (v_mfma_f32_16x16x32_f16) - 0 never, 1 always, 2 from
+ *                    10 240 agents (magat_encoder_desc.form_agents when set); needs off[31]; NOT bit-identical to the 32-row form
  *   LAT_AGENTS (512) largest agent count (magat_encoder_desc.form_agents when set) whose encoder runs ONE AGENT PER WORKGROUP
  *                    (csrc/block_lat.hip: layer1.conv2 .. layer3, pool, head and compressMLP in one launch; the batch-1 step of the
  *                    reference's inference loop); results bit-identical to the eight-agent-group kernels; 0 = never
@@ -615,7 +617,8 @@ typedef struct magat_encoder_desc {
   int n_feat;      /* numFeatureMap: width of `feat` (128 for *_withMLP, 1152 otherwise) */
   int n_comp;      /* bottleneckFeature G (0: skip compressMLP) */
   const float* pack; /* device pointer to the folded parameter pack */
-  int64_t off[32];   /* float offsets into pack: see DESIGN.md "encoder pack" */
+  int64_t off[32];   /* float offsets into pack: see DESIGN.md "encoder pack".  off[31]: layer3.conv2 once more in 16-row
+                        fragments (encoder.pack_block3_tile16; option CHAIN_TILE16), 0 = absent: the 32-row form at every size */
   int64_t chain_off; /* float offset of the BasicBlock chain kernel's fragment-major weights (encoder.pack_chain_weights: layer1.
                         conv2+downsample, layer2.conv1, layer2.conv2+downsample), 0 = absent -> layer-by-layer kernels (ABI 2) */
   int64_t chain3_off; /* float offset of the layer3 kernel's weights (encoder.pack_block3_weights), 0 = absent (ABI 2) */

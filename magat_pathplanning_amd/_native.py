@@ -22,7 +22,8 @@ TAGS = {0: "untagged", 1: "conv_first", 2: "layer1.conv1", 3: "layer1.conv2+ds",
 TAG_ACTIONS = 12
 # magat_form_count ids (include/magat_hip.h MAGAT_FORM_*)
 FORMS = {"head_longk": 0, "head_splitk": 1, "gat_pack": 2, "gat_persist": 3, "gat_hsplit": 4, "chain_persist": 5,
-         "head_compress": 6, "guard_one": 7, "csr_fused": 8, "gat_mid": 9, "chain_lat": 10, "head_lat": 11, "guard_lat": 12, "stem_lat": 13, "actions_tail": 14, "gnn_dense": 15, "sim_guided": 16, "sim_expert": 17, "sim_mapf": 18, "sim_mapf_lns": 19, "sim_mapf_audit": 20, "sim_mapf_cbs": 21, "sim_mapf_ecbs": 22}
+         "head_compress": 6, "guard_one": 7, "csr_fused": 8, "gat_mid": 9, "chain_lat": 10, "head_lat": 11, "guard_lat": 12, "stem_lat": 13, "actions_tail": 14, "gnn_dense": 15, "sim_guided": 16, "sim_expert": 17, "sim_mapf": 18, "sim_mapf_lns": 19, "sim_mapf_audit": 20, "sim_mapf_cbs": 21, "sim_mapf_ecbs": 22,
+         "chain_tile16": 23}
 TAG_GNN_DENSE = 25
 TAG_SIM_GUIDED = 26
 TAG_SIM_EXPERT = 27

@@ -458,7 +458,10 @@ __global__ __launch_bounds__(256, 1) void block_chain_w4_kernel(const ChainParam
 // residual input at the top of every group).  LDS = four 37.9 KB units U0..U3; their roles alternate with the group parity:
 //   X1 @ U3', X2 @ U2'   -A->  Y @ U1'   -B->  Z @ (U2', U3')   -C->  layer3's IN @ (U0', U1')     [' = rotated by 2 on odd groups]
 //   layer3: IN (U0', U1'), MID (U2', U3'); pooled epilogue scratch in MID; meanwhile the next X1 -> U1', X2 -> U0' (= its U3'', U2'').
-struct FullParams { ChainParams c; L3Params l; };
+struct FullParams {
+  ChainParams c; L3Params l;
+  const char* w2a16; const char* w2b16;      // conv2's two blocks once more in 16-row fragments (block_walk.h walk16), or null
+};
 
 
 
@@ -469,6 +472,9 @@ struct FullParams { ChainParams c; L3Params l; };
 // and a quarter of the centre cell - 11 adds, 4 selects and 4 lane exchanges per channel, no LDS, no barrier; every lane
 // then stores pooled values straight from registers.  The next group's inputs land in the MID region (dead once every wave
 // has left conv2), so the units keep their roles from group to group (no rotation).
+// T16: the large-batch form (option CHAIN_TILE16) - layer3.conv2 on 18 half tiles of 16 rows (block_walk.h walk16: another MFMA
+// shape, another summation order); conv1, MID and everything in front of layer3 are the same code.
+template <bool T16>
 __global__ __launch_bounds__(256, 1) void block_full_p_kernel(const FullParams q) {
   extern __shared__ __attribute__((aligned(1024))) char lds[];
   const ChainParams& p = q.c;
@@ -494,7 +500,10 @@ __global__ __launch_bounds__(256, 1) void block_full_p_kernel(const FullParams q
   const int ct = wave & 1, rg = wave >> 1, ct2 = wave;
   constexpr int BPT1 = 9 * 4 * 2, BPT2A = 9 * 4 * 2, BPT2B = (9 * 4 + 4) * 2;      // 1 KB blocks per channel tile (layer3)
   f32x4 bq[4];                      // conv2's bias (loaded once: a load behind the input DMA would wait for it)
-  {
+  if constexpr (T16) {              // channel quads 4 half + (lane >> 4) of the wave's 32 channels
+#pragma unroll
+    for (int hf = 0; hf < 2; ++hf) bq[hf] = *reinterpret_cast<const f32x4*>(l3.b2 + 32 * ct2 + 16 * hf + 4 * (lane >> 4));
+  } else {
     const int fh = lane >> 5;
 #pragma unroll
     for (int qd = 0; qd < 4; ++qd) bq[qd] = *reinterpret_cast<const f32x4*>(l3.b2 + 32 * ct2 + 8 * qd + 4 * fh);
@@ -536,13 +545,22 @@ __global__ __launch_bounds__(256, 1) void block_full_p_kernel(const FullParams q
     // layer3: IN = (U0, U1), MID = (U2, U3)
     constexpr int L_IN = U0, L_MID = U2;
     const int ct1 = ct, rg1 = rg;
-    f32x16 acc[9];
+    f32x16 acc[T16 ? 1 : 9];
+    f32x4 acc16[2][T16 ? HT_N : 1];
+    if constexpr (T16) {
 #pragma unroll
-    for (int s = 0; s < 9; ++s)
+      for (int hf = 0; hf < 2; ++hf)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) acc[s][r] = 0.f;
+        for (int s = 0; s < HT_N; ++s) acc16[hf][s] = f32x4{0.f, 0.f, 0.f, 0.f};
+    } else {
+#pragma unroll
+      for (int s = 0; s < 9; ++s)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[s][r] = 0.f;
+    }
     auto l3_half = [&](const int h) __attribute__((always_inline)) {
-      const char* w2 = h == 0 ? l3.w2a + (size_t)ct2 * BPT2A * 1024 : l3.w2b + (size_t)ct2 * BPT2B * 1024;
+      const char* w2 = h == 0 ? (T16 ? q.w2a16 : l3.w2a) + (size_t)ct2 * BPT2A * 1024
+                              : (T16 ? q.w2b16 : l3.w2b) + (size_t)ct2 * BPT2B * 1024;
       // conv1, output channels 64 h .. 64 h + 63 -> MID (channel tiles 2 h + ct1 of the weight block)
       const char* w1h = l3.w1 + (size_t)(2 * h) * BPT1 * 1024;
       if (rg1 == 0) {
@@ -569,7 +587,8 @@ __global__ __launch_bounds__(256, 1) void block_full_p_kernel(const FullParams q
       if (h == 0) FULL_STAMP(12); else FULL_STAMP(14);
       __syncthreads();
       FULL_STAMP(5 + 2 * h);
-      walk4<W4All, 4, 4, 8 * BLK, 8 * BLK, MAGAT_W4_D>(lds, L_MID, L_IN, w2, acc, h == 1);
+      if constexpr (T16) walk16<2, 2, 8 * BLK, 8 * BLK, 3>(lds, L_MID, L_IN, w2, acc16, h == 1);
+      else walk4<W4All, 4, 4, 8 * BLK, 8 * BLK, MAGAT_W4_D>(lds, L_MID, L_IN, w2, acc, h == 1);
       // (after the first half: MID is rewritten by the next conv1; after the second: MID and IN are dead in every wave)
       L3_LDS_SYNC();
       FULL_STAMP(6 + 2 * h);
@@ -591,7 +610,47 @@ __global__ __launch_bounds__(256, 1) void block_full_p_kernel(const FullParams q
     FULL_STAMP(9);
     // ---- relu(acc * s2 + bias), 2 x 2 sums in registers, stores.  Accumulator s = tile W4All::t[s]:
     //      0..3 interior tiles Ia Ib Ic Id, 4 C, 5 T (top), 6 B (bottom), 7 L (left), 8 R (right)
-    {
+    if constexpr (T16) {
+      // half tiles (block_walk.h HT_PIX): a lane holds 4 channels of one (slot, agent) column per half tile and channel half.
+      // Slot 0 | 1 lanes sum the corner cells 0 | 2 and 6 | 8 and the column-edge-middle cells 5 | 3 in registers; cells 1, 7
+      // and 4 are two in-lane sums one slot apart (DPP row_ror:8), stored by the slot 0 lane.
+      const int agent = lane & 7, kq = lane >> 4;
+      const bool sl = (lane >> 3) & 1;
+      const int m = group * AG + agent;
+      const int cellA = sl ? 2 : 0, cellB = sl ? 8 : 6, cellE = sl ? 3 : 5;
+      const bool mok = m < p.M;
+#pragma unroll
+      for (int hf = 0; hf < 2; ++hf) {
+        const int g = 8 * ct2 + 4 * hf + kq;         // channel quad of the tile's 128 channels
+        float* ob = l3.out + (long long)(m >> 7) * 9 * (128 * 128) + (l3.out_gl ? g * 512 + (m & 127) * 4 : (m & 127) * 128 + 4 * g);
+        f32x4 vA, vB, vE, v1, v7, v4;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          float v[HT_N];
+#pragma unroll
+          for (int s = 0; s < HT_N; ++s) v[s] = magat_relu(__builtin_fmaf(acc16[hf][s][c], s2, bq[hf][c]));      // (keeps NaN, like torch.relu)
+          const float ea = sl ? v[HT_RA] : v[HT_LA], eb = sl ? v[HT_RB] : v[HT_LB];      // the column-edge pixel of the corner cell
+          const float xa = sl ? v[HT_LA] : v[HT_RA], xb = sl ? v[HT_LB] : v[HT_RB];      // ... and of the edge-middle cell
+          vA[c] = (v[HT_CT] + v[HT_I1]) + (v[HT_TA] + ea);
+          vB[c] = (v[HT_CB] + v[HT_I2]) + (v[HT_BA] + eb);
+          vE[c] = (v[HT_I5] + v[HT_I6]) + (xa + xb);
+          const float p1 = v[HT_TB] + v[HT_I3], p7 = v[HT_BB] + v[HT_I4], p4 = v[HT_I7] + v[HT_I8];
+          v1[c] = p1 + dpp_mov<0x128>(p1);                       // + the lane 8 away (row_ror:8): the other slot
+          v7[c] = p7 + dpp_mov<0x128>(p7);
+          v4[c] = p4 + dpp_mov<0x128>(p4);
+        }
+        if (mok) {
+          CHAIN_OUT_STORE(ob + (long long)cellA * (128 * 128), vA);
+          CHAIN_OUT_STORE(ob + (long long)cellB * (128 * 128), vB);
+          CHAIN_OUT_STORE(ob + (long long)cellE * (128 * 128), vE);
+          if (!sl) {
+            CHAIN_OUT_STORE(ob + (long long)1 * (128 * 128), v1);
+            CHAIN_OUT_STORE(ob + (long long)7 * (128 * 128), v7);
+            CHAIN_OUT_STORE(ob + (long long)4 * (128 * 128), v4);
+          }
+        }
+      }
+    } else {
       const int fr = lane & 31, fh = lane >> 5, agent = fr & 7;
       const bool lo = (lane >> 3) & 1, hi = (lane >> 4) & 1;       // slot psl = 2 hi + lo
       const int m = group * AG + agent;
@@ -738,7 +797,7 @@ extern "C" int magat_block3_set_debug_buffer(long long* dev_buf) { g_block3_dbg 
 // its output) and of magat_block3 (without its input).
 int magat_block_full(const void* in1, const void* in2, const float* wchain, const float* bA, const float* bB, const float* bC,
                      float* out, const float* w3, const float* b1, const float* b2, int M, int* range_flag, hipStream_t st,
-                     const float* scales, int out_gl) {
+                     const float* scales, int out_gl, const float* w3t16, int Mform) {
   if (!in1 || !in2 || !wchain || !bA || !bB || !bC || !out || !w3 || !b1 || !b2) return MAGAT_ERR_NULL;
   if (M <= 0) return MAGAT_ERR_BAD_SHAPE;
   FullParams q;
@@ -772,7 +831,15 @@ int magat_block_full(const void* in1, const void* in2, const float* wchain, cons
 #endif
   if (out_gl != 0 && out_gl != 1) return MAGAT_ERR_UNSUPPORTED;
   l.out_gl = out_gl;
-  if (magat_ensure_dyn_lds(reinterpret_cast<const void*>(&block_full_p_kernel), MAGAT_LDS_BLOCK_FULL_P, LDS_TOTAL) != MAGAT_OK)
+  // layer3.conv2 on 16-row tiles (option CHAIN_TILE16: 0 never, 1 always, 2 from MAGAT_CHAIN_TILE16_FROM agents): another
+  // summation order, so the form is chosen on the agent count of the WHOLE batch (Mform), like the head's
+  const int t16opt = magat_opt(MAGAT_OPT_CHAIN_TILE16);
+  const bool t16 = t16opt == 1 || (t16opt >= 2 && w3t16 && (Mform > 0 ? Mform : M) >= MAGAT_CHAIN_TILE16_FROM);
+  if (t16 && !w3t16) return MAGAT_ERR_UNSUPPORTED;      // (forced, and the pack holds no 16-row fragments)
+  q.w2a16 = t16 ? reinterpret_cast<const char*>(w3t16) : nullptr;
+  q.w2b16 = t16 ? reinterpret_cast<const char*>(w3t16) + n2a : nullptr;
+  const void* kfn = t16 ? reinterpret_cast<const void*>(&block_full_p_kernel<true>) : reinterpret_cast<const void*>(&block_full_p_kernel<false>);
+  if (magat_ensure_dyn_lds(kfn, t16 ? MAGAT_LDS_BLOCK_FULL_P16 : MAGAT_LDS_BLOCK_FULL_P, LDS_TOTAL) != MAGAT_OK)
     return MAGAT_ERR_LAUNCH;
   int dev = 0, cus = 256;
   if (hipGetDevice(&dev) == hipSuccess) {
@@ -782,7 +849,11 @@ int magat_block_full(const void* in1, const void* in2, const float* wchain, cons
   const int grid = p.groups < cus ? p.groups : cus;
   if (p.groups > cus) magat_form_note(MAGAT_FORM_CHAIN_PERSIST);
   const int pid = magat_prof_begin(MAGAT_TAG_BLOCK_FULL, st);
-  hipLaunchKernelGGL(block_full_p_kernel, dim3((unsigned)grid), dim3(256), LDS_TOTAL, st, q);
+  if (t16) {
+    magat_form_note(MAGAT_FORM_CHAIN_TILE16);
+    hipLaunchKernelGGL(block_full_p_kernel<true>, dim3((unsigned)grid), dim3(256), LDS_TOTAL, st, q);
+  } else
+    hipLaunchKernelGGL(block_full_p_kernel<false>, dim3((unsigned)grid), dim3(256), LDS_TOTAL, st, q);
   magat_prof_end(pid, st);
   return magat_check_launch();
 }

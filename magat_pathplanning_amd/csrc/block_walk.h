@@ -227,3 +227,167 @@ struct W4P1 { static constexpr int NT = 2; static constexpr int t[2] = {T_I2, T_
 struct W4P2 { static constexpr int NT = 2; static constexpr int t[2] = {T_C, T_ET}; };
 struct W4P3 { static constexpr int NT = 3; static constexpr int t[3] = {T_EB, T_EL, T_ER}; };
 
+
+// ---------------------------------------------------------------------------------------------------------------------------
+// 16-row tiles: the same maps walked with v_mfma_f32_16x16x32_f16 (layer3.conv2 of large batches; block_fused.hip, option
+// CHAIN_TILE16).  The chip holds a higher clock on this shape (tools/exp/mfma_shape_f16.hip: 1.11 x the FLOP/s of 32x32x16 at
+// 0.98 x the cycles), and two corners that share a map side make one tile with 6 taps: 132 half-tile-taps per channel tile
+// where the nine 32-row tiles run 138.
+// A half tile = 2 pixels x 8 agents: column lane & 15 = (slot (lane >> 3) & 1, agent lane & 7); the lane's operand of a
+// 32-channel k step is chunk 4 k32 + (lane >> 4) of the same LDS map - one ds_read_b128 at an immediate offset, as in walk4.
+// The accumulator of a half tile and a 16-channel half holds, in lane l and register r, channel 16 half + 4 (l >> 4) + r of
+// column l & 15.  The pixel pairs are chosen for the 2 x 2 pooling behind layer3 (slot 0 | slot 1 of every half tile):
+//   corner cells 0 | 2: CT + Ta + (La | Ra) + I1         corner cells 6 | 8: CB + Ba + (Lb | Rb) + I2
+//   column-edge-middle cells 5 | 3: (Ra + Rb | La + Lb) + I5 + I6          - all in-lane sums -
+//   row-edge-middle cells 1, 7 and the centre cell 4: Tb + I3, Bb + I4, I7 + I8 summed over the two slots (DPP row_ror:8).
+// Slots hold pixels of opposite parity (ds_read_b128 is served 16 lanes = the two slots of a k chunk at a time:
+// conflict-free) except in the four column-edge tiles, whose pixels all have one parity (2-way, as in the 32-row tiles).
+constexpr int HT_N = 18;
+constexpr int HT_PIX[HT_N][2] = {{7, 10},  {25, 28}, {8, 9},   {26, 27}, {16, 13}, {22, 19}, {14, 15}, {20, 21},      // I1 .. I8
+                                 {0, 5},   {30, 35},                                                                    // CT, CB
+                                 {1, 4},   {2, 3},   {31, 34}, {32, 33},                                                // Ta Tb Ba Bb
+                                 {6, 12},  {24, 18}, {17, 11}, {23, 29}};                                               // La Lb Ra Rb
+// taps run by a half tile: the union over its two pixels (corner pairs: per-lane validity handled by address)
+constexpr int HT_TAPS[HT_N] = {0x1FF, 0x1FF, 0x1FF, 0x1FF, 0x1FF, 0x1FF, 0x1FF, 0x1FF, 0x1F8, 0x03F,
+                               0x1F8, 0x1F8, 0x03F, 0x03F, 0x1B6, 0x1B6, 0x0DB, 0x0DB};
+constexpr int HT_I1 = 0, HT_I2 = 1, HT_I3 = 2, HT_I4 = 3, HT_I5 = 4, HT_I6 = 5, HT_I7 = 6, HT_I8 = 7, HT_CT = 8, HT_CB = 9,
+              HT_TA = 10, HT_TB = 11, HT_BA = 12, HT_BB = 13, HT_LA = 14, HT_LB = 15, HT_RA = 16, HT_RB = 17;
+constexpr bool ht_tap_valid(int pix, int tp) {
+  const int y = pix / 6 + tp / 3 - 1, x = pix % 6 + tp % 3 - 1;
+  return y >= 0 && y < 6 && x >= 0 && x < 6;
+}
+// every pixel once; a half tile runs exactly the taps valid for at least one of its pixels, and only the two corner pairs run
+// a tap that one of the pixels does not have; 132 half-tile-taps
+constexpr bool ht_tables_ok() {
+  int seen[NPIX] = {}, taps = 0;
+  for (int s = 0; s < HT_N; ++s) {
+    for (int sl = 0; sl < 2; ++sl) seen[HT_PIX[s][sl]] += 1;
+    for (int tp = 0; tp < 9; ++tp) {
+      const bool v0 = ht_tap_valid(HT_PIX[s][0], tp), v1 = ht_tap_valid(HT_PIX[s][1], tp);
+      const bool run = HT_TAPS[s] >> tp & 1;
+      if (run != (v0 || v1)) return false;
+      if (run && v0 != v1 && s != HT_CT && s != HT_CB) return false;
+      taps += run;
+    }
+  }
+  for (int pix = 0; pix < NPIX; ++pix)
+    if (seen[pix] != 1) return false;
+  return taps == 132;
+}
+static_assert(ht_tables_ok(), "half tiles: pixels, tap masks or the tap count");
+constexpr int h16_minshift(int s) {
+  int m = 99;
+  for (int tp = 0; tp < 9; ++tp)
+    if (HT_TAPS[s] >> tp & 1) {
+      const int sh = 6 * (tp / 3 - 1) + (tp % 3 - 1);
+      if (sh < m) m = sh;
+    }
+  return m;
+}
+// items (tap, k32 step, half tile), tap-major like w4_seq; KSM / KS2 count 32-channel steps here
+template <int KSM, int KS2>
+constexpr W4Seq<(132 * KSM + HT_N * KS2) + 1> h16_seq() {
+  W4Seq<(132 * KSM + HT_N * KS2) + 1> q{};
+  int n = 0;
+  for (int tp = 0; tp < 9; ++tp)
+    for (int ks = 0; ks < KSM; ++ks) {
+      bool first = true;
+      for (int s = 0; s < HT_N; ++s)
+        if (HT_TAPS[s] >> tp & 1) {
+          q.it[n].tp = (signed char)tp; q.it[n].ks = (signed char)ks; q.it[n].s = (signed char)s; q.it[n].first = first;
+          first = false;
+          ++n;
+        }
+    }
+  q.nmain = n;
+  for (int ks = 0; ks < KS2; ++ks)
+    for (int s = 0; s < HT_N; ++s) {
+      q.it[n].tp = 9; q.it[n].ks = (signed char)ks; q.it[n].s = (signed char)s; q.it[n].first = s == 0;
+      ++n;
+    }
+  q.n = n;
+  return q;
+}
+// Weights: the 16-row pack (encoder.pack_block3_tile16) - per (tap | residual, k32 step) four 1 KB blocks [half 2][plane 2],
+// lane l of a block: output channel 16 half + (l & 15) of the wave's channel tile, the 8 channels of chunk 4 k32 + (l >> 4).
+// Ring of D k32 steps (the register count of walk4's ring per 32 k values).  Per item six products: for each plane pair in
+// walk4's order (hi.hi, lo.hi, hi.lo) the two channel halves back to back; the operand reads of item i + 2 between them.
+template <int KSM, int KS2, int PS_IN, int PS_IN2, int D>
+__device__ __forceinline__ void walk16(char* lds, int in_off, int in2_off, const char* wbase, f32x4 (&acc)[2][HT_N], bool with_res) {
+  u32x4 w[D][4];
+  constexpr auto SQ = h16_seq<KSM, KS2>();
+  constexpr int NMAIN = 9 * KSM, NSTEP = NMAIN + KS2;
+  int tid = threadIdx.x;
+  asm volatile("" : "+v"(tid));        // (keeps the address set-up inside the caller's loop over the halves)
+  const int lane = tid & 63;
+  const unsigned lane16 = (unsigned)lane * 16u;
+  const int agent = lane & 7, sl = (lane >> 3) & 1, kq = lane >> 4;
+  unsigned ab[HT_N], b0[HT_N];
+  int cmask[2] = {0, 0};                 // corner pairs: the lane's valid taps
+#pragma unroll
+  for (int s = 0; s < HT_N; ++s) {
+    const int pix = sl ? HT_PIX[s][1] : HT_PIX[s][0];
+    ab[s] = (unsigned)(pix * PIXB + agent * 16 + kq * BLK);
+    b0[s] = ab[s] + (unsigned)(in_off + h16_minshift(s) * PIXB);
+    asm volatile("" : "+v"(b0[s]));      // (the base stays a register of its own: every offset below then fits the instruction)
+    if (s == HT_CT || s == HT_CB) {
+      const int y = pix / 6, x = pix - 6 * y;
+#pragma unroll
+      for (int tp = 0; tp < 9; ++tp) {
+        const int dy = tp / 3 - 1, dx = tp % 3 - 1;
+        if (y + dy >= 0 && y + dy < 6 && x + dx >= 0 && x + dx < 6) cmask[s - HT_CT] |= 1 << tp;
+      }
+    }
+  }
+  const unsigned az = (unsigned)(ZPIX * PIXB + agent * 16 + kq * BLK + in_off);
+  auto load_w = [&](int step, u32x4 (&b)[4]) {
+#pragma unroll
+    for (int j = 0; j < 4; ++j) b[j] = *reinterpret_cast<const u32x4*>(wbase + (size_t)step * 4096 + (lane16 + 1024u * j));
+  };
+  constexpr int AV = MAGAT_W4_AV;
+  u32x4 av[AV][2];
+  auto rd = [&](const W4Item it, int pl, u32x4& dst) {
+    if (it.tp == 9) {                                    // residual: the block input at the same pixel
+      dst = *reinterpret_cast<const u32x4*>(lds + (ab[it.s] + (unsigned)in2_off) + (pl * PS_IN2 + it.ks * 4 * BLK));
+    } else if (it.s == HT_CT || it.s == HT_CB) {         // corner pixels: per-lane validity, the others read the zero pixel
+      const int sh = 6 * (it.tp / 3 - 1) + (it.tp % 3 - 1);
+      const unsigned a = (cmask[it.s - HT_CT] >> it.tp & 1) ? ab[it.s] + (unsigned)(in_off + sh * PIXB) : az;
+      dst = *reinterpret_cast<const u32x4*>(lds + a + (pl * PS_IN + it.ks * 4 * BLK));
+    } else {
+      const int sh = 6 * (it.tp / 3 - 1) + (it.tp % 3 - 1) - h16_minshift(it.s);
+      dst = *reinterpret_cast<const u32x4*>(lds + b0[it.s] + (sh * PIXB + pl * PS_IN + it.ks * 4 * BLK));
+    }
+  };
+#pragma unroll
+  for (int j = 0; j < D - 1; ++j)
+    if (j < NSTEP) load_w(j, w[j]);
+#pragma unroll
+  for (int j = 0; j < AV - 1; ++j) {
+    rd(SQ.it[j], 0, av[j][0]);
+    rd(SQ.it[j], 1, av[j][1]);
+  }
+#pragma clang loop unroll(full)
+  for (int i = 0; i < SQ.n; ++i) {
+    const W4Item it = SQ.it[i];
+    if (KS2 > 0 && i == SQ.nmain && !with_res) break;            // (uniform; the first half of conv2 has no residual)
+    const int step = it.tp * KSM + it.ks;              // (residual items: tp = 9)
+    if (it.first && step + D - 1 < NSTEP) {
+      if (step + D - 1 < NMAIN || with_res) load_w(step + D - 1, w[(step + D - 1) % D]);
+    }
+    constexpr int LA = AV - 1;
+    const bool more = i + LA < SQ.n;
+    const bool more_ok = more && (i + LA < SQ.nmain || with_res);
+    const f16x8 a0 = __builtin_bit_cast(f16x8, av[i % AV][0]), a1 = __builtin_bit_cast(f16x8, av[i % AV][1]);
+    acc[0][it.s] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, w[step % D][0]), a0, acc[0][it.s], 0, 0, 0);
+    acc[1][it.s] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, w[step % D][2]), a0, acc[1][it.s], 0, 0, 0);
+    W4_PIN();
+    if (more) { if (more_ok) rd(SQ.it[more ? i + LA : i], 0, av[(i + LA) % AV][0]); W4_PIN(); }
+    acc[0][it.s] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, w[step % D][1]), a0, acc[0][it.s], 0, 0, 0);
+    acc[1][it.s] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, w[step % D][3]), a0, acc[1][it.s], 0, 0, 0);
+    W4_PIN();
+    if (more) { if (more_ok) rd(SQ.it[more ? i + LA : i], 1, av[(i + LA) % AV][1]); W4_PIN(); }
+    acc[0][it.s] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, w[step % D][0]), a1, acc[0][it.s], 0, 0, 0);
+    acc[1][it.s] = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, w[step % D][2]), a1, acc[1][it.s], 0, 0, 0);
+    W4_PIN();
+  }
+}

@@ -500,7 +500,7 @@ static int enc_run_resnet(const magat_encoder_desc* d, const float* x, float* fe
         rc = magat_block_full(buf[1], buf[0], pk + d->chain_off, sp ? sp + 928 : pk + d->off[5], sp ? sp + 960 : pk + d->off[7],
                               sp ? sp + 1024 : pk + d->off[9], buf[2], pk + d->chain3_off, sp ? sp + 1088 : pk + d->off[11],
                               sp ? sp + 1216 : pk + d->off[13], mm, reinterpret_cast<int*>(range_flag), st, sp ? sp + 1344 : nullptr,
-                              head_gl ? 1 : 0);
+                              head_gl ? 1 : 0, d->off[31] > 0 ? pk + d->off[31] : nullptr, Mform);
       if (rc != MAGAT_OK) return rc;
       cur = 2; hin = Ho; win = Wo; lstart = 3; pooled_in = true;
     } else if (fused1 && d->chain_off > 0 && Ho == 6 && Wo == 6 && nblocks >= 2 && magat_opt(MAGAT_OPT_BLOCK_FUSED)) {

@@ -57,10 +57,11 @@ void magat_form_note(int id);      // which form a launch took (MAGAT_FORM_*; pr
 #define MAGAT_FORM_SIM_MAPF_AUDIT 20  // magat_sim_mapf_audit or its wide form launched (one count per call)
 #define MAGAT_FORM_SIM_MAPF_CBS 21    // magat_sim_mapf_cbs launched its one-wave-per-case kernel
 #define MAGAT_FORM_SIM_MAPF_ECBS 22   // magat_sim_mapf_ecbs launched its one-wave-per-case kernel
-#define MAGAT_FORMS_TABLE 23
+#define MAGAT_FORM_CHAIN_TILE16 23   // magat_block_full launched the form with layer3.conv2 on 16-row tiles (option CHAIN_TILE16)
+#define MAGAT_FORMS_TABLE 24
 static_assert(MAGAT_PROF_TAGS_ALL >= MAGAT_PROF_TAGS && MAGAT_FORMS_ALL >= MAGAT_FORMS, "internal tag / form tables");
 static_assert(MAGAT_PROF_TAGS_TABLE > MAGAT_TAG_SIM_MAPF_ECBS && MAGAT_PROF_TAGS_TABLE >= MAGAT_PROF_TAGS_ALL &&
-              MAGAT_FORMS_TABLE > MAGAT_FORM_SIM_MAPF_ECBS && MAGAT_FORMS_TABLE >= MAGAT_FORMS_ALL, "internal tag / form tables");
+              MAGAT_FORMS_TABLE > MAGAT_FORM_CHAIN_TILE16 && MAGAT_FORMS_TABLE >= MAGAT_FORMS_ALL, "internal tag / form tables");
 
 // bf16x6 split-MFMA GEMM (conv_gemm_bf16x6.hip), reached through magat_conv_gemm_f32 when desc->in_fmt == 1
 int magat_conv_gemm_bf16x6(const magat_conv_gemm_desc* d, hipStream_t st);
@@ -75,7 +76,14 @@ size_t magat_block3_weight_floats();
 int magat_block_full(const void* in1, const void* in2, const float* wchain, const float* bA, const float* bB, const float* bC,
                      float* out, const float* w3, const float* b1, const float* b2, int M, int* range_flag, hipStream_t st,
                      const float* scales = nullptr,       // 5 device floats replacing the 1 / weight-scale of stages A, B, C, layer3.conv1, conv2
-                     int out_gl = 0);                     // 1: pooled map granule-major (when magat_block_full_out_gl())
+                     int out_gl = 0,                      // 1: pooled map granule-major (when magat_block_full_out_gl())
+                     const float* w3t16 = nullptr,        // layer3.conv2 in 16-row fragments (encoder.pack_block3_tile16), or null
+                     int Mform = 0);                      // agent count the 16-row form is chosen on (0 = M; option CHAIN_TILE16)
+// CHAIN_TILE16 = 2: first agent count that takes the 16-row form.  It is not slower from 4096 agents (two 8-agent groups per CU;
+// profiles/r07a/ab_tile16.txt: 2 100 agents 141.1 against 140.7 us, 4 100: 207.8 / 211.2, 6 100: 227.0 / 233.7), but one planning
+// instance equals its rows of a 6 400 .. 9 000-agent batch bit for bit today (tests/test_gpu_latency.py, test_gpu_model.py: the
+// latency forms and HEAD_SPLITK = 0 against the 32-row form) - the hand-over sits above those sizes, at five groups per CU
+#define MAGAT_CHAIN_TILE16_FROM 10240
 int magat_block_full_out_gl();
 // the same chain with ONE agent per workgroup (block_lat.hip: the latency form of few-agent calls; bit-identical pooled map)
 struct magat_lat_head {      // ... with the encoder head (9 x 128 -> 128) and compressMLP (128 -> 128) in its epilogue
@@ -115,7 +123,8 @@ enum MagatOpt {
   MAGAT_OPT_ENC_CHUNK, MAGAT_OPT_CONV_SPLIT, MAGAT_OPT_CONV_PCHAIN,
   MAGAT_OPT_L1_FUSED, MAGAT_OPT_HEAD_SPLITK, MAGAT_OPT_GAT_CHUNK_MB, MAGAT_OPT_GAT_SPLIT, MAGAT_OPT_RANGE_GUARD,
   MAGAT_OPT_BLOCK_FUSED, MAGAT_OPT_CSR_TILED, MAGAT_OPT_HEAD_F16, MAGAT_OPT_GAT_MFMA, MAGAT_OPT_SKINNY, MAGAT_OPT_GAT_PACK,
-  MAGAT_OPT_CONV_BNFILL, MAGAT_OPT_HEAD_COMPRESS, MAGAT_OPT_CONV_TM, MAGAT_OPT_CSR_FUSED, MAGAT_OPT_LAT_AGENTS, MAGAT_OPT_GAT_WIDE_FROM, MAGAT_OPT_COUNT
+  MAGAT_OPT_CONV_BNFILL, MAGAT_OPT_HEAD_COMPRESS, MAGAT_OPT_CONV_TM, MAGAT_OPT_CSR_FUSED, MAGAT_OPT_LAT_AGENTS, MAGAT_OPT_GAT_WIDE_FROM,
+  MAGAT_OPT_CHAIN_TILE16, MAGAT_OPT_COUNT
 };
 int magat_opt(int id);
 // hipFuncAttributeMaxDynamicSharedMemorySize, remembered per (kernel slot, device)
@@ -147,6 +156,7 @@ enum MagatLdsSlot {
   MAGAT_LDS_SIM_MOVE_WIDE,                      // sim_frontend.hip: the move step with its cell grid in a workspace, N near 4096
   MAGAT_LDS_SIM_MAPF_LNS,                       // sim_mapf_lns.hip: the R layers
   MAGAT_LDS_SIM_MAPF_CBS,                       // sim_mapf_cbs.hip: the R layers of horizons above 128
+  MAGAT_LDS_BLOCK_FULL_P16,                     // block_fused.hip: block_full_p_kernel<true> (layer3.conv2 on 16-row tiles)
   MAGAT_LDS_END
 };
 static_assert(MAGAT_LDS_END <= MAGAT_LDS_SLOTS, "LDS attribute slots");

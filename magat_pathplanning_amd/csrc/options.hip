@@ -52,6 +52,9 @@ const OptEntry kOpts[MAGAT_OPT_COUNT] = {
                              // (gat_mid.hip, X fragments in registers) instead of what follows gat_mfma.hip's N <= 102: the two-launch
                              // form up to 105 agents (0.36 against 0.25 ms per 512 instances), the CSR kernels above (0.76 against
                              // 0.27 ms at 128 agents).  Values below 103 mean 103, above 128 never
+    {"CHAIN_TILE16", 2},     // one-launch chain kernel: layer3.conv2 on 16-row tiles (v_mfma_f32_16x16x32_f16: a higher clock, 132
+                             // instead of 138 half-tile-taps; another summation order than the 32-row form): 0 = never, 1 = always,
+                             // 2 = from MAGAT_CHAIN_TILE16_FROM agents (magat_encoder_desc.form_agents when set)
 };
 
 int g_val[MAGAT_OPT_COUNT];

@@ -14,6 +14,8 @@ the "encoder pack" consumed by magat_encoder_forward_f32 (include/magat_hip.h):
   off[16] compressMLP weight [G][n_feat]                   off[17] compressMLP bias [G]
   off[18..23] empty since round 5 (the bf16x3 weight planes of round 1's bf16x6 flavour)
   off[24+2l], off[25+2l] the same two weights as f16x2 planes of (w * 2^e) + one float32 2^-e  ("f16x3" GEMM, in_fmt 4)
+  off[30] first K-permuted copy of those planes (plane-granule activations); off[31] layer3.conv2 in 16-row fragments
+          (pack_block3_tile16; option CHAIN_TILE16)
 
 Every offset is a multiple of 4 floats.  Folding is done in float64 and stored as float32.
 """
@@ -159,7 +161,8 @@ def fold_resnet(sd, H=11, W=11, pre="ConvLayers.0", linear=None, compress=None):
             nxt = sorted(o for o in offs[:18] if o > offs[slot])
             return pack[offs[slot]:(nxt[0] if nxt else n_f32)].reshape(128, -1)
         chain3_off = pack.numel()
-        pack = torch.cat([pack] + pack_block3_weights(rows3(10)[:, :9 * 64], rows3(12)[:, :9 * 128 + 64])).contiguous()
+        blocks3 = pack_block3_weights(rows3(10)[:, :9 * 64], rows3(12)[:, :9 * 128 + 64])
+        pack = torch.cat([pack] + blocks3).contiguous()
     # the head once more as f16x2 planes (in_fmt 4): with the layer3 kernel's pooled output the head is a plain valid conv
     # over the pooled map, 5x faster on the split-MFMA kernel than on the float32 matrix cores
     nxt = sorted(o for o in offs[:18] if o > offs[14])
@@ -200,6 +203,11 @@ def fold_resnet(sd, H=11, W=11, pre="ConvLayers.0", linear=None, compress=None):
         w1rows = pack[offs[2]:(nxt[0] if nxt else n_f32)][:32 * 288].reshape(32, 288)
         l1frag_off = pack.numel()
         pack = torch.cat([pack, pack_chain_weights(w1rows, 32, 0)]).contiguous()
+    # layer3.conv2 once more in 16-row fragments, for the large-batch form of the one-launch chain kernel (option CHAIN_TILE16);
+    # offs[31] != 0 marks their presence (magat_encoder_desc.off[31])
+    if chain3_off:
+        offs[31] = pack.numel()
+        pack = torch.cat([pack, pack_block3_tile16(blocks3)]).contiguous()
     meta = dict(variant=0 if large else 1, H=H, W=W, n_feat=n_feat, n_comp=n_comp, clast=clast, chain=chain_off,
                 chain3=chain3_off, head16=head16_off, comp16=comp16_off, l1frag=l1frag_off, headfrag=headfrag_off,
                 compfrag=compfrag_off)
@@ -275,6 +283,23 @@ def pack_block3_weights(w1, w2):
     e = 0 if mx == 0.0 else 13 - int(math.floor(math.log2(mx)))
     e = max(-14, min(e, 24))
     return [pack_chain_weights(w1, 64, 0), pack_chain_weights(lo, 64, 0, e=e), pack_chain_weights(hi, 64, 64, e=e)]
+
+
+def pack_block3_tile16(blocks):
+    """The two conv2 blocks of pack_block3_weights once more in 16-ROW fragments (csrc/block_walk.h walk16: layer3.conv2 as
+    v_mfma_f32_16x16x32_f16 products): per channel tile and 32-channel k step (two consecutive 16-channel steps of a tap, or of
+    the residual segment) four 1 KB blocks [half 2][plane 2][64 lanes][8 halves] - lane l holds, for output channel
+    32 ct + 16 half + (l & 15), the 8 weights that lane 32 ((l >> 4) & 1) + 16 half + (l & 15) holds in 16-channel step
+    2 k32 + (l >> 5) of the 32-row pack: a permutation of its 16-byte pieces, same planes, same scale.  Returns one float32
+    tensor: block a (73 728 floats), then block b (81 920)."""
+    out = []
+    for blk in blocks[1:3]:
+        h = blk[:-4].contiguous().view(torch.int16)
+        s16 = h.numel() // (4 * 2 * 64 * 8)
+        assert s16 % 2 == 0 and h.numel() == 4 * s16 * 1024
+        # [ct][k32][step of the pair = kq >> 1][plane][lane half = kq & 1][half][column][8] -> [ct][k32][half][plane][kq][column][8]
+        out.append(h.view(4, s16 // 2, 2, 2, 2, 2, 16, 8).permute(0, 1, 5, 3, 2, 4, 6, 7).contiguous().view(-1).view(torch.float32))
+    return torch.cat(out)
 
 
 def chain_channel(ks, fh, i):
