@@ -301,6 +301,39 @@ int magat_sim_guided_states_wide(const uint8_t* map, int map_batched, int H, int
                                  float* x, int FOV, int B, int N, int mode, int dynamic_obstacles, uint8_t* agent_view,
                                  void* workspace, size_t workspace_bytes, void* stream);
 
+/* magat_sim_replayed_states[_wide]: MAGAT_GUIDE_SEMI without agent_view - the state of ANY step of a known schedule in one call
+ *   (expert.py: expert_samples(replay=True); memory.py: ExpertMemory(replay=True)).  The maps are static and the SEMI search
+ *   writes the map's own crop into the remembered map, so after step t that map is seen AND blocked, where `seen` is the union of
+ *   the FOV x FOV windows of the agent's cells 0 .. t that lie on the map (an agent whose goal is off the map is never searched
+ *   and has seen nothing) and blocked = off the map or map != 0.  Per (row, agent) the wave rebuilds `seen` as bit masks a padded
+ *   row - in registers (narrow) or in the LDS of the parent bits, which the search needs only afterwards (wide) - and then runs the
+ *   search, goal marker, path drawing and write-out of magat_sim_guided_states[_wide]: the same tensors as stepping the case with a
+ *   carried agent_view.  pos / goal (B,N,2) are the row's current cells and goals, as there.  The history of row b is step
+ *   row_step[b] of case row_case[b] (int32, clamped into the source), the cell of agent n at step s is
+ *     pos_table[case][s][n]             (cases, T, N, 2) int32, magat_sim_expert_schedule's layout, T <= 1024;            or
+ *     cells[case][n][s] = row << 8 | col  while s < lengths[case][n], goal[case][n] behind it - magat_sim_expert_pick's store:
+ *                                       cells (cases, N, Lcap) uint16, lengths (cases, N), goal (cases, N, 2); steps up to 1023.
+ *   Exactly one of the two is given (the other's pointers NULL).  Steps are loaded 64 at a time; a step that repeats the cell
+ *   before it costs nothing.  Checks, before anything is launched: the operands and shape limits of the guided entry of the
+ *   same width with its codes; history or row_case / row_step NULL, no source, or a store with a pointer missing
+ *   MAGAT_ERR_NULL; both sources MAGAT_ERR_UNSUPPORTED; cases, T (table) or Lcap (store) <= 0 MAGAT_ERR_BAD_SHAPE; T > 1024
+ *   MAGAT_ERR_UNSUPPORTED; then (wide) the workspace checks of magat_sim_guided_states_wide - the same workspace size.  One
+ *   launch, profiling tag 26 ("sim_guided"), form counter 24 ("sim_replay", numbered in the library); no host synchronisation. */
+typedef struct magat_sim_history_desc {
+  const int32_t* row_case;    /* (B,) */
+  const int32_t* row_step;    /* (B,) */
+  const int32_t* pos_table;   /* (cases, T, N, 2), or NULL */
+  const uint16_t* cells;      /* (cases, N, Lcap), or NULL with lengths and goal */
+  const int32_t* lengths;     /* (cases, N) */
+  const int32_t* goal;        /* (cases, N, 2) */
+  int32_t cases, T, Lcap;
+} magat_sim_history_desc;
+int magat_sim_replayed_states(const uint8_t* map, int map_batched, int H, int W, const int32_t* pos, const int32_t* goal,
+                              float* x, int FOV, int B, int N, const magat_sim_history_desc* history, void* stream);
+int magat_sim_replayed_states_wide(const uint8_t* map, int map_batched, int H, int W, const int32_t* pos, const int32_t* goal,
+                                   float* x, int FOV, int B, int N, const magat_sim_history_desc* history, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+
 /* magat_sim_move: multiRobotSimNew.move + check_collision (utils/new_simulator.py:334-454, 471-520),
  *   batched: action key = argmax of the 5 logits (convectToActionKey_softmax :863-869; or given keys `actions_in`), proposed
  *   move (up 0, left 1, down 2, right 3, stop 4), shielding in the reference's order - out of the arena, face-to-face

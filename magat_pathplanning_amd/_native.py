@@ -23,7 +23,7 @@ TAG_ACTIONS = 12
 # magat_form_count ids (include/magat_hip.h MAGAT_FORM_*)
 FORMS = {"head_longk": 0, "head_splitk": 1, "gat_pack": 2, "gat_persist": 3, "gat_hsplit": 4, "chain_persist": 5,
          "head_compress": 6, "guard_one": 7, "csr_fused": 8, "gat_mid": 9, "chain_lat": 10, "head_lat": 11, "guard_lat": 12, "stem_lat": 13, "actions_tail": 14, "gnn_dense": 15, "sim_guided": 16, "sim_expert": 17, "sim_mapf": 18, "sim_mapf_lns": 19, "sim_mapf_audit": 20, "sim_mapf_cbs": 21, "sim_mapf_ecbs": 22,
-         "chain_tile16": 23}
+         "chain_tile16": 23, "sim_replay": 24}
 TAG_GNN_DENSE = 25
 TAG_SIM_GUIDED = 26
 TAG_SIM_EXPERT = 27
@@ -88,6 +88,13 @@ class SimStepDesc(ctypes.Structure):
                 ("done_out", ctypes.c_void_p), ("flowtime_out", ctypes.c_void_p), ("makespan_out", ctypes.c_void_p)]
 
 
+class SimHistoryDesc(ctypes.Structure):
+    """magat_sim_history_desc (include/magat_hip.h)."""
+    _fields_ = [("row_case", ctypes.c_void_p), ("row_step", ctypes.c_void_p), ("pos_table", ctypes.c_void_p),
+                ("cells", ctypes.c_void_p), ("lengths", ctypes.c_void_p), ("goal", ctypes.c_void_p),
+                ("cases", ctypes.c_int32), ("T", ctypes.c_int32), ("Lcap", ctypes.c_int32)]
+
+
 _I, _P, _Z = ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t
 _SIGNATURES = {
     "magat_abi_version": (ctypes.c_int, []),
@@ -133,6 +140,8 @@ _SIGNATURES = {
     "magat_sim_move": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "magat_sim_guided_states_wide_workspace_bytes": (_Z, [_I] * 5),
     "magat_sim_guided_states_wide": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P, _P, _Z, _P]),
+    "magat_sim_replayed_states": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _I, ctypes.POINTER(SimHistoryDesc), _P]),
+    "magat_sim_replayed_states_wide": (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _I, _I, ctypes.POINTER(SimHistoryDesc), _P, _Z, _P]),
     "magat_sim_move_wide_workspace_bytes": (_Z, [_I] * 4),
     "magat_sim_move_wide": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _Z, _P]),
     "magat_sim_step_wide": (_I, [ctypes.POINTER(SimStepDesc), _P, _Z, _P]),

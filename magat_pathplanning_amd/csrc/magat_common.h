@@ -58,10 +58,11 @@ void magat_form_note(int id);      // which form a launch took (MAGAT_FORM_*; pr
 #define MAGAT_FORM_SIM_MAPF_CBS 21    // magat_sim_mapf_cbs launched its one-wave-per-case kernel
 #define MAGAT_FORM_SIM_MAPF_ECBS 22   // magat_sim_mapf_ecbs launched its one-wave-per-case kernel
 #define MAGAT_FORM_CHAIN_TILE16 23   // magat_block_full launched the form with layer3.conv2 on 16-row tiles (option CHAIN_TILE16)
-#define MAGAT_FORMS_TABLE 24
+#define MAGAT_FORM_SIM_REPLAY 24     // magat_sim_replayed_states or its wide form launched (SemiLG from the schedule; tag MAGAT_TAG_SIM_GUIDED)
+#define MAGAT_FORMS_TABLE 25
 static_assert(MAGAT_PROF_TAGS_ALL >= MAGAT_PROF_TAGS && MAGAT_FORMS_ALL >= MAGAT_FORMS, "internal tag / form tables");
 static_assert(MAGAT_PROF_TAGS_TABLE > MAGAT_TAG_SIM_MAPF_ECBS && MAGAT_PROF_TAGS_TABLE >= MAGAT_PROF_TAGS_ALL &&
-              MAGAT_FORMS_TABLE > MAGAT_FORM_CHAIN_TILE16 && MAGAT_FORMS_TABLE >= MAGAT_FORMS_ALL, "internal tag / form tables");
+              MAGAT_FORMS_TABLE > MAGAT_FORM_SIM_REPLAY && MAGAT_FORMS_TABLE >= MAGAT_FORMS_ALL, "internal tag / form tables");
 
 // bf16x6 split-MFMA GEMM (conv_gemm_bf16x6.hip), reached through magat_conv_gemm_f32 when desc->in_fmt == 1
 int magat_conv_gemm_bf16x6(const magat_conv_gemm_desc* d, hipStream_t st);

@@ -1,5 +1,6 @@
 // A*-guided state encodings of the reference's state encoder on the device (dataloader/statetransformer_Guidance.py:241-495,
 // config.guidance = LocalG_S|SD, GlobalG_S|SD, SemiLG_S|SD; the planner is offlineExpert/a_star.py:75-189).
+//   magat_sim_replayed_states the SemiLG encoding with the remembered maps rebuilt from the agents' schedules (no agent_view)
 //   magat_sim_guided_states   obstacle map + agent / goal coordinates (+ the agents' remembered maps) -> the
 //                             (B,N,3,FOV+2,FOV+2) {0,1} state tensor whose channel 1 holds the cells of the reference's A* path
 // The output is integer work and must EQUAL the reference's, so the search is the reference's step for step:
@@ -20,11 +21,14 @@ namespace {
 constexpr int GUIDE_MAX_CANVAS = 64;      // rows / columns of the search canvas: a row is one 64-bit mask, coordinates take 6 bits
 constexpr size_t GUIDE_LDS_HEAD = 3 * GUIDE_MAX_CANVAS * sizeof(unsigned long long) + 3 * GUIDE_MAX_WT * sizeof(unsigned);
 
+// REPLAY (magat_sim_replayed_states): SemiLG without `view` - the wave first rebuilds which cells the agent has seen from its
+// schedule (hist; sim_guidance_parts.h), one 64-bit mask per padded row held by lane = row, and the grid reads that.
+template <bool REPLAY>
 __global__ __launch_bounds__(64) void guided_states_kernel(const uint8_t* __restrict__ map, long long map_stride, int H, int Wm,
                                                            const int* __restrict__ pos, const int* __restrict__ goal,
                                                            float* __restrict__ x, int fov, int N, int mode, int dyn,
-                                                           uint8_t* __restrict__ view) {
-  extern __shared__ __align__(16) unsigned char smem_raw[];
+                                                           uint8_t* __restrict__ view, GuideHistory hist) {
+  GUIDE_DYN_LDS(smem_raw);
   const int lane = threadIdx.x;
   const long long ag = blockIdx.x;                       // b * N + n
   const int b = (int)(ag / N);
@@ -48,9 +52,18 @@ __global__ __launch_bounds__(64) void guided_states_kernel(const uint8_t* __rest
   const bool search = pos_in && goal_in;
   // the agents and the obstacles inside the FOV; SemiLG writes the obstacle crop into the agent's remembered map (guide_window)
   const int Hp = H + 2 * half, Wp = Wm + 2 * half;
-  uint8_t* vw = (semi && search) ? view + ag * (long long)Hp * Wp : nullptr;
+  uint8_t* vw = (!REPLAY && semi && search) ? view + ag * (long long)Hp * Wp : nullptr;
   guide_window(mp, H, Wm, pos, b, N, cx, cy, fov, wmap, wocc, vw, lane);
   GUIDE_WAVE_SYNC();
+  unsigned long long seen = 0ull;                        // REPLAY: padded row `lane` of the cells seen so far
+  if constexpr (REPLAY) {
+    if (search) {
+      const unsigned long long span = (1ull << fov) - 1ull;      // a window's columns, shifted to its first
+      guide_history_walk(hist, b, (int)(ag - (long long)b * N), N, H, Wm, lane, [&](int ux, int uy) {
+        if (lane >= ux && lane < ux + fov) seen |= span << uy;
+      });
+    }
+  }
   int grow, gcol;
   guide_goal_marker(cx, cy, gx, gy, goal_in, fov, grow, gcol);
   const int Hc = local ? Wt : H + 2 * half + 2, Wc = local ? Wt : Wm + 2 * half + 2;
@@ -75,7 +88,14 @@ __global__ __launch_bounds__(64) void guided_states_kernel(const uint8_t* __rest
   } else if (search) {
     // the padded map or the agent's remembered map, the agents in the FOV, the free ring, the cleared goal (guide_canvas_cell)
     for (int r = 0; r < Hc; ++r) {
-      const int val = guide_canvas_cell(r, lane, Hc, Wc, mp, H, Wm, cx, cy, fov, wmap, wocc, semi || dyn, semi, vw, tx, ty);
+      int val;
+      if constexpr (REPLAY) {
+        const unsigned long long row = (r >= 1 && r < Hc - 1) ? guide_lane_u64(seen, r - 1) : 0ull;
+        val = guide_canvas_cell_replay(r, lane, Hc, Wc, mp, H, Wm, cx, cy, fov, wmap, wocc,
+                                       lane >= 1 && ((row >> ((lane - 1) & 63)) & 1ull), tx, ty);
+      } else {
+        val = guide_canvas_cell(r, lane, Hc, Wc, mp, H, Wm, cx, cy, fov, wmap, wocc, semi || dyn, semi, vw, tx, ty);
+      }
       const unsigned long long m = __ballot(val != 0);
       if (lane == 0) unavail[r] = m;
     }
@@ -175,9 +195,32 @@ extern "C" int magat_sim_guided_states(const uint8_t* map, int map_batched, int 
   hipStream_t st = static_cast<hipStream_t>(stream);
   magat_form_note(MAGAT_FORM_SIM_GUIDED);
   const int pid = magat_prof_begin(MAGAT_TAG_SIM_GUIDED, st);
-  hipLaunchKernelGGL(guided_states_kernel, dim3((unsigned)((long long)B * N)), dim3(64), lds, st, map,
+  hipLaunchKernelGGL(guided_states_kernel<false>, dim3((unsigned)((long long)B * N)), dim3(64), lds, st, map,
                      map_batched ? (long long)H * W : 0LL, H, W, pos, goal, x, FOV, N, mode, dynamic_obstacles ? 1 : 0,
-                     mode == MAGAT_GUIDE_SEMI ? agent_view : nullptr);
+                     mode == MAGAT_GUIDE_SEMI ? agent_view : nullptr, GuideHistory{});
+  magat_prof_end(pid, st);
+  return magat_check_launch();
+}
+
+extern "C" int magat_sim_replayed_states(const uint8_t* map, int map_batched, int H, int W, const int32_t* pos,
+                                         const int32_t* goal, float* x, int FOV, int B, int N,
+                                         const magat_sim_history_desc* history, void* stream) {
+  if (!map || !pos || !goal || !x) return MAGAT_ERR_NULL;
+  if (B <= 0 || N <= 0 || H <= 0 || W <= 0 || FOV <= 0 || !(FOV & 1)) return MAGAT_ERR_BAD_SHAPE;
+  if (FOV < 3 || FOV + 2 > GUIDE_MAX_WT) return MAGAT_ERR_UNSUPPORTED;
+  if ((long long)B * N > 0x7fffffffLL) return MAGAT_ERR_UNSUPPORTED;
+  const int half = FOV / 2;
+  if (H > GUIDE_MAX_CANVAS - 2 * half - 2 || W > GUIDE_MAX_CANVAS - 2 * half - 2) return MAGAT_ERR_UNSUPPORTED;
+  GuideHistory hist;
+  const int rc = guide_history_check(history, hist);
+  if (rc != MAGAT_OK) return rc;
+  const int Hc = H + 2 * half + 2, Wc = W + 2 * half + 2;
+  const size_t lds = GUIDE_LDS_HEAD + (size_t)Hc * Wc * sizeof(unsigned);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  magat_form_note(MAGAT_FORM_SIM_REPLAY);
+  const int pid = magat_prof_begin(MAGAT_TAG_SIM_GUIDED, st);
+  hipLaunchKernelGGL(guided_states_kernel<true>, dim3((unsigned)((long long)B * N)), dim3(64), lds, st, map,
+                     map_batched ? (long long)H * W : 0LL, H, W, pos, goal, x, FOV, N, MAGAT_GUIDE_SEMI, 1, nullptr, hist);
   magat_prof_end(pid, st);
   return magat_check_launch();
 }

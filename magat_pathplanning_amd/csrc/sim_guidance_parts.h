@@ -10,6 +10,13 @@ constexpr int GUIDE_MAX_WT = 32;          // FOV + 2: a window row is one 32-bit
 
 #define GUIDE_WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_SEQ_CST, "wavefront"); __builtin_amdgcn_wave_barrier(); } while (0)
 
+// the kernels' dynamic LDS (tools/host_wave compiles them for the host, where it is the stand-in's buffer)
+#ifdef MAGAT_HOST_WAVE
+#define GUIDE_DYN_LDS(var) unsigned char* var = reinterpret_cast<unsigned char*>(host_wave::dyn_lds)
+#else
+#define GUIDE_DYN_LDS(var) extern __shared__ __align__(16) unsigned char var[]
+#endif
+
 template <int CTRL>
 __device__ __forceinline__ unsigned long long guide_dpp_u64(unsigned long long v) {
   const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)v, CTRL, 0xf, 0xf, true);
@@ -90,6 +97,103 @@ __device__ __forceinline__ int guide_canvas_cell(int r, int c, int Hc, int Wc, c
     if (r == tx && c == ty && val == 1) val = 0;
   }
   return val;
+}
+
+// ---- the replay form of SemiLG (magat_sim_replayed_states[_wide]): the agent's remembered map is rebuilt from its schedule.
+// The maps are static and guide_window writes the map's own crop, so the view after step t is
+//   view(r, c) = seen(r, c) AND blocked(r - half, c - half),   seen = the union of the FOV x FOV windows (padded rows cell.row ..
+//   cell.row + FOV - 1, columns cell.col .. cell.col + FOV - 1) of the agent's cells 0 .. t that lie on the map
+// and only `seen` has to be rebuilt - as row masks, right before the search.
+constexpr int GUIDE_MAX_STEPS = 1024;     // steps of a history: the wide horizon
+
+// Where the cells of a batch row come from: row b is step row_step[b] of case row_case[b]; agent n's cell at step s is
+// table[case][s][n] (expert_schedule's layout), or - the memory's store - cells[case][n][s] = row << 8 | col while s < lengths
+// [case][n] and goal[case][n] behind it (expert_schedule_kernel's / expert_pick_kernel's rule).  Exactly one source is set.
+struct GuideHistory {
+  const int* row_case;         // (B,)
+  const int* row_step;         // (B,)
+  const int* table;            // (cases, T, N, 2), or null
+  const uint16_t* cells;       // (cases, N, Lcap), or null
+  const int* lengths;          // (cases, N)
+  const int* goal;             // (cases, N, 2)
+  int cases, T, Lcap;
+};
+
+// Calls window(row, col) - wave-uniform arguments, every lane - once for each cell of agent n's history in batch row b that lies
+// on the map; a cell that repeats the one before it (a wait, the padding behind a path) is skipped.  The steps are loaded 64 at a
+// time, lane = step, and broadcast from there.  case and step are clamped into the source: nothing is read outside it.
+template <typename F>
+__device__ __forceinline__ void guide_history_walk(const GuideHistory& h, int b, int n, int N, int H, int Wm, int lane, F&& window) {
+  int c = __builtin_amdgcn_readfirstlane(h.row_case[b]), t = __builtin_amdgcn_readfirstlane(h.row_step[b]);
+  const int tmax = (h.table ? h.T : GUIDE_MAX_STEPS) - 1;
+  c = c < 0 ? 0 : (c >= h.cases ? h.cases - 1 : c);
+  t = t < 0 ? 0 : (t > tmax ? tmax : t);
+  const long long ag = (long long)c * N + n;
+  int L = 0, gx = 0, gy = 0;
+  if (!h.table) {
+    L = h.lengths[ag];
+    L = L < 0 ? 0 : (L > h.Lcap ? h.Lcap : L);      // never read behind the row
+    gx = h.goal[2 * ag];
+    gy = h.goal[2 * ag + 1];
+  }
+  int lastx = -1, lasty = -1;
+  for (int s0 = 0; s0 <= t; s0 += 64) {
+    const int s = s0 + lane;
+    int rx = -1, ry = -1;
+    if (s <= t) {
+      if (h.table) {
+        const long long i = (((long long)c * h.T + s) * N + n) * 2;
+        rx = h.table[i];
+        ry = h.table[i + 1];
+      } else if (s < L) {
+        const unsigned v = h.cells[ag * h.Lcap + s];
+        rx = (int)(v >> 8);
+        ry = (int)(v & 255u);
+      } else {
+        rx = gx;
+        ry = gy;
+      }
+    }
+    const int cnt = t - s0 + 1 < 64 ? t - s0 + 1 : 64;
+    for (int j = 0; j < cnt; ++j) {
+      const int ux = __builtin_amdgcn_readlane(rx, j), uy = __builtin_amdgcn_readlane(ry, j);
+      if (ux == lastx && uy == lasty) continue;
+      lastx = ux;
+      lasty = uy;
+      if (ux >= 0 && ux < H && uy >= 0 && uy < Wm) window(ux, uy);
+    }
+  }
+}
+
+// guide_canvas_cell of the replay form: a cell outside the current FOV holds `seen` AND blocked(cell) - a padding-ring cell that
+// was never seen is free, a seen one is blocked: what the carried byte view holds.  seen: the bit of padded cell (r - 1, c - 1),
+// read only inside the ring.  The agents inside the FOV always block (SemiLG).
+__device__ __forceinline__ int guide_canvas_cell_replay(int r, int c, int Hc, int Wc, const uint8_t* __restrict__ mp, int H, int Wm,
+                                                        int cx, int cy, int fov, const unsigned* wmap, const unsigned* wocc, bool seen,
+                                                        int tx, int ty) {
+  int val = 0;
+  if (r >= 1 && r < Hc - 1 && c >= 1 && c < Wc - 1) {
+    const int half = fov / 2;
+    const int mr = r - 1 - half, mc = c - 1 - half;
+    const int fa = mr - cx + half, fc = mc - cy + half;
+    const bool infov = fa >= 0 && fa < fov && fc >= 0 && fc < fov;
+    if (infov) val = (int)((wmap[fa] >> fc) & 1u) + (int)((wocc[fa] >> fc) & 1u);
+    else if (seen) val = (mr >= 0 && mr < H && mc >= 0 && mc < Wm) ? (mp[(long long)mr * Wm + mc] != 0 ? 1 : 0) : 1;
+    if (r == tx && c == ty && val == 1) val = 0;
+  }
+  return val;
+}
+
+// the history's checks of the two replay entry points, before anything is launched (MAGAT_OK, or the code to return)
+inline int guide_history_check(const magat_sim_history_desc* h, GuideHistory& out) {
+  if (!h || !h->row_case || !h->row_step) return MAGAT_ERR_NULL;
+  const bool table = h->pos_table != nullptr, store = h->cells || h->lengths || h->goal;
+  if (table && store) return MAGAT_ERR_UNSUPPORTED;      // both sources
+  if (!table && !(h->cells && h->lengths && h->goal)) return MAGAT_ERR_NULL;      // neither, or half a store
+  if (h->cases <= 0 || (table ? h->T <= 0 : h->Lcap <= 0)) return MAGAT_ERR_BAD_SHAPE;
+  if (table && h->T > GUIDE_MAX_STEPS) return MAGAT_ERR_UNSUPPORTED;
+  out = GuideHistory{h->row_case, h->row_step, h->pos_table, h->cells, h->lengths, h->goal, h->cases, table ? h->T : 0, table ? 0 : h->Lcap};
+  return MAGAT_OK;
 }
 
 // (3, FOV+2, FOV+2) floats of one agent: channel 0 the window's obstacles, 1 the path mask, 2 the window's agents

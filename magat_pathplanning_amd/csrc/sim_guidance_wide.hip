@@ -1,6 +1,7 @@
 // The wide form of the A*-guided state encodings: GlobalG_S|SD and SemiLG_S|SD on maps up to 256 x 256 (sim_guidance.hip holds
 // the form for canvases up to 64 x 64, LocalG and the algorithm's description; the pieces both share are sim_guidance_parts.h).
 //   magat_sim_guided_states_wide                   the arguments of magat_sim_guided_states + a workspace
+//   magat_sim_replayed_states_wide                 SemiLG with the remembered maps rebuilt from the agents' schedules (no agent_view)
 //   magat_sim_guided_states_wide_workspace_bytes   min(B N, GUIDEW_CAP) * canvas rows * canvas columns * 8 bytes
 // The search is the narrow form's step for step - pop = lexicographic minimum of (f, g, row, col), closed at push with the first
 // pusher as parent, neighbours up, left, down, right - so the tensors EQUAL the reference's.  What changes is where things live:
@@ -32,12 +33,15 @@ inline size_t guidew_lds_bytes(int Hc, int nw) { return (size_t)3 * Hc * nw * si
 
 __device__ __forceinline__ int guidew_abs(int v) { return v < 0 ? -v : v; }
 
-template <int NW>
+// REPLAY (magat_sim_replayed_states_wide): SemiLG without `view` - the cells the agent has seen so far are rebuilt from its
+// schedule (hist; sim_guidance_parts.h) as NW words a padded row in par0's storage, which the search does not need before the grid
+// is built; par0 is zeroed again behind the grid, so the form takes no LDS of its own.
+template <int NW, bool REPLAY>
 __global__ __launch_bounds__(64) void guided_states_wide_kernel(const uint8_t* __restrict__ map, long long map_stride, int H, int Wm,
                                                                 const int* __restrict__ pos, const int* __restrict__ goal,
                                                                 float* __restrict__ x, int fov, int N, long long agents, int semi,
-                                                                int dyn, uint8_t* __restrict__ view, u64* workspace) {
-  extern __shared__ __align__(16) unsigned char smem_raw[];
+                                                                int dyn, uint8_t* __restrict__ view, u64* workspace, GuideHistory hist) {
+  GUIDE_DYN_LDS(smem_raw);
   const int lane = threadIdx.x;
   const int Wt = fov + 2, half = fov / 2;
   const int Hc = H + 2 * half + 2, Wc = Wm + 2 * half + 2, Hp = H + 2 * half, Wp = Wm + 2 * half;
@@ -58,8 +62,19 @@ __global__ __launch_bounds__(64) void guided_states_wide_kernel(const uint8_t* _
     GUIDE_WAVE_SYNC();
     const bool pos_in = cx >= 0 && cx < H && cy >= 0 && cy < Wm, goal_in = gx >= 0 && gx < H && gy >= 0 && gy < Wm;
     const bool search = pos_in && goal_in;
-    uint8_t* vw = (semi && search) ? view + ag * (long long)Hp * Wp : nullptr;
+    uint8_t* vw = (!REPLAY && semi && search) ? view + ag * (long long)Hp * Wp : nullptr;
     guide_window(mp, H, Wm, pos, b, N, cx, cy, fov, wmap, wocc, vw, lane);
+    if constexpr (REPLAY) {
+      if (search) {
+        // a window is FOV rows of at most two words: lane = (row, which word); the ORs of different cells commute
+        guide_history_walk(hist, b, (int)(ag - (long long)b * N), N, H, Wm, lane, [&](int ux, int uy) {
+          const int k = (uy >> 6) + (lane & 1);
+          const int first = uy > 64 * k ? uy - 64 * k : 0, last = uy + fov - 1 < 64 * k + 63 ? uy + fov - 1 - 64 * k : 63;
+          if (lane < 2 * fov && k < NW && last >= first)
+            atomicOr(&par0[(ux + (lane >> 1)) * NW + k], ((1ull << (last - first + 1)) - 1ull) << first);
+        });
+      }
+    }
     GUIDE_WAVE_SYNC();
     const int sx = cx + half + 1, sy = cy + half + 1, tx = gx + half + 1, ty = gy + half + 1;      // start and goal on the canvas
     bool found = false;
@@ -68,13 +83,23 @@ __global__ __launch_bounds__(64) void guided_states_wide_kernel(const uint8_t* _
       for (int r = 0; r < Hc; ++r) {
 #pragma unroll
         for (int k = 0; k < NW; ++k) {
-          const int val = guide_canvas_cell(r, 64 * k + lane, Hc, Wc, mp, H, Wm, cx, cy, fov, wmap, wocc, semi || dyn, semi != 0, vw,
-                                            tx, ty);
+          const int c = 64 * k + lane;
+          int val;
+          if constexpr (REPLAY) {
+            const bool inner = r >= 1 && r < Hc - 1 && c >= 1 && c < Wc - 1;
+            val = guide_canvas_cell_replay(r, c, Hc, Wc, mp, H, Wm, cx, cy, fov, wmap, wocc,
+                                           inner && has_bit(par0[(r - 1) * NW + ((c - 1) >> 6)], (c - 1) & 63), tx, ty);
+          } else {
+            val = guide_canvas_cell(r, c, Hc, Wc, mp, H, Wm, cx, cy, fov, wmap, wocc, semi || dyn, semi != 0, vw, tx, ty);
+          }
           const u64 m = __ballot(val != 0);
           if (lane == 0) unavail[r * NW + k] = m;
         }
       }
       GUIDE_WAVE_SYNC();
+      if constexpr (REPLAY) {
+        for (int i = lane; i < Hc * NW; i += 64) par0[i] = 0ull;      // the seen cells are used up: the parent bits start clear
+      }
       // ---- A*
       if (lane == 0) {
         unavail[sx * NW + (sy >> 6)] |= 1ull << (sy & 63);
@@ -162,6 +187,45 @@ extern "C" size_t magat_sim_guided_states_wide_workspace_bytes(int B, int N, int
   return (size_t)groups * (size_t)(H + 2 * half + 2) * (size_t)(W + 2 * half + 2) * sizeof(u64);
 }
 
+namespace {
+
+// the launch both entry points share: the kernel of the canvas's word count, with or without the replay
+template <bool REPLAY>
+int guidew_launch(const uint8_t* map, int map_batched, int H, int W, const int32_t* pos, const int32_t* goal, float* x, int FOV, int B,
+                  int N, int semi, int dyn, uint8_t* view, void* workspace, const GuideHistory& hist, int form, void* stream) {
+  const int half = FOV / 2, Hc = H + 2 * half + 2, Wc = W + 2 * half + 2, nw = guidew_words(Wc);
+  const long long agents = (long long)B * N;
+  const dim3 grid((unsigned)(agents < GUIDEW_CAP ? agents : GUIDEW_CAP)), block(64);
+  const size_t lds = guidew_lds_bytes(Hc, nw);                 // <= 3 * 286 * 5 * 8 + 384 bytes
+  const long long map_stride = map_batched ? (long long)H * W : 0LL;
+  u64* ws = static_cast<u64*>(workspace);
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  magat_form_note(form);
+  const int pid = magat_prof_begin(MAGAT_TAG_SIM_GUIDED, st);
+  switch (nw) {
+    case 2:
+      hipLaunchKernelGGL((guided_states_wide_kernel<2, REPLAY>), grid, block, lds, st, map, map_stride, H, W, pos, goal, x, FOV, N, agents,
+                         semi, dyn, view, ws, hist);
+      break;
+    case 3:
+      hipLaunchKernelGGL((guided_states_wide_kernel<3, REPLAY>), grid, block, lds, st, map, map_stride, H, W, pos, goal, x, FOV, N, agents,
+                         semi, dyn, view, ws, hist);
+      break;
+    case 4:
+      hipLaunchKernelGGL((guided_states_wide_kernel<4, REPLAY>), grid, block, lds, st, map, map_stride, H, W, pos, goal, x, FOV, N, agents,
+                         semi, dyn, view, ws, hist);
+      break;
+    default:
+      hipLaunchKernelGGL((guided_states_wide_kernel<GUIDEW_MAX_WORDS, REPLAY>), grid, block, lds, st, map, map_stride, H, W, pos, goal, x,
+                         FOV, N, agents, semi, dyn, view, ws, hist);
+      break;
+  }
+  magat_prof_end(pid, st);
+  return magat_check_launch();
+}
+
+}  // namespace
+
 extern "C" int magat_sim_guided_states_wide(const uint8_t* map, int map_batched, int H, int W, const int32_t* pos,
                                             const int32_t* goal, float* x, int FOV, int B, int N, int mode, int dynamic_obstacles,
                                             uint8_t* agent_view, void* workspace, size_t workspace_bytes, void* stream) {
@@ -175,35 +239,26 @@ extern "C" int magat_sim_guided_states_wide(const uint8_t* map, int map_batched,
   if (!workspace) return MAGAT_ERR_NULL;
   if (workspace_bytes < magat_sim_guided_states_wide_workspace_bytes(B, N, H, W, FOV)) return MAGAT_ERR_UNSUPPORTED;
   if (reinterpret_cast<uintptr_t>(workspace) % sizeof(u64)) return MAGAT_ERR_WORKSPACE;
-  const int half = FOV / 2, Hc = H + 2 * half + 2, Wc = W + 2 * half + 2, nw = guidew_words(Wc);
-  const long long agents = (long long)B * N;
-  const dim3 grid((unsigned)(agents < GUIDEW_CAP ? agents : GUIDEW_CAP)), block(64);
-  const size_t lds = guidew_lds_bytes(Hc, nw);                 // <= 3 * 286 * 5 * 8 + 384 bytes
-  const long long map_stride = map_batched ? (long long)H * W : 0LL;
-  const int semi = mode == MAGAT_GUIDE_SEMI ? 1 : 0, dyn = dynamic_obstacles ? 1 : 0;
-  uint8_t* view = semi ? agent_view : nullptr;
-  u64* ws = static_cast<u64*>(workspace);
-  hipStream_t st = static_cast<hipStream_t>(stream);
-  magat_form_note(MAGAT_FORM_SIM_GUIDED);
-  const int pid = magat_prof_begin(MAGAT_TAG_SIM_GUIDED, st);
-  switch (nw) {
-    case 2:
-      hipLaunchKernelGGL(guided_states_wide_kernel<2>, grid, block, lds, st, map, map_stride, H, W, pos, goal, x, FOV, N, agents, semi,
-                         dyn, view, ws);
-      break;
-    case 3:
-      hipLaunchKernelGGL(guided_states_wide_kernel<3>, grid, block, lds, st, map, map_stride, H, W, pos, goal, x, FOV, N, agents, semi,
-                         dyn, view, ws);
-      break;
-    case 4:
-      hipLaunchKernelGGL(guided_states_wide_kernel<4>, grid, block, lds, st, map, map_stride, H, W, pos, goal, x, FOV, N, agents, semi,
-                         dyn, view, ws);
-      break;
-    default:
-      hipLaunchKernelGGL(guided_states_wide_kernel<GUIDEW_MAX_WORDS>, grid, block, lds, st, map, map_stride, H, W, pos, goal, x, FOV, N,
-                         agents, semi, dyn, view, ws);
-      break;
-  }
-  magat_prof_end(pid, st);
-  return magat_check_launch();
+  const int semi = mode == MAGAT_GUIDE_SEMI ? 1 : 0;
+  return guidew_launch<false>(map, map_batched, H, W, pos, goal, x, FOV, B, N, semi, dynamic_obstacles ? 1 : 0,
+                              semi ? agent_view : nullptr, workspace, GuideHistory{}, MAGAT_FORM_SIM_GUIDED, stream);
+}
+
+extern "C" int magat_sim_replayed_states_wide(const uint8_t* map, int map_batched, int H, int W, const int32_t* pos,
+                                              const int32_t* goal, float* x, int FOV, int B, int N,
+                                              const magat_sim_history_desc* history, void* workspace, size_t workspace_bytes,
+                                              void* stream) {
+  if (!map || !pos || !goal || !x) return MAGAT_ERR_NULL;
+  if (B <= 0 || N <= 0 || H <= 0 || W <= 0 || FOV <= 0 || !(FOV & 1)) return MAGAT_ERR_BAD_SHAPE;
+  if (FOV < 3 || FOV + 2 > GUIDE_MAX_WT) return MAGAT_ERR_UNSUPPORTED;
+  if ((long long)B * N > 0x7fffffffLL) return MAGAT_ERR_UNSUPPORTED;
+  if (H > GUIDEW_SIDE || W > GUIDEW_SIDE) return MAGAT_ERR_UNSUPPORTED;
+  GuideHistory hist;
+  const int rc = guide_history_check(history, hist);
+  if (rc != MAGAT_OK) return rc;
+  if (!workspace) return MAGAT_ERR_NULL;
+  if (workspace_bytes < magat_sim_guided_states_wide_workspace_bytes(B, N, H, W, FOV)) return MAGAT_ERR_UNSUPPORTED;
+  if (reinterpret_cast<uintptr_t>(workspace) % sizeof(u64)) return MAGAT_ERR_WORKSPACE;
+  return guidew_launch<true>(map, map_batched, H, W, pos, goal, x, FOV, B, N, 1, 1, nullptr, workspace, hist, MAGAT_FORM_SIM_REPLAY,
+                             stream);
 }

@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import _native as nat
-from .simulator import GUIDANCE_MODES, _dev_i32, batched_fov_states, batched_gso, new_agent_view
+from .simulator import GUIDANCE_MODES, _dev_i32, batched_fov_states, batched_gso, new_agent_view, replayed_semi_states
 
 # expert_samples works on chunks of cases that hold at most this many (case, step, agent) samples (padded steps included)
 MAX_AGENT_STEPS = 1 << 18
@@ -161,7 +161,7 @@ def expert_stats(target, start, goal, valid):
 
 def expert_samples(obstacle_map, paths, lengths, goal, makespan, comm_radius, dynamic_commR=False, symmetric_norm=False, FOV=9,
                    guidance="Project_G", gso_dtype=torch.float32, T=None, check=True, max_steps=64,
-                   max_agent_steps=MAX_AGENT_STEPS, start=None, wide=False):
+                   max_agent_steps=MAX_AGENT_STEPS, start=None, wide=False, replay=False):
     """DataTransformer.pathtransformer_RelativeCoordinate (:237-265) for C cases: obstacle_map (H,W) or (C,H,W), the padded
     schedule (pack_schedules) -> dict(inputTensor (C,T,N,3,FOV+2,FOV+2) float32, target (C,T,N,5), GSO (C,T,N,N) gso_dtype,
     pos (C,T,N,2), valid (C,T), radii (C,) float64, grow_steps (C,) int32, makespan (C,), bad (C,)).  Steps at or behind a case's
@@ -175,7 +175,9 @@ def expert_samples(obstacle_map, paths, lengths, goal, makespan, comm_radius, dy
     of different lengths cost their own steps and no kernel sees a padded row's all-zero positions.  The memoryless encodings
     and the GSO take one call over the compacted pairs; 'SemiLG_*' takes one call per step with ONE agent_view per case carried
     from step to step (AgentState.toSeqInputTensor's order), over the cases that still have that step (longest case first,
-    so they are a prefix of the batch).
+    so they are a prefix of the batch).  replay=True serves 'SemiLG_*' like the memoryless encodings instead: ONE
+    replayed_semi_states call per chunk over the compacted pairs, each agent's remembered map rebuilt on the device from the
+    schedule's own `pos` - the same bits, no per-step loop and no carried view; with any other guidance the keyword has no effect.
 
     SYNCHRONISES with the host, so it cannot be captured into a graph: the step validity is read back once to build the
     compaction index, and so are `bad` (check=True) and grow_steps (dynamic_commR).
@@ -223,7 +225,12 @@ def expert_samples(obstacle_map, paths, lengths, goal, makespan, comm_radius, dy
         case = torch.div(idx, T, rounding_mode="floor").to(dev)
         idx = idx.to(dev)
         p = pf.index_select(0, idx)
-        if semi:
+        if semi and replay:
+            step = (idx - case * T).to(torch.int32)
+            mm = m if m.dim() == 2 else m.index_select(0, case)
+            hist = dict(case=(case - c0).to(torch.int32), step=step, table=pos[c0:c1])
+            xf.index_copy_(0, idx, replayed_semi_states(mm, p, goal.index_select(0, case), hist, FOV, guidance, wide))
+        elif semi:
             # longest case first: the cases that still have step t are the first k of the batch, and so are their views
             steps = live[c0:c1].sum(dim=1)
             order = torch.argsort(steps, descending=True, stable=True)

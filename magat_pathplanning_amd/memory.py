@@ -16,7 +16,8 @@ expert_samples is that materialisation - inputTensor (C,T,N,3,11,11) and GSO (C,
 50 x 50 / 100 agents come to gigabytes.  ExpertMemory stores the schedules only and encodes exactly the drawn steps when a
 minibatch is asked for: one launch of magat_sim_expert_pick (csrc/sim_expert_pick.h) decodes positions, targets, goals, radii
 and maps of the drawn samples, then batched_fov_states and batched_gso run on those rows - the kernels and the arguments
-expert_samples uses, so a minibatch equals the same rows of flatten_samples(expert_samples(...)) bit for bit.
+expert_samples uses, so a minibatch equals the same rows of flatten_samples(expert_samples(...)) bit for bit.  guidance
+'SemiLG_*' (replay=True) encodes the rows with replayed_semi_states instead, the store itself as the agents' history.
 
 HIP only: CPU tensors raise MagatNativeError.  minibatch never waits for the device; append, check and online_expert do."""
 import torch
@@ -24,7 +25,7 @@ import torch
 from . import _native as nat
 from . import mapf
 from .expert import MAX_AGENT_STEPS, bad_move_message, expert_radius, expert_schedule
-from .simulator import GUIDANCE_MODES, _dev_i32, batched_fov_states, batched_gso
+from .simulator import GUIDANCE_MODES, _dev_i32, batched_fov_states, batched_gso, replayed_semi_states
 
 MAX_SIDE = 256               # a stored cell is row << 8 | col
 NO_ROW = 0x7fffffff          # the error flag's value while every index has been in range
@@ -46,16 +47,18 @@ class ExpertMemory:
     samples, sum(makespan + 1); mem.cases the number of stored cases.  There is no eviction: a full memory refuses.
 
     comm_radius, dynamic_commR, symmetric_norm, FOV, guidance, gso_dtype, wide: expert_samples' arguments, fixed for the memory.
-    guidance 'SemiLG_*' raises ValueError: an agent's view is the history of its whole episode, so one step cannot be encoded
-    without replaying the case - expert_samples stays the way to those samples."""
+    guidance 'SemiLG_*' raises ValueError unless replay=True: an agent's view is the history of its whole episode, so one step
+    cannot be encoded without replaying the case (expert_samples does).  With replay=True the memory is built and a minibatch
+    replays on the device: replayed_semi_states rebuilds each drawn agent's remembered map from the stored cells 0 .. step (the
+    store itself is the history), in the one launch that encodes the states.  Other guidances do not read the keyword."""
 
     def __init__(self, capacity, N, H, W, max_length, comm_radius, dynamic_commR=False, symmetric_norm=False, FOV=9,
-                 guidance="Project_G", gso_dtype=torch.float32, shared_map=None, wide=False, device="cuda"):
+                 guidance="Project_G", gso_dtype=torch.float32, shared_map=None, wide=False, device="cuda", replay=False):
         if guidance not in GUIDANCE_MODES:
             raise ValueError("guidance must be one of %s, got %r" % (sorted(GUIDANCE_MODES), guidance))
-        if guidance.startswith("SemiLG"):
+        if guidance.startswith("SemiLG") and not replay:
             raise ValueError("ExpertMemory: guidance %r encodes an agent's view of its whole episode so far; one step cannot be "
-                             "encoded without replaying the case (use expert_samples)" % guidance)
+                             "encoded without replaying the case (use expert_samples, or replay=True)" % guidance)
         if gso_dtype not in (torch.float32, torch.float64):
             raise TypeError("ExpertMemory: gso_dtype must be torch.float32 or torch.float64, got %s" % (gso_dtype,))
         capacity, N, H, W, max_length = int(capacity), int(N), int(H), int(W), int(max_length)
@@ -75,6 +78,7 @@ class ExpertMemory:
         self.comm_radius, self.dynamic_commR, self.symmetric_norm = float(comm_radius), bool(dynamic_commR), bool(symmetric_norm)
         self.FOV, self.guidance, self.gso_dtype, self.wide, self.device = int(FOV), guidance, gso_dtype, bool(wide), dev
         self.shared_map = shared_map
+        self.replay = bool(replay) and guidance.startswith("SemiLG")
         self._cells = torch.zeros(capacity, N, max_length, dtype=torch.int16, device=dev)      # (the bits of `cells`)
         self.cells = self._cells.view(torch.uint16)
         self.lengths = torch.zeros(capacity, N, dtype=torch.int32, device=dev)
@@ -199,7 +203,8 @@ class ExpertMemory:
         takes), GSO (M,N,N) gso_dtype, pos (M,N,2) int32, case, step (M,) int32 - and the pick's other outputs goal (M,N,2) int32,
         radii (M,) float64, map (M,H,W) uint8 (the shared map itself in a shared-map memory), plus indices.
 
-        One launch of magat_sim_expert_pick, then batched_fov_states on the picked positions, goals and maps and batched_gso with
+        One launch of magat_sim_expert_pick, then batched_fov_states on the picked positions, goals and maps (a replay memory:
+        replayed_semi_states on them, with the store as the history of the picked case / step) and batched_gso with
         comm_radius (dynamic_commR: the picked radii) - expert_samples' calls on the same rows.  No host synchronisation.  An index
         outside the range is clamped into it (the row is then still a real sample) and remembered: check() raises.  out: a dict
         from an earlier call with the same M - the pick's outputs are written into its tensors and nothing is allocated for them,
@@ -242,7 +247,11 @@ class ExpertMemory:
                 nat.ptr(self.flag), self.cases, N, self.max_length, H, W, M, nat.current_stream(dev)), "magat_sim_expert_pick")
         if self.maps is None:
             b["map"] = self.shared_map
-        b["inputTensor"] = batched_fov_states(b["map"], b["pos"], b["goal"], self.FOV, self.guidance, None, self.wide)
+        if self.replay:
+            hist = dict(case=b["case"], step=b["step"], cells=self.cells, lengths=self.lengths, goal=self.goal)
+            b["inputTensor"] = replayed_semi_states(b["map"], b["pos"], b["goal"], hist, self.FOV, self.guidance, self.wide)
+        else:
+            b["inputTensor"] = batched_fov_states(b["map"], b["pos"], b["goal"], self.FOV, self.guidance, None, self.wide)
         b["GSO"] = batched_gso(b["pos"], b["radii"] if self.dynamic_commR else self.comm_radius,
                                symmetric_norm=self.symmetric_norm, dtype=self.gso_dtype)
         b["indices"] = indices

@@ -17,6 +17,8 @@ and the step behind it (multiRobotSimNew.move, :471-549) with the episode state 
     S = ep.gso(); x = ep.states(); done = ep.step(logits)        # radius grown at step 0 like the reference
 
 HIP only (csrc/sim_frontend.hip, csrc/sim_guidance.hip): CPU tensors raise MagatNativeError."""
+import ctypes
+
 import torch
 
 from . import _native as nat
@@ -186,6 +188,74 @@ def batched_fov_states(obstacle_map, pos, goal, FOV=9, guidance="Project_G", age
                                                         nat.ptr(x), FOV, B, N, guided[0], guided[1],
                                                         nat.ptr(agent_view) if guided[0] == nat.GUIDE_SEMI else None,
                                                         nat.current_stream(pos.device)), "magat_sim_guided_states")
+    return x
+
+
+def replayed_semi_states(obstacle_map, pos, goal, history, FOV=9, guidance="SemiLG_S", wide=False, workspace=None):
+    """'SemiLG_*' states of ANY step of a known schedule, in one call and without an agent_view: the map each agent remembers
+    is rebuilt on the device from the cells it has stood on (csrc/sim_guidance_parts.h: the maps are static, so that map is
+    "seen so far AND blocked") - the tensors batched_fov_states gives when the case is stepped from its start with a carried
+    agent_view.  obstacle_map (H,W) or (B,H,W), pos / goal (B,N,2): the rows' current cells and goals, as in batched_fov_states
+    -> x (B,N,3,FOV+2,FOV+2) float32.  history: a dict with case, step - (B,) int32 device tensors: row b is step step[b] of
+    case case[b] - and ONE source of the cells,
+        table                  (cases,T,N,2) int32, expert_schedule's pos (T <= 1024), or
+        cells, lengths, goal   ExpertMemory's store: (cases,N,Lcap) uint16 = row << 8 | col, (cases,N), (cases,N,2) int32 - cell s of
+                               an agent is cells[s] while s < lengths, its goal behind that (expert_schedule's rule).
+    A step whose cell is off the map, or an agent whose goal is, contributes nothing.  The refusals of batched_fov_states: CPU
+    tensors, and without `wide` a map above 54 x 54 at FOV 9 (wide, workspace: its keywords).  One launch, no host
+    synchronisation, no read-back; counted in form 'sim_replay'."""
+    if guidance not in GUIDANCE_MODES or GUIDANCE_MODES[guidance] is None or GUIDANCE_MODES[guidance][0] != nat.GUIDE_SEMI:
+        raise ValueError("replayed_semi_states: guidance must be 'SemiLG_S' or 'SemiLG_SD', got %r" % (guidance,))
+    pos, goal = _dev_i32(pos, "pos"), _dev_i32(goal, "goal")
+    if not isinstance(obstacle_map, torch.Tensor) or not obstacle_map.is_cuda:
+        raise nat.MagatNativeError("obstacle_map must be a device tensor (no CPU fallback)")
+    m = obstacle_map.to(torch.uint8).contiguous()
+    B, N, _ = pos.shape
+    assert goal.shape == pos.shape
+    batched = m.dim() == 3
+    assert m.dim() in (2, 3) and (not batched or m.shape[0] == B)
+    H, W = m.shape[-2], m.shape[-1]
+    keys = set(history)
+    if not {"case", "step"} <= keys or ("table" in keys) == bool(keys & {"cells", "lengths", "goal"}):
+        raise ValueError("replayed_semi_states: history holds case, step and either table or cells, lengths, goal - not %s"
+                         % sorted(keys))
+    case, step = _dev_i32(history["case"], "history['case']"), _dev_i32(history["step"], "history['step']")
+    if case.numel() != B or step.numel() != B:
+        raise ValueError("replayed_semi_states: history's case and step must hold one entry per row (%d)" % B)
+    d = nat.SimHistoryDesc()
+    d.row_case, d.row_step = case.data_ptr(), step.data_ptr()
+    if "table" in keys:
+        table = _dev_i32(history["table"], "history['table']")
+        if table.dim() != 4 or table.shape[2] != N or table.shape[3] != 2:
+            raise ValueError("replayed_semi_states: history['table'] must be (cases,T,%d,2), not %s" % (N, tuple(table.shape)))
+        d.pos_table, d.cases, d.T = table.data_ptr(), table.shape[0], table.shape[1]
+    else:
+        if not {"cells", "lengths", "goal"} <= keys:
+            raise ValueError("replayed_semi_states: a store history holds cells, lengths and goal")
+        cells = history["cells"]
+        if (not isinstance(cells, torch.Tensor) or not cells.is_cuda or cells.dtype not in (torch.uint16, torch.int16)
+                or cells.dim() != 3 or cells.shape[1] != N or not cells.is_contiguous()):
+            raise nat.MagatNativeError("history['cells'] must be a contiguous (cases,%d,Lcap) uint16 device tensor" % N)
+        lengths, hgoal = _dev_i32(history["lengths"], "history['lengths']"), _dev_i32(history["goal"], "history['goal']")
+        cases = cells.shape[0]
+        if tuple(lengths.shape) != (cases, N) or tuple(hgoal.shape) != (cases, N, 2):
+            raise ValueError("replayed_semi_states: history's lengths and goal must be (%d,%d) and (%d,%d,2)" % (cases, N, cases, N))
+        d.cells, d.lengths, d.goal = cells.data_ptr(), lengths.data_ptr(), hgoal.data_ptr()
+        d.cases, d.Lcap = cases, cells.shape[2]
+    x = torch.empty(B, N, 3, FOV + 2, FOV + 2, dtype=torch.float32, device=pos.device)
+    with torch.cuda.device(pos.device):
+        lib = nat.lib()
+        if wide and guided_needs_wide(H, W, FOV):
+            if workspace is None:
+                workspace = _guide_workspaces.setdefault(pos.device, _Workspace())
+            ws = workspace.get(lib.magat_sim_guided_states_wide_workspace_bytes(B, N, H, W, FOV), pos.device)
+            nat.check(lib.magat_sim_replayed_states_wide(nat.ptr(m), 1 if batched else 0, H, W, nat.ptr(pos), nat.ptr(goal),
+                                                         nat.ptr(x), FOV, B, N, ctypes.byref(d), nat.ptr(ws), ws.numel(),
+                                                         nat.current_stream(pos.device)), "magat_sim_replayed_states_wide")
+        else:
+            nat.check(lib.magat_sim_replayed_states(nat.ptr(m), 1 if batched else 0, H, W, nat.ptr(pos), nat.ptr(goal), nat.ptr(x),
+                                                    FOV, B, N, ctypes.byref(d), nat.current_stream(pos.device)),
+                      "magat_sim_replayed_states")
     return x
 
 

@@ -1,6 +1,7 @@
 """Device time of expert_samples on the two packs the reference transformer is timed on by
 tools/make_golden_expert.py --time: 64 cases x 10 agents on a 20 x 20 map and 8 cases x 100 agents on a 50 x 50 map, per
-guidance family, dynamic radius.  The schedules come from the same maker and seed with the numpy restatement of the
+guidance family, dynamic radius; SemiLG_SD twice, on the carried view (one call per step) and with replay=True (one call per
+chunk), in the same run.  The schedules come from the same maker and seed with the numpy restatement of the
 reference's A* (tests/guidance_restatement.py, pinned against the reference by tests/test_host_guidance.py) in place of the
 reference's own; that they are the packs the reference was timed on is asserted through their step counts (STEPS below, the
 counts make_golden_expert.py --time prints).  hipEvents around each call,
@@ -40,9 +41,10 @@ def main():
         maps = torch.from_numpy(np.stack([m for m, _, _ in cases]).astype(np.uint8)).to(dev)
         steps = int(pk["makespan"].sum().item()) + C
         assert steps == want
-        for guidance in ("Project_G", "LocalG_SD", "GlobalG_SD", "SemiLG_SD"):
+        for guidance, replay in (("Project_G", False), ("LocalG_SD", False), ("GlobalG_SD", False), ("SemiLG_SD", False),
+                                 ("SemiLG_SD", True)):
             def call():
-                s = expert_samples(maps, comm_radius=7.0, dynamic_commR=True, guidance=guidance, **pk)
+                s = expert_samples(maps, comm_radius=7.0, dynamic_commR=True, guidance=guidance, replay=replay, **pk)
                 expert_stats(s["target"], pk["start"], pk["goal"], s["valid"])
             for _ in range(3):
                 call()
@@ -56,7 +58,7 @@ def main():
                 b.synchronize()
                 ms.append(a.elapsed_time(b))
             ms.sort()
-            row = dict(cases=C, agents=N, map=size, guidance=guidance, steps=steps, T=pk["T"], median_ms=ms[len(ms) // 2], min_ms=ms[0],
+            row = dict(cases=C, agents=N, map=size, guidance=guidance, replay=replay, steps=steps, T=pk["T"], median_ms=ms[len(ms) // 2], min_ms=ms[0],
                        max_ms=ms[-1], us_per_agent_step=1e3 * ms[len(ms) // 2] / (steps * N))
             rows.append(row)
             print(json.dumps(row), flush=True)

@@ -13,6 +13,7 @@
 #include <stdlib.h>
 #include <string.h>
 
+#define MAGAT_HOST_WAVE 1      // for the few places where a kernel's text has to differ on the host (its dynamic LDS)
 #define __device__
 #define __host__
 #define __global__
@@ -55,9 +56,10 @@ inline unsigned long long ballot(bool p) {
   });
 }
 inline int update_dpp(int old, int src, int ctrl, int row_mask, int bank_mask, bool bound_ctrl) {
-  if (row_mask != 0xf || bank_mask != 0xf || !bound_ctrl || (ctrl != 0x130 && ctrl != 0x138)) abort();      // wave_shl:1, wave_shr:1 only
+  const bool ror = ctrl > 0x120 && ctrl < 0x130;      // row_ror:n, a rotation inside each row of 16 lanes
+  if (row_mask != 0xf || bank_mask != 0xf || !bound_ctrl || (ctrl != 0x130 && ctrl != 0x138 && !ror)) abort();      // else wave_shl:1, wave_shr:1 only
   (void)old;
-  const int from = ctrl == 0x130 ? lane + 1 : lane - 1;
+  const int from = ror ? (lane & ~15) | ((lane - (ctrl & 15)) & 15) : ctrl == 0x130 ? lane + 1 : lane - 1;
   return exchange((unsigned)src, [from](const unsigned long long* s) { return from >= 0 && from < kLanes ? (int)(unsigned)s[from] : 0; });
 }
 inline int readlane(int v, int l) {
@@ -86,7 +88,10 @@ struct BlockDim {
 };
 inline unsigned long long dyn_lds[256 * 64];      // the dynamic LDS of a workgroup: 128 KB
 struct GridDim {
-  unsigned x = 1, y = 1, z = 1;
+  struct X {
+    operator unsigned() const { return blocks; }
+  } x;
+  unsigned y = 1, z = 1;
 };
 // runs kernel(args...) for every workgroup of the grid, block.x threads each: whole wavefronts, 1 to 4 of them
 template <typename K, typename... A>
@@ -131,6 +136,9 @@ static host_wave::BlockDim blockDim;
 
 #define __syncthreads() host_wave::meet()
 #define __builtin_amdgcn_ballot_w64(p) host_wave::ballot(p)
+#define __ballot(p) host_wave::ballot(p)
+#define __builtin_amdgcn_fence(order, scope) ((void)0)
+#define __builtin_amdgcn_wave_barrier() ((void)pthread_barrier_wait(&host_wave::wave_barrier[host_wave::wave]))
 #define __builtin_amdgcn_update_dpp(o, s, c, r, b, bc) host_wave::update_dpp(o, s, c, r, b, bc)
 #define __builtin_amdgcn_readfirstlane(v) host_wave::readlane(v, 0)
 #define __builtin_amdgcn_readlane(v, l) host_wave::readlane(v, l)
@@ -148,6 +156,8 @@ inline int atomicMin(int* p, int v) {
   }
   return old;
 }
+inline unsigned atomicOr(unsigned* p, unsigned v) { return __atomic_fetch_or(p, v, __ATOMIC_RELAXED); }
+inline unsigned long long atomicOr(unsigned long long* p, unsigned long long v) { return __atomic_fetch_or(p, v, __ATOMIC_RELAXED); }
 #define __HIP_MEMORY_SCOPE_AGENT 0
 #define __hip_atomic_fetch_add(p, v, order, scope) __atomic_fetch_add(p, v, order)
 #define hipLaunchKernelGGL(kernel, grid, block, lds, stream, ...) host_wave::launch(kernel, grid, block, __VA_ARGS__)
