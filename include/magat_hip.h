@@ -396,6 +396,84 @@ int magat_sim_move_wide(const float* logits, const int32_t* actions_in, const ui
                         int32_t* flags_out, int B, int N, void* workspace, size_t workspace_bytes, void* stream);
 int magat_sim_step_wide(const magat_sim_step_desc* d, void* workspace, size_t workspace_bytes, void* stream);
 
+/* The case pool (csrc/sim_pool.hip; rollout.py: EpisodePool): B slots over a queue of C cases, for the reference's validation /
+ * test loop (agents/decentralplannerlocal_OnlineExpert_GAT.py:859-957).  A slot whose episode is over writes its case's result
+ * row and takes the next case of the queue on the device; no entry synchronises with the host.
+ * magat_sim_pool_step[_wide]: magat_sim_step[_wide] - the same kernel - with d->currentstep / d->maxstep replaced per slot by
+ *   slot_step [B] / slot_maxstep [B] (d's two scalars are not read).  over [B] = 1 when the call finalised the slot's episode
+ *   (every agent had arrived before the call, or slot_step >= slot_maxstep), else 0; sticky [B] |= the call's flag word when
+ *   the slot moved.  A slot with slot_case [B] < 0 holds no case: over = 0, nothing else is read or written.  Checks and codes
+ *   of magat_sim_step[_wide]; one of the five arrays NULL: MAGAT_ERR_NULL.
+ * magat_sim_pool_turn: after a step.  A slot that is over writes row slot_case of the results - rows [MAGAT_POOL_COLUMNS][C]
+ *   int32: retired, all_reach (done), num_reach, steps (slot_step), makespan, flowtime, predicted_collision (sticky bits 0-3),
+ *   flag_bits (sticky) - and r_end_pos [C][N][2], r_first_move, r_end_step [C][N]; with `record`, traj_len [C] = steps -
+ *   first_step + 1.  Then it is refilled: the finished slots take the cases next, next + 1, ... in ascending slot order (a
+ *   slot's rank = the finished slots below it); start, goal and (map_batched) the map are copied in, reach_goal, first_move,
+ *   end_step, sticky and the slot's agent_view (agent_view_bytes a slot; NULL: none) are zeroed, slot_step = first_step,
+ *   slot_maxstep = q_maxstep[case], and radii [B] / r_radius [C] = the case's step-0 radius, magat_sim_connect_radius's loop
+ *   and bits; a case still disconnected after radius_max_steps growth steps gets MAGAT_POOL_STATUS_DISCONNECTED in its status
+ *   column.  Beyond the queue the slot goes idle: slot_case = -1, the positions stay.  A slot that is not over: with `record`
+ *   traj [C][N][traj_cells] uint16, cell slot_step - first_step + 1, = row << 8 | col of its positions (cell 0 is the start,
+ *   written at the refill); then slot_step += 1.  counters [4] int32: next, remaining, and one word handed from the turn's first
+ *   launch (one wavefront: counts the finished slots, moves next and remaining) to its second (one workgroup per slot).
+ *   init != 0: every slot counts as finished and no row is written - the first fill; the caller has set counters = {0, C} and
+ *   zeroed rows.  N <= 5120; record: H, W <= 256; 1 <= B <= C.
+ * magat_sim_pool_uniforms: u [B][N] float64 in [0, 1), 53 bits from two 32-bit draws of the case generator's stream keyed on
+ *   (seed, slot_case, slot_step, agent): a case's uniforms do not depend on its slot or on B.  An idle slot gets 0. */
+#define MAGAT_POOL_RETIRED 0
+#define MAGAT_POOL_ALL_REACH 1
+#define MAGAT_POOL_NUM_REACH 2
+#define MAGAT_POOL_STEPS 3
+#define MAGAT_POOL_MAKESPAN 4
+#define MAGAT_POOL_FLOWTIME 5
+#define MAGAT_POOL_PREDICTED 6
+#define MAGAT_POOL_FLAG_BITS 7
+#define MAGAT_POOL_STATUS 8
+#define MAGAT_POOL_COLUMNS 9
+#define MAGAT_POOL_STATUS_DISCONNECTED 2      /* status bit 1 */
+typedef struct magat_sim_pool_desc {
+  const uint8_t* q_map;        /* [C or 1][H][W] */
+  const int32_t* q_start;      /* [C][N][2] */
+  const int32_t* q_goal;       /* [C][N][2] */
+  const int32_t* q_maxstep;    /* [C] */
+  int32_t map_batched, H, W, C, B, N;
+  int32_t first_step, record, traj_cells, radius_max_steps;
+  double comm_radius;
+  int32_t* slot_case;          /* [B] in/out */
+  int32_t* slot_step;          /* [B] in/out */
+  int32_t* slot_maxstep;       /* [B] */
+  const int32_t* over;         /* [B] magat_sim_pool_step's */
+  int32_t* sticky;             /* [B] */
+  uint8_t* map;                /* [B][H][W] when map_batched, else NULL: the step reads q_map */
+  int32_t* pos;                /* [B][N][2] */
+  int32_t* goal;               /* [B][N][2] */
+  uint8_t* reach_goal;         /* [B][N] */
+  int32_t* first_move;         /* [B][N] */
+  int32_t* end_step;           /* [B][N] */
+  const int32_t* done;         /* [B] the step's done_out */
+  const int32_t* flowtime;     /* [B] the step's flowtime_out */
+  const int32_t* makespan;     /* [B] the step's makespan_out */
+  double* radii;               /* [B] */
+  uint8_t* agent_view;         /* [B][agent_view_bytes] or NULL */
+  int64_t agent_view_bytes;
+  int32_t* counters;           /* [4] */
+  int32_t* rows;               /* [MAGAT_POOL_COLUMNS][C] */
+  double* r_radius;            /* [C] */
+  int32_t* r_end_pos;          /* [C][N][2] */
+  int32_t* r_first_move;       /* [C][N] */
+  int32_t* r_end_step;         /* [C][N] */
+  uint16_t* traj;              /* [C][N][traj_cells] when record */
+  int32_t* traj_len;           /* [C] when record */
+} magat_sim_pool_desc;
+int magat_sim_pool_step(const magat_sim_step_desc* d, const int32_t* slot_case, const int32_t* slot_step,
+                        const int32_t* slot_maxstep, int32_t* over, int32_t* sticky, void* stream);
+int magat_sim_pool_step_wide(const magat_sim_step_desc* d, const int32_t* slot_case, const int32_t* slot_step,
+                             const int32_t* slot_maxstep, int32_t* over, int32_t* sticky, void* workspace,
+                             size_t workspace_bytes, void* stream);
+int magat_sim_pool_turn(const magat_sim_pool_desc* d, int init, void* stream);
+int magat_sim_pool_uniforms(const int32_t* slot_case, const int32_t* slot_step, double* u, uint64_t seed, int B, int N,
+                            void* stream);
+
 /* Dense GSO -> everything the CSR kernels need, for N <= 1024, in ONE streaming pass over S plus one small kernel, with no
  * host synchronisation: addGSO's in-place scrub (scrub_nan / gso_mode 0|1 as magat_gso_prepare; values are written back only
  * where they change), the edge test (edge_rule: 0 |S| > 1e-9 in S's dtype, 1 GAT_origin |float(S) + I| > 1e-9, 2 float(S) != 0)

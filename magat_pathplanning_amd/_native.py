@@ -95,6 +95,27 @@ class SimHistoryDesc(ctypes.Structure):
                 ("cases", ctypes.c_int32), ("T", ctypes.c_int32), ("Lcap", ctypes.c_int32)]
 
 
+class SimPoolDesc(ctypes.Structure):
+    """magat_sim_pool_desc (include/magat_hip.h)."""
+    _fields_ = [("q_map", ctypes.c_void_p), ("q_start", ctypes.c_void_p), ("q_goal", ctypes.c_void_p),
+                ("q_maxstep", ctypes.c_void_p), ("map_batched", ctypes.c_int32), ("H", ctypes.c_int32), ("W", ctypes.c_int32),
+                ("C", ctypes.c_int32), ("B", ctypes.c_int32), ("N", ctypes.c_int32), ("first_step", ctypes.c_int32),
+                ("record", ctypes.c_int32), ("traj_cells", ctypes.c_int32), ("radius_max_steps", ctypes.c_int32),
+                ("comm_radius", ctypes.c_double), ("slot_case", ctypes.c_void_p), ("slot_step", ctypes.c_void_p),
+                ("slot_maxstep", ctypes.c_void_p), ("over", ctypes.c_void_p), ("sticky", ctypes.c_void_p),
+                ("map", ctypes.c_void_p), ("pos", ctypes.c_void_p), ("goal", ctypes.c_void_p), ("reach_goal", ctypes.c_void_p),
+                ("first_move", ctypes.c_void_p), ("end_step", ctypes.c_void_p), ("done", ctypes.c_void_p),
+                ("flowtime", ctypes.c_void_p), ("makespan", ctypes.c_void_p), ("radii", ctypes.c_void_p),
+                ("agent_view", ctypes.c_void_p), ("agent_view_bytes", ctypes.c_int64), ("counters", ctypes.c_void_p),
+                ("rows", ctypes.c_void_p), ("r_radius", ctypes.c_void_p), ("r_end_pos", ctypes.c_void_p),
+                ("r_first_move", ctypes.c_void_p), ("r_end_step", ctypes.c_void_p), ("traj", ctypes.c_void_p),
+                ("traj_len", ctypes.c_void_p)]
+
+
+# columns of magat_sim_pool_desc.rows (include/magat_hip.h MAGAT_POOL_*)
+POOL_COLUMNS = ("retired", "all_reach", "num_reach", "steps", "makespan", "flowtime", "predicted_collision", "flag_bits", "status")
+POOL_STATUS_DISCONNECTED = 2
+
 _I, _P, _Z = ctypes.c_int, ctypes.c_void_p, ctypes.c_size_t
 _SIGNATURES = {
     "magat_abi_version": (ctypes.c_int, []),
@@ -145,6 +166,10 @@ _SIGNATURES = {
     "magat_sim_move_wide_workspace_bytes": (_Z, [_I] * 4),
     "magat_sim_move_wide": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _Z, _P]),
     "magat_sim_step_wide": (_I, [ctypes.POINTER(SimStepDesc), _P, _Z, _P]),
+    "magat_sim_pool_step": (_I, [ctypes.POINTER(SimStepDesc), _P, _P, _P, _P, _P, _P]),
+    "magat_sim_pool_step_wide": (_I, [ctypes.POINTER(SimStepDesc), _P, _P, _P, _P, _P, _P, _Z, _P]),
+    "magat_sim_pool_turn": (_I, [ctypes.POINTER(SimPoolDesc), _I, _P]),
+    "magat_sim_pool_uniforms": (_I, [_P, _P, _P, ctypes.c_uint64, _I, _I, _P]),
     "magat_gso_prepare": (_I, [_P, _I, _Z, _I, _I, _P]),
     "magat_conv_gemm_f32": (_I, [ctypes.POINTER(ConvGemmDesc), _P]),
     "magat_conv_wgrad_workspace_floats": (_Z, [_I] * 7),

@@ -64,6 +64,14 @@ static_assert(MAGAT_PROF_TAGS_ALL >= MAGAT_PROF_TAGS && MAGAT_FORMS_ALL >= MAGAT
 static_assert(MAGAT_PROF_TAGS_TABLE > MAGAT_TAG_SIM_MAPF_ECBS && MAGAT_PROF_TAGS_TABLE >= MAGAT_PROF_TAGS_ALL &&
               MAGAT_FORMS_TABLE > MAGAT_FORM_SIM_REPLAY && MAGAT_FORMS_TABLE >= MAGAT_FORMS_ALL, "internal tag / form tables");
 
+// the move step with per-instance counters (sim_frontend.hip: sim_move_kernel), launched for the case pool's entries (sim_pool.hip)
+struct magat_sim_pool_slots {
+  const int32_t* slot_case; const int32_t* slot_step; const int32_t* slot_maxstep;      // [B] each
+  int32_t* over; int32_t* sticky;                                                       // [B] each
+};
+int magat_sim_step_slots(const magat_sim_step_desc* d, const magat_sim_pool_slots* slots, void* stream, bool wide, void* workspace,
+                         size_t workspace_bytes);
+
 // bf16x6 split-MFMA GEMM (conv_gemm_bf16x6.hip), reached through magat_conv_gemm_f32 when desc->in_fmt == 1
 int magat_conv_gemm_bf16x6(const magat_conv_gemm_desc* d, hipStream_t st);
 int magat_layer1_fused(const float* x, const float* w0, const float* b0, const float* w1, const float* b1, void* out,

@@ -532,6 +532,12 @@ struct SimBook {
   int* done_out;           // [B] all agents had reached their goals BEFORE this call
   int* flowtime_out;       // [B] written when the episode is over
   int* makespan_out;       // [B]
+  // the case pool (sim_pool.hip): step and maxstep per instance instead of the two scalars above (null: the scalars hold)
+  const int* slot_step;    // [B]
+  const int* slot_maxstep; // [B]
+  const int* slot_case;    // [B] the case a slot holds; < 0: none, the slot takes no part
+  int* over;               // [B] 1 when this call finalised the slot's episode
+  int* sticky;             // [B] the flag words of the episode's calls, or-ed
 };
 
 template <bool WIDE>
@@ -548,6 +554,14 @@ __global__ __launch_bounds__(1024) void sim_move_kernel(const float* __restrict_
   // episode bookkeeping of multiRobotSimNew.move (new_simulator.py:471-549), when the caller keeps its state on the device
   __shared__ int n_reached;
   bool active = true, finalize = false;
+  if (bk.slot_step) {
+    if (bk.slot_case[b] < 0) {                                 // an idle slot of the pool: its state stays as it is
+      if (t == 0) bk.over[b] = 0;
+      return;
+    }
+    bk.step = bk.slot_step[b];
+    bk.maxstep = bk.slot_maxstep[b];
+  }
   if (bk.reach) {
     if (t == 0) n_reached = 0;
     __syncthreads();
@@ -559,6 +573,7 @@ __global__ __launch_bounds__(1024) void sim_move_kernel(const float* __restrict_
     active = !all_reached && bk.step < bk.maxstep;
     finalize = all_reached || bk.step >= bk.maxstep;
     if (t == 0 && bk.done_out) bk.done_out[b] = all_reached ? 1 : 0;
+    if (t == 0 && bk.over) bk.over[b] = finalize ? 1 : 0;
     __syncthreads();
   }
   if (!active) {
@@ -723,6 +738,7 @@ __global__ __launch_bounds__(1024) void sim_move_kernel(const float* __restrict_
     }
   }
   if (flags_out && t == 0) flags_out[b] = flags;
+  if (bk.sticky && t == 0) bk.sticky[b] |= flags;
   }
   if (finalize && bk.end_step && bk.first_move) {
     // episode over (everybody arrived before this call, or the step budget is spent): :528-547
@@ -852,10 +868,19 @@ int sim_move_launch(const float* logits, const int32_t* actions_in, const uint8_
   return magat_check_launch();
 }
 
-int sim_step_launch(const magat_sim_step_desc* d, void* stream, bool wide, void* workspace, size_t workspace_bytes) {
+int sim_step_launch(const magat_sim_step_desc* d, void* stream, bool wide, void* workspace, size_t workspace_bytes,
+                    const magat_sim_pool_slots* slots = nullptr) {
   if (!d) return MAGAT_ERR_NULL;
   if (!d->goal || !d->reach_goal || !d->first_move || !d->end_step) return MAGAT_ERR_NULL;
   SimBook bk{};
+  if (slots) {
+    if (!slots->slot_case || !slots->slot_step || !slots->slot_maxstep || !slots->over || !slots->sticky) return MAGAT_ERR_NULL;
+    bk.slot_step = slots->slot_step;
+    bk.slot_maxstep = slots->slot_maxstep;
+    bk.slot_case = slots->slot_case;
+    bk.over = slots->over;
+    bk.sticky = slots->sticky;
+  }
   bk.reach = d->reach_goal;
   bk.first_move = d->first_move;
   bk.end_step = d->end_step;
@@ -869,6 +894,13 @@ int sim_step_launch(const magat_sim_step_desc* d, void* stream, bool wide, void*
                          workspace_bytes);
 }
 }  // namespace
+
+// the pool's step (sim_pool.hip: magat_sim_pool_step, magat_sim_pool_step_wide): the same kernel, counters per instance
+int magat_sim_step_slots(const magat_sim_step_desc* d, const magat_sim_pool_slots* slots, void* stream, bool wide, void* workspace,
+                         size_t workspace_bytes) {
+  if (!slots) return MAGAT_ERR_NULL;
+  return sim_step_launch(d, stream, wide, workspace, workspace_bytes, slots);
+}
 
 extern "C" int magat_sim_move(const float* logits, const int32_t* actions_in, const uint8_t* map, int map_batched, int H,
                               int W, int32_t* pos, const int32_t* goal, int32_t* actions_out, int8_t* moves_out,
