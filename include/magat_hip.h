@@ -39,6 +39,21 @@ extern "C" {
 #define MAGAT_MODE_GNN 3          /* no attention: GraphFilterBatch / BatchLSIGF (graphML.py:5485-5700), the GNN baseline:
                                      z_k = z_{k-1} @ float(S), the edge weights are the GSO VALUES (CSR entry point only,
                                      magat_gnn_forward_csr_f32; P = 1, taps = weight (F,1,K,G), no ReLU inside the layer) */
+#define MAGAT_MODE_SIMILARITY 4   /* attentionMode == 'GAT_Similarity' (GraphFilterBatchSimilarityAttentional, graphML.py:4690-4857,
+                                     1449-1564, 2095-2179): cosine scores e_ij = (x_i / max(|x_i|, 1e-9)) . (q_j / max(|q_j|, 1e-9)),
+                                     q_j = W x_j (no bias, no LeakyReLU) under GAT_origin's mask |float(S)+I| > 1e-9; the filter is
+                                     KeyQuery's (full taps (P,F,1,K,G)).  P = 1 and G == F only (the reference's own reshapes need
+                                     both).  Pack layout: KeyQuery's; `weight_bias` and `mixer` are ignored.  float32 inference
+                                     entry points only.  One launch (gat_small.hip / gat_mid.hip, cosine scores in the G2 epilogue)
+                                     for 32 / 64 features on N <= 128 and 128 features on N = 97 .. 105, K = 2 | 3, with the range
+                                     guard on: a value beyond the f16 planes' range OR a non-zero row too small for their
+                                     resolution (scaled norm below 1 / 8) raises the flag, and the predicated float32 form rewrites
+                                     the output.  That form, and every other shape: float32 MFMA maps GEMM, one kernel that
+                                     normalises the Q columns of the maps and writes the normalised rows of X into the workspace
+                                     (magat_gat_workspace_bytes and the CSR sizes grow by B N G floats), then the KeyQuery graph
+                                     kernels on them (128 features beyond 105 agents and N > 128: the generic CSR score and hop
+                                     kernels).  The bf16 and the
+                                     training entry points answer MAGAT_ERR_UNSUPPORTED, as does any call with P != 1 or G != F. */
 
 int magat_abi_version(void);
 /* 0 = release build.  1 = EXPERIMENT build: at least one source was compiled with timing-experiment switches (*_WHATIF_*:

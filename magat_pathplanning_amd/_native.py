@@ -14,7 +14,9 @@ MODE_KEYQUERY = 0
 MODE_GAT_MODIFIED = 1
 MODE_GAT_ORIGIN = 2
 MODE_GNN = 3
-_MODE_IDS = {"KeyQuery": MODE_KEYQUERY, "GAT_modified": MODE_GAT_MODIFIED, "GAT_origin": MODE_GAT_ORIGIN}
+MODE_SIMILARITY = 4
+_MODE_IDS = {"KeyQuery": MODE_KEYQUERY, "GAT_modified": MODE_GAT_MODIFIED, "GAT_origin": MODE_GAT_ORIGIN,
+             "GAT_Similarity": MODE_SIMILARITY}
 TAGS = {0: "untagged", 1: "conv_first", 2: "layer1.conv1", 3: "layer1.conv2+ds", 4: "layer2.conv1",
         5: "layer2.conv2+ds", 6: "layer3.conv1", 7: "layer3.conv2+ds", 8: "head(avgpool+fc+linear)",
         9: "compressMLP", 10: "gat_maps_gemm", 11: "gat_graph", 12: "actionsMLP", 13: "head_mean",

@@ -332,7 +332,7 @@ constexpr int CSR_MAX_N = 8190;
 static_assert((2 * CSR_MAX_N + 2) * sizeof(int) < 64 * 1024 && (2 * (CSR_MAX_N + 1) + 2) * sizeof(int) >= 64 * 1024, "");
 
 struct WsLayout {
-  size_t status, z, cscptr, cscsrc, cscpos, csctmp, att, t0, t1, ytmp, order, total;
+  size_t status, z, cscptr, cscsrc, cscpos, csctmp, att, t0, t1, ytmp, order, xhat, total;
 };
 // the form with the maps inside the graph kernels (gat_csr_fused.hip): bf16 storage + the column view of magat_gso_csr_build
 bool csr_fused_form(size_t esz, bool have_csc, int G, int F, int K, int P, int mode, int concat) {
@@ -358,6 +358,7 @@ WsLayout ws_layout(int B, int N, long long nnz, int G, int F, int K, int P, int 
   w.t1 = take(K > 3 ? tb : 0);
   w.ytmp = take(concat ? 0 : (size_t)B * N * P * F * esz);
   w.order = take(fused ? magat_gat_csr_fused_order_bytes(B, N) : 0);
+  w.xhat = take(mode == MAGAT_MODE_SIMILARITY ? (size_t)B * N * G * sizeof(float) : 0);      // normalised X rows (magat_gat_cos_prepare)
   w.total = o;
   return w;
 }
@@ -894,8 +895,11 @@ int csr_forward(const ST* X, const int* rowptr, const int* colidx, long long nnz
                 const int* pre_cscpos = nullptr, int y_f32 = 0) {
   if (!X || !rowptr || !packed || !Y || (nnz > 0 && !colidx)) return MAGAT_ERR_NULL;
   if (B <= 0 || N <= 0 || nnz < 0 || G <= 0 || F <= 0 || K <= 0 || P <= 0) return MAGAT_ERR_BAD_SHAPE;
-  if (mode < MAGAT_MODE_KEYQUERY || mode > MAGAT_MODE_GNN) return MAGAT_ERR_UNSUPPORTED;
+  if (mode < MAGAT_MODE_KEYQUERY || mode > MAGAT_MODE_SIMILARITY) return MAGAT_ERR_UNSUPPORTED;
   const bool gnn = mode == MAGAT_MODE_GNN;     // fixed edge weights (the GSO values) instead of attention
+  // GAT_Similarity: float32 only, one head; the generic score and hop kernels run as KeyQuery on normalised operands
+  const bool cosine = mode == MAGAT_MODE_SIMILARITY;
+  if (cosine && (sizeof(ST) != sizeof(float) || P != 1 || G != F)) return MAGAT_ERR_UNSUPPORTED;
   if (gnn && (P != 1 || (nnz > 0 && K > 1 && !edge_vals) || (G & 3))) return MAGAT_ERR_BAD_SHAPE;
   if ((!gnn && G != F) || !supported_width(F)) return MAGAT_ERR_UNSUPPORTED;
   if (N > CSR_MAX_N) return MAGAT_ERR_UNSUPPORTED;
@@ -929,8 +933,18 @@ int csr_forward(const ST* X, const int* rowptr, const int* colidx, long long nnz
     //  elements - magat_hip.h "Alignment" (2); the workspace the caller sized for this form holds no maps, so there is no
     //  fall-through to the unfused kernels)
   }
-  int rc = csr_maps_gemm<ST>(X, packed, Z, B * N, G, L, stream, reinterpret_cast<int32_t*>(ws + w.status));
+  // (GAT_Similarity: float32 MFMA maps, as in gat_f32.hip - the direction of a tiny agent's q_j must survive)
+  int rc = cosine ? magat_gat_maps_gemm(reinterpret_cast<const float*>(X), packed, reinterpret_cast<float*>(Z), B * N, G, L.NC, L.NC,
+                                        stream, 0, nullptr, 1)
+                  : csr_maps_gemm<ST>(X, packed, Z, B * N, G, L, stream, reinterpret_cast<int32_t*>(ws + w.status));
   if (rc != MAGAT_OK) return rc;
+  if (cosine) {
+    rc = magat_gat_cos_prepare(reinterpret_cast<const float*>(X), reinterpret_cast<float*>(Z), reinterpret_cast<float*>(ws + w.xhat),
+                               (long long)B * N, G, L.qoff, L.NC, 0, stream);
+    if (rc != MAGAT_OK) return rc;
+    X = reinterpret_cast<const ST*>(ws + w.xhat);      // (read below for the scores' x_i only: the taps come from Z)
+    mode = MAGAT_MODE_KEYQUERY;
+  }
 
   CsrParams p = {};
   p.X = X; p.Z = Z; p.rowptr = rowptr; p.colidx = colidx; p.cscptr = cscptr; p.cscsrc = cscsrc; p.cscpos = cscpos;
@@ -956,7 +970,7 @@ int csr_forward(const ST* X, const int* rowptr, const int* colidx, long long nnz
       if ((rc = magat_check_launch()) != MAGAT_OK) return rc;
     }
     if (!gnn) {
-      if (mode == MAGAT_MODE_KEYQUERY && csr_tiled_ok<ST>(p, G, 1)) rc = run_tiled<ST>(p, G, true, st);
+      if (mode == MAGAT_MODE_KEYQUERY && !cosine && csr_tiled_ok<ST>(p, G, 1)) rc = run_tiled<ST>(p, G, true, st);
       else { MAGAT_CSR_DISPATCH(G, run_scores, ST) }
       if (rc != MAGAT_OK) return rc;
     }
@@ -980,7 +994,7 @@ int csr_forward(const ST* X, const int* rowptr, const int* colidx, long long nnz
         p.told_head_stride = F;
       }
       p.Tnew = tbuf[h & 1];
-      if (csr_tiled_ok<ST>(p, F, 2)) rc = run_tiled<ST>(p, F, false, st);
+      if (!cosine && csr_tiled_ok<ST>(p, F, 2)) rc = run_tiled<ST>(p, F, false, st);
       else { MAGAT_CSR_DISPATCH(F, run_hop, ST) }
       if (rc != MAGAT_OK) return rc;
     }

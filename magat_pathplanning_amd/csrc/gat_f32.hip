@@ -52,6 +52,8 @@ struct GatParams {
   int b0;                        // first instance of this chunk
   long long* dbg;                // optional phase timestamps [blocks][8] (instrumentation; null in production)
   int skip;                      // instrumentation: bit0 skip scores, bit1 skip hops (wrong results; for PMC deltas)
+  int origin_mask;               // gat_dense_kernel: edges by GAT_origin's rule |float(S) + I| > 1e-9 (GAT_origin, GAT_Similarity);
+                                 // (in the alignment gap behind `skip`: no other field moves)
   const int* order;              // when set: slot s of the instance walk processes instance order[s] (balanced assignment)
   const unsigned* rmask_pre;     // when set: [B][N][4] edge masks made by gat_prepare_kernel (the kernel then never reads S)
   long long zts;                 // 0: Z rows are NC wide; > 0: Z is split into 128-column tiles zts floats apart (row stride 128):
@@ -242,7 +244,7 @@ __global__ void gat_dense_kernel(const GatParams p) {
     if constexpr (WIDE) {   // GSO rows -> 128-bit edge masks (one wave per row, coalesced reads, ballot)
       // every wave owns rows wave, wave + nwaves, ... (at most 8 since NT >= 8 N): all their loads are issued
       // first and the ballots run afterwards - one memory latency per instance instead of one per row
-      const float sl = p.mode == MAGAT_MODE_GAT_ORIGIN ? 1.f : 0.f;
+      const float sl = p.origin_mask ? 1.f : 0.f;
       if (p.rmask_pre) {      // made by gat_prepare_kernel: 16 bytes per row instead of the GSO row
         const unsigned* src = p.rmask_pre + (long long)b * N * 4;
         for (int idx = t; idx < 4 * N; idx += NT) rmask[idx] = src[idx];
@@ -288,7 +290,7 @@ __global__ void gat_dense_kernel(const GatParams p) {
     } else {                // mask -> A (1/0)
       for (int idx = t; idx < N * N; idx += NT) {
         const int i = idx / N, j = idx - i * N;
-        const float sl = (p.mode == MAGAT_MODE_GAT_ORIGIN && i == j) ? 1.f : 0.f;
+        const float sl = (p.origin_mask && i == j) ? 1.f : 0.f;
         A[i * p.lda_a + j] = is_edge(p.S, sbase + idx, p.s_is_f64, sl) ? 1.f : 0.f;
       }
     }
@@ -1038,6 +1040,42 @@ __global__ void head_mean_relu_kernel(const float* __restrict__ ytmp, float* __r
   if (book) magat_guard_book(book);
 }
 
+// ---- GAT_Similarity (graphML.py:1449-1564): e_ij = cos(x_i, q_j), q_j = W x_j, every norm clamped at 1e-9 on its own (torch's
+// CosineSimilarity) - KeyQuery's score x_i . q_j of the NORMALISED operands.  Behind the maps GEMM this kernel divides the G score
+// columns of every Z row by their norm in place and writes the normalised X rows into the workspace; the KeyQuery score kernels
+// (gat_dense_kernel, csr_scores_kernel) then run on (Xhat, Z) as they are.  They read X for x_i only - the taps come from Z - so
+// the filter still sees the layer's own input.  G / 4 lanes per row, 16 bytes of either row per lane, sums of squares in float32
+// over __shfl_xor inside the row's lanes (a zero row stays zero: 0 * 1e9).
+template <int G>
+__global__ __launch_bounds__(256) void gat_cos_prepare_kernel(const float* __restrict__ X, float* __restrict__ Z,
+                                                              float* __restrict__ Xhat, long long M, int qoff, int zrow,
+                                                              long long zts, const int* __restrict__ run_if) {
+  if (run_if && *run_if == 0) return;      // (predicated form: inside the range guard's re-run behind the one-launch cosine kernel)
+  constexpr int LPR = G / 4;          // lanes per row: 4 .. 64, a row never straddles two waves
+  constexpr int RPB = 256 / LPR;      // rows per workgroup step
+  static_assert(LPR >= 4 && LPR <= 64 && (LPR & (LPR - 1)) == 0, "G in {16, 32, 64, 128, 256}");
+  const int sub = threadIdx.x % LPR;
+  const int col = qoff + 4 * sub;     // (a 4-column piece never crosses a 128-column tile: qoff is a multiple of G)
+  const long long zoff = zts ? (long long)(col >> 7) * zts + (col & 127) : (long long)col;
+  for (long long m = blockIdx.x * (long long)RPB + threadIdx.x / LPR; m < M; m += (long long)gridDim.x * RPB) {
+    float* zq = Z + m * zrow + zoff;
+    f32x4 x = *reinterpret_cast<const f32x4*>(X + m * G + 4 * sub);
+    f32x4 q = *reinterpret_cast<const f32x4*>(zq);
+    float sx = fmaf(x[3], x[3], fmaf(x[2], x[2], fmaf(x[1], x[1], x[0] * x[0])));
+    float sq = fmaf(q[3], q[3], fmaf(q[2], q[2], fmaf(q[1], q[1], q[0] * q[0])));
+#pragma unroll
+    for (int o = LPR / 2; o > 0; o >>= 1) {      // (every lane of a row has the same m: the row's lanes leave the loop together)
+      sx += __shfl_xor(sx, o, 64);
+      sq += __shfl_xor(sq, o, 64);
+    }
+    const float ix = 1.f / fmaxf(sqrtf(sx), 1e-9f), iq = 1.f / fmaxf(sqrtf(sq), 1e-9f);
+    x *= ix;
+    q *= iq;
+    *reinterpret_cast<f32x4*>(Xhat + m * G + 4 * sub) = x;
+    *reinterpret_cast<f32x4*>(zq) = q;
+  }
+}
+
 long long* g_gat_dbg = nullptr;   // see magat_gat_set_debug_buffer
 
 size_t gat_lds_bytes(int N, int G, int F, int nwaves) {
@@ -1153,6 +1191,23 @@ int magat_gat_maps_gemm(const float* X, const float* packed, float* Z, int M, in
   return gat_maps_gemm_f32(X, packed, Z, M, G, NC, ldz, stream, ntile_stride, nullptr, MAGAT_TAG_GAT_MAPS);
 }
 
+int magat_gat_cos_prepare(const float* X, float* Z, float* Xhat, long long M, int G, int qoff, int ldz, long long ntile_stride,
+                          void* stream, const int32_t* run_if) {
+  if (!X || !Z || !Xhat) return MAGAT_ERR_NULL;
+  if (M <= 0 || !supported_width(G) || (qoff % G) || (ldz & 3)) return MAGAT_ERR_BAD_SHAPE;
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const int rpb = 256 / (G / 4);
+  long long blocks = (M + rpb - 1) / rpb;
+  if (blocks > 2048) blocks = 2048;      // (memory-bound: the workgroups stride over the rest)
+  if (run_if && blocks > 128) blocks = 128;      // (a launch that returns at once pays for every workgroup it dispatches)
+  const int zrow = ntile_stride ? 128 : ldz;
+  const int pid = magat_prof_begin(run_if ? MAGAT_TAG_RANGE_GUARD : MAGAT_TAG_GAT_PREPARE, st);
+  MAGAT_WIDTH_SWITCH(G, hipLaunchKernelGGL((gat_cos_prepare_kernel<WW>), dim3((unsigned)blocks), dim3(256), 0, st, X, Z, Xhat, M,
+                                           qoff, zrow, ntile_stride, reinterpret_cast<const int*>(run_if)));
+  magat_prof_end(pid, st);
+  return magat_check_launch();
+}
+
 // 1 when the LDS-resident dense-GSO kernel covers this shape, 0 when the caller must use the CSR entry point
 extern "C" int magat_gat_dense_supported(int N, int G, int F) {
   if (N <= 0 || N > 128 || G != F || !supported_width(G)) return 0;
@@ -1185,11 +1240,17 @@ extern "C" size_t magat_gat_workspace_bytes(int B, int N, int G, int F, int K, i
   const int chunk = gat_chunk_instances(B, N, ldz);
   size_t bytes = GAT_STATUS_BYTES + magat_align_up((size_t)chunk * N * ldz * sizeof(float), 256);
   if (!concat) bytes += magat_align_up((size_t)B * N * P * F * sizeof(float), 256);
+  if (mode == MAGAT_MODE_SIMILARITY) bytes += magat_align_up((size_t)B * N * G * sizeof(float), 256);      // the normalised X rows
   return bytes;
 }
 
 static bool gat_one_launch(int N, int G, int F, int K, int mode, int concat) {
   (void)concat;
+  // GAT_Similarity: the cosine forms of gat_small.hip (N <= 32) and gat_mid.hip, and only with the range guard on - a row too small for the f16 planes
+  // raises its flag and is served by the float32 re-run
+  if (mode == MAGAT_MODE_SIMILARITY)
+    return magat_opt(MAGAT_OPT_GAT_MFMA) && magat_opt(MAGAT_OPT_GAT_SPLIT) && magat_opt(MAGAT_OPT_RANGE_GUARD) != 0 &&
+           (magat_gat_small_supported(N, G, F, K, mode) || magat_gat_mid_supported(N, G, F, K, mode));
   return magat_opt(MAGAT_OPT_GAT_MFMA) && magat_opt(MAGAT_OPT_GAT_SPLIT) &&
          (magat_gat_mfma_supported(N, G, F, K, mode) || magat_gat_small_supported(N, G, F, K, mode) ||
           magat_gat_mid_supported(N, G, F, K, mode));
@@ -1206,8 +1267,9 @@ static int gat_forward_impl(const float* X, const void* S, int s_is_f64, const f
                             int mode, int concat, const magat_conv_gemm_desc* tail, int* tail_done, void* stream) {
   if (!X || !S || !packed || !Y) return MAGAT_ERR_NULL;
   if (B <= 0 || N <= 0 || G <= 0 || F <= 0 || K <= 0 || P <= 0) return MAGAT_ERR_BAD_SHAPE;
-  if (mode < MAGAT_MODE_KEYQUERY || mode > MAGAT_MODE_GAT_ORIGIN) return MAGAT_ERR_UNSUPPORTED;
-  if (G != F || !supported_width(G) || N > 128) return MAGAT_ERR_UNSUPPORTED;
+  const bool cosine = mode == MAGAT_MODE_SIMILARITY;
+  if ((mode < MAGAT_MODE_KEYQUERY || mode > MAGAT_MODE_GAT_ORIGIN) && !cosine) return MAGAT_ERR_UNSUPPORTED;
+  if (G != F || !supported_width(G) || N > 128 || (cosine && P != 1)) return MAGAT_ERR_UNSUPPORTED;
   const int width = concat ? P * F : F;
   if (ldy < width || (ldy & 3)) return MAGAT_ERR_BAD_SHAPE;
   // X rows are read in 16-byte pieces by every form (gat_small / gat_mid, the maps GEMMs and the range guard's float32 re-run
@@ -1222,6 +1284,7 @@ static int gat_forward_impl(const float* X, const void* S, int s_is_f64, const f
   // beyond gat_dense_kernel's tiles (128 features: N > 105) only the one-launch form of gat_mid.hip exists, with gat_slim_kernel
   // as the range guard's float32 re-run; no attention tensor there (the CSR kernels serve such requests)
   const bool slim = lds > 160 * 1024;
+  if (slim && cosine) return MAGAT_ERR_UNSUPPORTED;      // (128 features on N > 105: the CSR kernels serve GAT_Similarity there)
   if (slim && !(G == 128 && F == 128 && mode == MAGAT_MODE_KEYQUERY && !A_opt && gat_one_launch(N, G, F, K, mode, concat) &&
                 (reinterpret_cast<uintptr_t>(Y) & 15) == 0))
     return MAGAT_ERR_UNSUPPORTED;
@@ -1249,6 +1312,10 @@ static int gat_forward_impl(const float* X, const void* S, int s_is_f64, const f
   p.N = N; p.K = K; p.P = P; p.mode = mode; p.concat = concat; p.s_is_f64 = s_is_f64;
   p.ldx = G; p.ldy = concat ? ldy : P * F; p.NC = ldz; p.lda_a = N | 1;
   p.qoff = L.qoff; p.uoff = L.uoff; p.c1off = L.c1off; p.c2off = L.c2off;
+  p.origin_mask = (mode == MAGAT_MODE_GAT_ORIGIN || cosine) ? 1 : 0;
+  // GAT_Similarity: the graph kernel runs as KeyQuery on the normalised rows gat_cos_prepare_kernel leaves behind the maps GEMM
+  float* Xhat = cosine ? Ytmp + (concat ? 0 : magat_align_up((size_t)B * N * P * F * sizeof(float), 256) / sizeof(float)) : nullptr;
+  if (cosine) { p.X = Xhat; p.mode = MAGAT_MODE_KEYQUERY; }
 
   // One launch of matrix-core products (gat_mfma.hip) when the shape allows; with the range guard on, the two-launch float32
   // form below follows in the same stream, every launch of it predicated on the flag the fused kernel raises.
@@ -1267,12 +1334,13 @@ static int gat_forward_impl(const float* X, const void* S, int s_is_f64, const f
                                  concat ? nullptr : Ytmp, P * F)
         : G != 128 && N <= 32
         ? magat_gat_small_forward(X, G, S, s_is_f64, masks, packed + magat_gat_f16_block_offset(L.NC, G), L.NC, bias, Y, ldy, B,
-                                  N, G, K, P, concat, guard ? status : nullptr, st, reinterpret_cast<const float*>(status + 4))
+                                  N, G, K, P, concat, guard ? status : nullptr, st, reinterpret_cast<const float*>(status + 4),
+                                  cosine ? 1 : 0)
         // (32 / 64 features on 33 .. 128 agents, 128 features on 103 .. 128: gat_mid.hip, a workgroup of ceil(N / 32) waves per
         //  instance - round 6)
         : magat_gat_mid_forward(X, G, S, s_is_f64, packed + magat_gat_f16_block_offset(L.NC, G), L.NC, bias, Y, ldy, B, N, G, K, P,
                                 concat, guard ? status : nullptr, st, reinterpret_cast<const float*>(status + 4),
-                                concat ? nullptr : Ytmp, P * F, G == 128 ? frag : nullptr);
+                                concat ? nullptr : Ytmp, P * F, G == 128 ? frag : nullptr, cosine ? 1 : 0);
     if (rc != MAGAT_OK || !guard) return rc;
     rerun_only = true;
     p.run_if = status;
@@ -1328,8 +1396,16 @@ static int gat_forward_impl(const float* X, const void* S, int s_is_f64, const f
     // own GEMM clears it - status[1] still counts every re-run)
     int rc = rerun_only ? gat_maps_gemm_f32(X + (size_t)b0 * N * G, packed, Z, cb * N, G, L.NC, ldz, stream, p.zts, status,
                                             MAGAT_TAG_RANGE_GUARD)
-                        : magat_gat_maps_gemm(X + (size_t)b0 * N * G, packed, Z, cb * N, G, L.NC, ldz, stream, p.zts, status);
+                        // (GAT_Similarity: float32 MFMA maps - an agent whose features are tiny, |x| ~ 1e-12, is zero in f16
+                        //  planes, and so would be its q_j, whose DIRECTION is what the cosine score reads; nothing to guard then)
+                        : magat_gat_maps_gemm(X + (size_t)b0 * N * G, packed, Z, cb * N, G, L.NC, ldz, stream, p.zts, status,
+                                              cosine ? 1 : 0);
     if (rc != MAGAT_OK) return rc;
+    if (cosine) {
+      rc = magat_gat_cos_prepare(X + (size_t)b0 * N * G, Z, Xhat + (size_t)b0 * N * G, (long long)cb * N, G, L.qoff, ldz, p.zts,
+                                 stream, rerun_only ? status : nullptr);
+      if (rc != MAGAT_OK) return rc;
+    }
     p.B = cb; p.b0 = b0;
     // heads per workgroup: when the LDS tiles allow only one workgroup per CU there is nothing to overlap a
     // workgroup's loads with, so one workgroup walks all P heads of its instance and prefetches the next head's

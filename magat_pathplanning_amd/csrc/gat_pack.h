@@ -28,7 +28,7 @@ struct PackLayout {
 };
 PackLayout pack_layout(int G, int F, int K, int P, int mode) {
   PackLayout L;
-  if (mode == MAGAT_MODE_KEYQUERY) {
+  if (mode == MAGAT_MODE_KEYQUERY || mode == MAGAT_MODE_SIMILARITY) {      // (GAT_Similarity: KeyQuery's layout, P = 1)
     L.qoff = 0;
     L.uoff = P * G;
     L.c1off = L.c2off = 0;

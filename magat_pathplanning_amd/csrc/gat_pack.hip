@@ -15,7 +15,7 @@ __global__ void pack_kernel(const float* __restrict__ weight, const float* __res
   // the same two planes once more in MFMA-fragment order for gat_mfma.hip (G = 128): 128-row blocks of Bt, per block
   // [32-row tile 4][k step 8][plane 2][lane 64][8 halfs], lane = row % 32 + 32 * (k % 16 / 8)
   // (KeyQuery only: the rank-1 modes' stream at the same offset is written by pack_frag_rank1_kernel, with its own size)
-  unsigned short* Fs = (G == 128 && (L.NC & 127) == 0 && mode == MAGAT_MODE_KEYQUERY)
+  unsigned short* Fs = (G == 128 && (L.NC & 127) == 0 && (mode == MAGAT_MODE_KEYQUERY || mode == MAGAT_MODE_SIMILARITY))
                            ? reinterpret_cast<unsigned short*>(packed + magat_gat_frag_offset(L.NC, G)) : nullptr;
   const long long total = (long long)L.NC * G;
   for (long long idx = blockIdx.x * (long long)blockDim.x + threadIdx.x; idx < total + L.NC;
@@ -32,7 +32,7 @@ __global__ void pack_kernel(const float* __restrict__ weight, const float* __res
     }
     const int col = (int)(idx / G), g = (int)(idx % G);
     float v = 0.f;
-    if (mode == MAGAT_MODE_KEYQUERY && col < L.uoff) {
+    if ((mode == MAGAT_MODE_KEYQUERY || mode == MAGAT_MODE_SIMILARITY) && col < L.uoff) {
       v = weight[(long long)col * G + g];  // (P,1,G,G): row p*G+g' = W_p[g',:]
     } else if (col >= L.uoff && col < L.uoff + P * K * F) {
       const int r = col - L.uoff, hp = r / (K * F), k = (r / F) % K, f = r % F;
@@ -42,7 +42,8 @@ __global__ void pack_kernel(const float* __restrict__ weight, const float* __res
         v = taps[k] * weight[((long long)hp * F + g) * G + f];
       else
         v = taps[(((long long)hp * F + f) * K + k) * G + g];  // (P,F,1,K,G)
-    } else if (mode != MAGAT_MODE_KEYQUERY && mode != MAGAT_MODE_GNN && col >= L.c1off && col < L.c2off + P) {
+    } else if (mode != MAGAT_MODE_KEYQUERY && mode != MAGAT_MODE_GNN && mode != MAGAT_MODE_SIMILARITY && col >= L.c1off &&
+               col < L.c2off + P) {
       const int which = col >= L.c2off, hp = which ? col - L.c2off : col - L.c1off;
       for (int f = 0; f < F; ++f)
         v = fmaf(mixer[(long long)hp * 2 * F + which * F + f], weight[((long long)hp * F + f) * G + g], v);
@@ -125,7 +126,7 @@ extern "C" size_t magat_gat_packed_floats(int G, int F, int K, int P, int mode) 
   const PackLayout L = pack_layout(G, F, K, P, mode);
   if (gat_rank1_frag(G, F, mode))      // + the one-launch kernel's weight stream and the per-head score constants
     return magat_gat_frag_offset(L.NC, G) + (size_t)(P * G + P * K * F) * G + (((size_t)P + 3) & ~(size_t)3);
-  if (G == 128 && (L.NC & 127) == 0 && mode == MAGAT_MODE_KEYQUERY)      // + the bf16 fragments of gat_csr_fused.hip (NC * G bf16)
+  if (G == 128 && (L.NC & 127) == 0 && (mode == MAGAT_MODE_KEYQUERY || mode == MAGAT_MODE_SIMILARITY))      // + the bf16 fragments of gat_csr_fused.hip (NC * G bf16)
     return magat_gat_csr_fused_offset(L.NC, G) + (size_t)L.NC * G / 2 + 4;
   return magat_gat_f16_block_offset(L.NC, G) + (size_t)L.NC * G + 4;
 }
@@ -137,7 +138,8 @@ extern "C" int magat_gat_pack_weights(const float* weight, const float* weight_b
   if (mode == MAGAT_MODE_GAT_MODIFIED && (!weight_bias || !mixer)) return MAGAT_ERR_NULL;
   if (mode == MAGAT_MODE_GAT_ORIGIN && !mixer) return MAGAT_ERR_NULL;
   if (G <= 0 || F <= 0 || K <= 0 || P <= 0) return MAGAT_ERR_BAD_SHAPE;
-  if (mode < MAGAT_MODE_KEYQUERY || mode > MAGAT_MODE_GNN) return MAGAT_ERR_UNSUPPORTED;
+  if (mode < MAGAT_MODE_KEYQUERY || mode > MAGAT_MODE_SIMILARITY) return MAGAT_ERR_UNSUPPORTED;
+  if (mode == MAGAT_MODE_SIMILARITY && (P != 1 || G != F)) return MAGAT_ERR_UNSUPPORTED;
   const PackLayout L = pack_layout(G, F, K, P, mode);
   const long long total = (long long)L.NC * (G + 1);
   int blocks = (int)((total + 255) / 256);

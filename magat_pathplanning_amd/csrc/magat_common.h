@@ -166,7 +166,10 @@ enum MagatLdsSlot {
   MAGAT_LDS_SIM_MAPF_LNS,                       // sim_mapf_lns.hip: the R layers
   MAGAT_LDS_SIM_MAPF_CBS,                       // sim_mapf_cbs.hip: the R layers of horizons above 128
   MAGAT_LDS_BLOCK_FULL_P16,                     // block_fused.hip: block_full_p_kernel<true> (layer3.conv2 on 16-row tiles)
-  MAGAT_LDS_END
+  MAGAT_LDS_GATS_COS_0,                         // gat_small.hip, cosine form (GAT_Similarity): 4 slots (width x taps)
+  MAGAT_LDS_GATS_COS_END = MAGAT_LDS_GATS_COS_0 + 4,
+  MAGAT_LDS_GATD_COS_0 = MAGAT_LDS_GATS_COS_END,  // gat_mid.hip, cosine form: 12 slots (width x taps x row tiles) + 2 of the 128-wide form
+  MAGAT_LDS_END = MAGAT_LDS_GATD_COS_0 + 14
 };
 static_assert(MAGAT_LDS_END <= MAGAT_LDS_SLOTS, "LDS attribute slots");
 
@@ -184,13 +187,16 @@ int magat_cast_rows_if(const void* src, void* dst, int to_bf16, long long M, int
 int magat_gat_small_supported(int N, int G, int F, int K, int mode);
 int magat_gat_small_forward(const float* X, int ldx, const void* S, int s_is_f64, const unsigned* rmask_pre, const float* Hs,
                             int NC, const float* bias, float* Y, int ldy, int B, int N, int G, int K, int P, int concat,
-                            int* range_flag, hipStream_t st, const float* x_scale);
+                            int* range_flag, hipStream_t st, const float* x_scale,
+                            int cosine = 0);      // 1: GAT_Similarity's cosine scores (P = 1, range_flag required: tiny rows raise it)
 // one-launch KeyQuery layer for the published widths on graphs of 33 .. 128 agents (gat_mid.hip: G = F in {32, 64}, K = 2 | 3)
 int magat_gat_mid_supported(int N, int G, int F, int K, int mode);
 int magat_gat_mid_forward(const float* X, int ldx, const void* S, int s_is_f64, const float* Hs, int NC, const float* bias, float* Y,
                           int ldy, int B, int N, int G, int K, int P, int concat, int* range_flag, hipStream_t st,
                           const float* x_scale,
-                          float* ypre = nullptr, int ldpre = 0, const float* wfrag = nullptr);      // head-mean scratch rows [B*N][P F]: lets few instances run a workgroup per head
+                          float* ypre = nullptr, int ldpre = 0, const float* wfrag = nullptr,
+                          int cosine = 0);      // 1: GAT_Similarity's cosine scores (P = 1, range_flag required)
+      // head-mean scratch rows [B*N][P F]: lets few instances run a workgroup per head
 // one-launch KeyQuery layer on the matrix cores (gat_mfma.hip)
 int magat_gat_mfma_supported(int N, int G, int F, int K, int mode);
 int magat_gat_mfma_forward(const float* X, int ldx, const void* S, int s_is_f64, const unsigned* rmask_pre,
@@ -208,6 +214,11 @@ int magat_gat_maps_gemm(const float* X, const float* packed, float* Z, int M, in
                         long long ntile_stride = 0,    // > 0: Z in 128-column tiles ntile_stride floats apart (row stride 128)
                         int32_t* status = nullptr,     // range guard status words (device int32[2]) or null: unguarded
                         int force_f32 = 0);            // 1: float32 MFMA kernel (training: Z feeds the backward)
+// GAT_Similarity behind the maps GEMM (gat_f32.hip, gat_cos_prepare_kernel): per row m of M, the G score columns of Z at qoff are
+// divided by max(|.|, 1e-9) in place and Xhat [M][G] = X[m] / max(|X[m]|, 1e-9) is written; the KeyQuery graph kernels then form
+// cosine scores from (Xhat, Z).  Z addressing as magat_gat_maps_gemm's (ldz, ntile_stride); G a supported width.
+int magat_gat_cos_prepare(const float* X, float* Z, float* Xhat, long long M, int G, int qoff, int ldz, long long ntile_stride,
+                          void* stream, const int32_t* run_if = nullptr);      // run_if: the launch is a no-op unless *run_if != 0
 
 // fp32 -> three bf16 planes (round-to-nearest-even each)
 __device__ __forceinline__ unsigned short magat_bf16_rne(float v) {

@@ -7,6 +7,7 @@ the layer evaluates the same algebra with differentiable torch ops on whatever d
 tensors live on -- that composite exists for backward only and is never used for inference.  On GPU tensors the
 training forward and backward of the graph part run on the HIP kernels too (_GatTrainFunction); the composite then only
 serves CPU tensors (the gloo / host tests) and requests for the dense attention tensor under autograd.
+GraphFilterBatchSimilarityAttentional (attentionMode 'GAT_Similarity') has no HIP backward: under autograd it always takes the composite.
 """
 import math
 import os
@@ -18,7 +19,9 @@ import torch.nn as nn
 from . import _native as nat
 
 ZERO_TOLERANCE = 1e-9
-_MODES = {"KeyQuery": nat.MODE_KEYQUERY, "GAT_modified": nat.MODE_GAT_MODIFIED, "GAT_origin": nat.MODE_GAT_ORIGIN}
+_MODES = {"KeyQuery": nat.MODE_KEYQUERY, "GAT_modified": nat.MODE_GAT_MODIFIED, "GAT_origin": nat.MODE_GAT_ORIGIN,
+          "GAT_Similarity": nat.MODE_SIMILARITY}
+_KEYQUERY_PACK = ("KeyQuery", "GAT_Similarity")      # pack layout [W_p | H_pk], no score columns, zero column bias
 
 
 class _Scratch:
@@ -77,7 +80,7 @@ def _flat_bias(layer, dev):
 
 def _packed_cols(mode_name, G, F, K, P):
     """NC: rows of the packed matrix Bt [NC][G] (pack_layout in csrc/gat_pack.h) = columns of the layer's one dense product."""
-    return P * G + P * K * F if mode_name == "KeyQuery" else (P * K * F + 2 * P + 31) // 32 * 32
+    return P * G + P * K * F if mode_name in _KEYQUERY_PACK else (P * K * F + 2 * P + 31) // 32 * 32
 
 
 def _packed_weights(layer, dev, stream, G, F, K, P, mode):
@@ -320,6 +323,10 @@ def gat_forward_rows(X, S, layer, out=None, want_attention=False, csr=None):
     _require_device(X)
     lib = nat.lib()
     B, N, G = X.shape
+    if getattr(layer, "_similarity", False):
+        layer._check_forward(B, N)
+        if X.dtype == torch.bfloat16:
+            raise NotImplementedError("GAT_Similarity is built with float32 storage only (got bfloat16 rows)")
     F, K, P = layer.F, layer.K, layer.P
     mode = _MODES[layer.attentionMode]
     concat = 1 if layer.concatenate else 0
@@ -376,7 +383,7 @@ def pack_torch(weight, weight_bias, mixer, taps, mode_name):
         P, F, _, K, G = taps.shape
         U = taps[:, :, 0].permute(0, 2, 1, 3).reshape(P * K * F, G)
     nc = _packed_cols(mode_name, G, F, K, P)
-    if mode_name == "KeyQuery":
+    if mode_name in _KEYQUERY_PACK:
         Bt = torch.cat((weight[:, 0].reshape(P * G, G), U), dim=0)
         return Bt, torch.zeros(nc, dtype=Bt.dtype, device=Bt.device)
     W = weight[:, 0]                                            # (P,F,G)
@@ -491,12 +498,16 @@ def _composite(layer, x, S):
     B, G, N = x.shape
     P, F, K = layer.P, layer.F, layer.K
     X = x.transpose(1, 2)                                            # B,N,G
-    if layer.attentionMode == "GAT_origin":
+    if layer.edge_rule == 1:                 # GAT_origin, GAT_Similarity: self-loops added in float32 (graphML.py:1018, 1503)
         S = S.detach().float() + torch.eye(N, dtype=torch.float32, device=S.device).view(1, 1, N, N)
     M = (S.detach().abs().sum(dim=1) > ZERO_TOLERANCE).to(x.dtype).unsqueeze(1)   # B,1,N,N
     if layer.attentionMode == "KeyQuery":
         Q = torch.einsum("bng,pog->bpno", X, layer.weight[:, 0])     # q_j = W x_j
         e = torch.einsum("big,bpjg->bpij", X, Q)
+    elif layer.attentionMode == "GAT_Similarity":
+        # e_ij = cos(x_i, W x_j) with torch's own op, as graphML.py:1515-1536 (eps = 1e-9 on each norm)
+        Q = torch.einsum("bng,pog->bpno", X, layer.weight[:, 0])
+        e = nn.functional.cosine_similarity(X[:, None, :, None, :], Q[:, :, None, :, :], dim=4, eps=ZERO_TOLERANCE)
     else:
         Wx = torch.einsum("bng,pfg->bpnf", X, layer.weight[:, 0])
         if layer.attentionMode != "GAT_origin":
@@ -569,13 +580,17 @@ class GraphFilterBatchAttentional(_DropsDeviceState, nn.Module):
     """Drop-in for the reference class of the same name (graphML.py:4506-4685)."""
 
     _edge_views = None
+    _similarity = False          # GraphFilterBatchSimilarityAttentional
+    _hip_backward = True         # the graph part of a training step on the HIP kernels (_GatTrainFunction)
 
     def __init__(self, G, F, K, P, E=1, bias=True, nonlinearity=nn.functional.relu, concatenate=True,
                  attentionMode="GAT_modified"):
         super().__init__()
         # E > 1 and nonlinearities other than ReLU take the general path of forward() (round 4): the models use E = 1 and ReLU
-        if attentionMode not in _MODES:
-            raise NotImplementedError("attentionMode %r: KeyQuery and GAT_modified are built" % (attentionMode,))
+        if attentionMode not in _MODES or (attentionMode == "GAT_Similarity") != self._similarity:
+            raise NotImplementedError("attentionMode %r: this class runs KeyQuery and GAT_modified (GAT_origin: "
+                                      "GraphFilterBatchAttentional_Origin, GAT_Similarity: "
+                                      "GraphFilterBatchSimilarityAttentional)" % (attentionMode,))
         self.G, self.F, self.K, self.P, self.E = G, F, K, P, E
         self.S = None
         self.aij = None
@@ -603,7 +618,7 @@ class GraphFilterBatchAttentional(_DropsDeviceState, nn.Module):
     @property
     def edge_rule(self):
         """Edge rule of the CSR builders (magat_gso_row_degrees): 0 |S| > 1e-9, 1 GAT_origin's |float(S) + I| > 1e-9."""
-        return 1 if self.attentionMode == "GAT_origin" else 0
+        return 1 if self.attentionMode in ("GAT_origin", "GAT_Similarity") else 0
 
     def _pack_tensors(self):
         return self.weight, self.weight_bias, self.mixer, self.filterWeight
@@ -641,7 +656,7 @@ class GraphFilterBatchAttentional(_DropsDeviceState, nn.Module):
         needs_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
         if self.E != 1 or not _is_relu(self.nonlinearity):
             y = self._forward_general(x)
-        elif needs_grad and x.is_cuda and not self.return_attention:
+        elif needs_grad and x.is_cuda and not self.return_attention and self._hip_backward:
             # training on the GPU: HIP forward + backward of the graph layer (CSR kernels), ReLU / head merge in torch
             N = self.N
             rowptr, colidx, nnz = dense_gso_to_csr(_gso3(self.S, B, N, x.device), self_loops=self.edge_rule)
@@ -746,6 +761,54 @@ class GraphFilterBatchAttentional_Origin(GraphFilterBatchAttentional):
             self.filterWeight.uniform_(-stdv, stdv)
             if self.bias is not None:
                 self.bias.uniform_(-stdv, stdv)
+
+
+class GraphFilterBatchSimilarityAttentional(GraphFilterBatchAttentional):
+    """Drop-in for the reference class of the same name (graphML.py:4690-4857), attentionMode 'GAT_Similarity': cosine scores
+    e_ij = cos(x_i, W x_j), each norm clamped at 1e-9 (graphML.py:1515-1536), under GAT_origin's mask |float(S) + I| > 1e-9
+    (:1503, 1553-1564), then KeyQuery's filter with the full taps (:2151-2179).  Parameters in the reference's order: mixer
+    (P,E,2F), weight_bias (P,E,F), weight (P,E,F,G), filterWeight (P,F,E,K,G), bias (F,1); mixer and weight_bias are never read.
+    The reference reshapes weight into (G,G) and the input into (B,P,E,G,N,1): F == G is required here at construction, and
+    P * E != 1 raises RuntimeError in forward, where the reference's reshape raises it.  Inference: the KeyQuery kernels behind
+    one normalisation kernel (MAGAT_MODE_SIMILARITY, float32 storage only); under autograd always the torch composite - the
+    HIP backward is not built for this mode."""
+
+    _similarity = True
+    _hip_backward = False
+
+    def __init__(self, G, F, K, P, E=1, bias=True, nonlinearity=nn.functional.relu, concatenate=True,
+                 attentionMode="GAT_Similarity"):
+        if G != F:
+            raise NotImplementedError("GAT_Similarity needs F == G (the reference reshapes W (P,E,F,G) into (1,P,E,G,G))")
+        super().__init__(G, F, K, P, E, bias, nonlinearity, concatenate, "GAT_Similarity")
+
+    def _register_parameters(self, bias):
+        # (state_dict order: mixer, weight_bias, weight, filterWeight, bias)
+        G, F, K, P, E = self.G, self.F, self.K, self.P, self.E
+        self.mixer = nn.Parameter(torch.empty(P, E, 2 * F))
+        self.weight_bias = nn.Parameter(torch.empty(P, E, F))
+        self.weight = nn.Parameter(torch.empty(P, E, F, G))
+        self.filterWeight = nn.Parameter(torch.empty(P, F, E, K, G))
+        _register_bias(self, bias)
+
+    def _pack_tensors(self):
+        return self.weight, None, None, self.filterWeight
+
+    def _check_forward(self, B, N):
+        """What the reference's forward raises, and what is not built - before anything is launched (layer.forward, and the
+        planner's direct call of gat_forward_rows)."""
+        if self.P * self.E != 1:
+            # graphML.py:1532: x (B,1,1,G,N) does not reshape into (B,P,E,G,N,1)
+            raise RuntimeError("shape '[%d, %d, %d, %d, %d, 1]' is invalid for input of size %d (GAT_Similarity runs with one "
+                               "attention head and one edge feature)" % (B, self.P, self.E, self.G, N, B * self.G * N))
+        if not _is_relu(self.nonlinearity):
+            raise NotImplementedError("GAT_Similarity is built with the ReLU nonlinearity only")
+        if self.storage_dtype == torch.bfloat16:
+            raise NotImplementedError("GAT_Similarity is built with float32 storage only (storage_dtype = bfloat16 is not)")
+
+    def forward(self, x):
+        self._check_forward(x.shape[0], self.N if self.S is not None else x.shape[2])
+        return super().forward(x)
 
 
 class _GnnTrainFunction(torch.autograd.Function):

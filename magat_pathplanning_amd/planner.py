@@ -34,7 +34,7 @@ import torch.nn as nn
 from . import _native as nat
 from . import encoder as enc
 from .graphml import (_MODES, _flat_bias, _gso3, CsrStructure, dense_route, GraphFilterBatchAttentional,
-                      GraphFilterBatchAttentional_Origin, gat_forward_rows)
+                      GraphFilterBatchAttentional_Origin, GraphFilterBatchSimilarityAttentional, gat_forward_rows)
 from .resnet import ResNet, ResNetSlim
 
 # config.bottleneckMode -> what the reference file of that name feeds the action MLP (the GAT files ..._GAT_bottleneck*.py
@@ -582,10 +582,11 @@ class DecentralPlannerGATNet(_PlannerBase):
         self.P = [config.nAttentionHeads]
         self.E = 1
         self.bias = True
-        if config.attentionMode not in ("GAT_modified", "KeyQuery", "GAT_origin"):
+        if config.attentionMode not in ("GAT_modified", "KeyQuery", "GAT_origin", "GAT_Similarity"):
             raise NotImplementedError("attentionMode %r is outside the built hot path (SURVEY.md section 8(f))"
                                       % (config.attentionMode,))
-        layer_cls = GraphFilterBatchAttentional_Origin if config.attentionMode == "GAT_origin" else GraphFilterBatchAttentional
+        layer_cls = {"GAT_origin": GraphFilterBatchAttentional_Origin,
+                     "GAT_Similarity": GraphFilterBatchSimilarityAttentional}.get(config.attentionMode, GraphFilterBatchAttentional)
         self.GFL = nn.Sequential(layer_cls(
             self.F[0], self.F[1], self.K[0], self.P[0], self.E, self.bias,
             concatenate=config.AttentionConcat, attentionMode=config.attentionMode))
@@ -595,6 +596,8 @@ class DecentralPlannerGATNet(_PlannerBase):
         if storage not in ("fp32", "bf16"):
             raise ValueError("config.gat_storage must be 'fp32' or 'bf16', got %r" % (storage,))
         if storage == "bf16":
+            if config.attentionMode == "GAT_Similarity":
+                raise NotImplementedError("config.gat_storage='bf16' is not built for attentionMode 'GAT_Similarity' (float32 only)")
             self.GFL[0].storage_dtype = torch.bfloat16
 
         width = self.F[-1] * config.nAttentionHeads if config.AttentionConcat else self.F[-1]
