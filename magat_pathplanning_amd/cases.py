@@ -16,6 +16,7 @@ for the device; valid_cases reads `valid` back once."""
 import torch
 
 from . import _native as nat
+from . import _sim_host as sh
 
 KINDS = {"maze": 0, "uniform": 1, "given": 2}      # include/magat_hip.h MAGAT_CASES_*
 CASE_KEYS = ("map", "start", "goal", "free_cells", "valid")
@@ -59,8 +60,8 @@ def generate_cases(C, H, W, N, density=0.1, complexity=0.01, kind="maze", obstac
     dev = torch.device(device)
     if dev.type != "cuda":
         raise nat.MagatNativeError("generate_cases: device must be a GPU (no CPU fallback), got %r" % (device,))
-    if obstacle_map is not None and (not isinstance(obstacle_map, torch.Tensor) or not obstacle_map.is_cuda):
-        raise nat.MagatNativeError("obstacle_map must be a device tensor (no CPU fallback)")
+    if obstacle_map is not None:
+        sh.dev_tensor(obstacle_map, "obstacle_map")
     if dev.index is None:
         dev = torch.device("cuda", torch.cuda.current_device())
     m = None
@@ -68,9 +69,8 @@ def generate_cases(C, H, W, N, density=0.1, complexity=0.01, kind="maze", obstac
         if kind not in ("maze", "given"):
             raise ValueError("obstacle_map implies kind='given', got kind=%r" % (kind,))
         kind = "given"
-        m = obstacle_map.to(dev).to(torch.uint8).contiguous()
-        assert m.dim() in (2, 3) and tuple(m.shape[-2:]) == (H, W) and (m.dim() == 2 or m.shape[0] == C), \
-            "obstacle_map must be (H,W) or (C,H,W)"
+        m, _, mH, mW = sh.dev_map(obstacle_map.to(dev), C)
+        assert (mH, mW) == (H, W), "obstacle_map must be (H,W) or (C,H,W)"
     if kind not in KINDS:
         raise ValueError("kind must be one of %s, got %r" % (sorted(KINDS), kind))
     if kind == "given" and m is None:
@@ -84,12 +84,9 @@ def generate_cases(C, H, W, N, density=0.1, complexity=0.01, kind="maze", obstac
                free_cells=torch.empty(max(C, 0), dtype=torch.int32, device=dev),
                valid=torch.empty(max(C, 0), dtype=torch.uint8, device=dev))
     entry = "magat_sim_cases_generate_wide" if wide and (H > MAX_SIDE or W > MAX_SIDE) else "magat_sim_cases_generate"
-    with torch.cuda.device(dev):
-        nat.check(getattr(nat.lib(), entry)(KINDS[kind], nat.ptr(m), 1 if m is not None and m.dim() == 3 else 0, H, W,
-                                            aisles, walk, threshold, int(seed) & ((1 << 64) - 1), int(first_case),
-                                            nat.ptr(out["map"]), nat.ptr(out["start"]), nat.ptr(out["goal"]),
-                                            nat.ptr(out["free_cells"]), nat.ptr(out["valid"]), C, N, nat.current_stream(dev)),
-                  entry)
+    sh.call(dev, entry, KINDS[kind], nat.ptr(m), 1 if m is not None and m.dim() == 3 else 0, H, W, aisles, walk, threshold,
+            int(seed) & ((1 << 64) - 1), int(first_case), nat.ptr(out["map"]), nat.ptr(out["start"]), nat.ptr(out["goal"]),
+            nat.ptr(out["free_cells"]), nat.ptr(out["valid"]), C, N)
     return out
 
 

@@ -23,7 +23,8 @@ import numpy as np
 import torch
 
 from . import _native as nat
-from .simulator import GUIDANCE_MODES, _dev_i32, batched_fov_states, batched_gso, new_agent_view, replayed_semi_states
+from . import _sim_host as sh
+from .simulator import GUIDANCE_MODES, batched_fov_states, batched_gso, new_agent_view, replayed_semi_states
 
 # expert_samples works on chunks of cases that hold at most this many (case, step, agent) samples (padded steps included)
 MAX_AGENT_STEPS = 1 << 18
@@ -82,8 +83,8 @@ def expert_schedule(paths, lengths, goal, makespan, T=None, check=False):
     the five leaves its target row zero and sets bad[c] = t * N + n of the first one in (t, n) order (-1: none); check=True
     reads `bad` (the one host synchronisation) and raises ValueError naming case, step and agent, as the reference's
     list.index does."""
-    paths, lengths = _dev_i32(paths, "paths"), _dev_i32(lengths, "lengths")
-    goal, makespan = _dev_i32(goal, "goal"), _dev_i32(makespan, "makespan")
+    paths, lengths = sh.dev_i32(paths, "paths"), sh.dev_i32(lengths, "lengths")
+    goal, makespan = sh.dev_i32(goal, "goal"), sh.dev_i32(makespan, "makespan")
     assert paths.dim() == 4 and paths.shape[3] == 2, "paths must be (C,N,Lmax,2)"
     C, N, Lmax, _ = paths.shape
     assert tuple(lengths.shape) == (C, N) and tuple(goal.shape) == (C, N, 2) and makespan.numel() == C
@@ -95,21 +96,13 @@ def expert_schedule(paths, lengths, goal, makespan, T=None, check=False):
     target = torch.empty(C, T, N, 5, dtype=torch.float32, device=dev)
     valid = torch.empty(C, T, dtype=torch.uint8, device=dev)
     bad = torch.empty(C, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        nat.check(nat.lib().magat_sim_expert_schedule(nat.ptr(paths), nat.ptr(lengths), nat.ptr(goal), nat.ptr(makespan),
-                                                      nat.ptr(pos), nat.ptr(target), nat.ptr(valid), nat.ptr(bad), C, N, Lmax, T,
-                                                      nat.current_stream(dev)), "magat_sim_expert_schedule")
+    sh.call(dev, "magat_sim_expert_schedule", nat.ptr(paths), nat.ptr(lengths), nat.ptr(goal), nat.ptr(makespan), nat.ptr(pos),
+            nat.ptr(target), nat.ptr(valid), nat.ptr(bad), C, N, Lmax, T)
     if check:
         msg = bad_move_message(bad.cpu(), N)
         if msg is not None:
             raise ValueError(msg)
     return dict(pos=pos, target=target, valid=valid, bad=bad)
-
-
-def _dev_u8(t, name):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise nat.MagatNativeError("%s must be a device tensor (no CPU fallback)" % name)
-    return t.to(torch.uint8).contiguous()
 
 
 def expert_radius(pos, valid, comm_radius, max_steps=64, return_step_grow=False):
@@ -118,7 +111,7 @@ def expert_radius(pos, valid, comm_radius, max_steps=64, return_step_grow=False)
     threshold *= 1.1 (float64) until every valid step's graph is connected; that one radius serves every step.  pos (C,T,N,2),
     valid (C,T) -> radii (C,) float64 (bit-equal to the reference's chain of multiplications), grow_steps (C,) int32 (the
     number of multiplications; -1: a step is still disconnected after max_steps of them)."""
-    pos, valid = _dev_i32(pos, "pos"), _dev_u8(valid, "valid")
+    pos, valid = sh.dev_i32(pos, "pos"), sh.dev_u8(valid, "valid")
     assert pos.dim() == 4 and pos.shape[3] == 2, "pos must be (C,T,N,2)"
     C, T, N, _ = pos.shape
     assert tuple(valid.shape) == (C, T)
@@ -126,10 +119,8 @@ def expert_radius(pos, valid, comm_radius, max_steps=64, return_step_grow=False)
     step_grow = torch.empty(C, T, dtype=torch.int32, device=dev)
     radii = torch.empty(C, dtype=torch.float64, device=dev)
     grow = torch.empty(C, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        nat.check(nat.lib().magat_sim_expert_radius(nat.ptr(pos), nat.ptr(valid), float(comm_radius), nat.ptr(step_grow),
-                                                    nat.ptr(radii), nat.ptr(grow), C, T, N, int(max_steps),
-                                                    nat.current_stream(dev)), "magat_sim_expert_radius")
+    sh.call(dev, "magat_sim_expert_radius", nat.ptr(pos), nat.ptr(valid), float(comm_radius), nat.ptr(step_grow), nat.ptr(radii),
+            nat.ptr(grow), C, T, N, int(max_steps))
     return (radii, grow, step_grow) if return_step_grow else (radii, grow)
 
 
@@ -139,10 +130,8 @@ def expert_stats(target, start, goal, valid):
     the first non-stop action / first arrival, 0 when the agent never moves / never arrives, like the reference -,
     makespanTarget = max(end) - min(first) + 1 and flowtimeTarget = sum(end - first + 1) (C,) int32, expert_pos (C,T+1,N,2)
     int32)."""
-    if not isinstance(target, torch.Tensor) or not target.is_cuda:
-        raise nat.MagatNativeError("target must be a device tensor (no CPU fallback)")
-    target = target.float().contiguous()
-    start, goal, valid = _dev_i32(start, "start"), _dev_i32(goal, "goal"), _dev_u8(valid, "valid")
+    target = sh.dev_tensor(target, "target").float().contiguous()
+    start, goal, valid = sh.dev_i32(start, "start"), sh.dev_i32(goal, "goal"), sh.dev_u8(valid, "valid")
     assert target.dim() == 4 and target.shape[3] == 5, "target must be (C,T,N,5)"
     C, T, N, _ = target.shape
     assert tuple(start.shape) == (C, N, 2) and tuple(goal.shape) == (C, N, 2) and tuple(valid.shape) == (C, T)
@@ -152,10 +141,8 @@ def expert_stats(target, start, goal, valid):
     mk = torch.empty(C, dtype=torch.int32, device=dev)
     flow = torch.empty(C, dtype=torch.int32, device=dev)
     epos = torch.empty(C, T + 1, N, 2, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        nat.check(nat.lib().magat_sim_expert_stats(nat.ptr(target), nat.ptr(start), nat.ptr(goal), nat.ptr(valid), nat.ptr(first),
-                                                   nat.ptr(end), nat.ptr(mk), nat.ptr(flow), nat.ptr(epos), C, T, N,
-                                                   nat.current_stream(dev)), "magat_sim_expert_stats")
+    sh.call(dev, "magat_sim_expert_stats", nat.ptr(target), nat.ptr(start), nat.ptr(goal), nat.ptr(valid), nat.ptr(first), nat.ptr(end),
+            nat.ptr(mk), nat.ptr(flow), nat.ptr(epos), C, T, N)
     return dict(expert_first_move=first, expert_end_step=end, makespanTarget=mk, flowtimeTarget=flow, expert_pos=epos)
 
 
@@ -191,16 +178,13 @@ def expert_samples(obstacle_map, paths, lengths, goal, makespan, comm_radius, dy
         raise ValueError("guidance must be one of %s, got %r" % (sorted(GUIDANCE_MODES), guidance))
     if gso_dtype not in (torch.float32, torch.float64):
         raise TypeError("expert_samples: gso_dtype must be torch.float32 or torch.float64, got %s" % (gso_dtype,))
-    if not isinstance(obstacle_map, torch.Tensor) or not obstacle_map.is_cuda:
-        raise nat.MagatNativeError("obstacle_map must be a device tensor (no CPU fallback)")
+    sh.dev_tensor(obstacle_map, "obstacle_map")      # refused before the schedule's launch
     sched = expert_schedule(paths, lengths, goal, makespan, T=T, check=check)
     pos, target, valid = sched["pos"], sched["target"], sched["valid"]
-    goal = _dev_i32(goal, "goal")
+    goal = sh.dev_i32(goal, "goal")
     C, T, N, _ = pos.shape
     dev = pos.device
-    m = obstacle_map.to(torch.uint8).contiguous()
-    assert m.dim() in (2, 3) and (m.dim() == 2 or m.shape[0] == C), "obstacle_map must be (H,W) or (C,H,W)"
-    H, W = m.shape[-2], m.shape[-1]
+    m, _, H, W = sh.dev_map(obstacle_map, C)
     if dynamic_commR:
         radii, grow = expert_radius(pos, valid, comm_radius, max_steps=max_steps)
         if bool((grow < 0).any().item()):
@@ -249,7 +233,7 @@ def expert_samples(obstacle_map, paths, lengths, goal, makespan, comm_radius, dy
         r = radii.index_select(0, case) if dynamic_commR else float(comm_radius)
         Sf.index_copy_(0, idx, batched_gso(p, r, symmetric_norm=symmetric_norm, dtype=gso_dtype))
     return dict(inputTensor=x, target=target, GSO=S, pos=pos, valid=valid, radii=radii, grow_steps=grow,
-                makespan=_dev_i32(makespan, "makespan"), bad=sched["bad"])
+                makespan=sh.dev_i32(makespan, "makespan"), bad=sched["bad"])
 
 
 def flatten_samples(samples):

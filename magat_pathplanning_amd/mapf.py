@@ -73,7 +73,7 @@ solve_cases reads `solved` back once per round."""
 import torch
 
 from . import _native as nat
-from .simulator import _dev_i32
+from . import _sim_host as sh
 
 MAX_HORIZON = 256
 MAX_SIDE = 64
@@ -89,6 +89,44 @@ MAX_W_MILLI_ECBS = 1 << 20   # ecbs_cases: round(1000 w)
 
 def default_horizon(H, W, N, wide=False):
     return min(WIDE_MAX_HORIZON if wide else MAX_HORIZON, 2 * (H + W) + N)
+
+
+def _route(H, W, T, wide, refuses=True):
+    """Which form serves an H x W map with horizon T: "narrow", "wide" or "refuse".  A shape inside the narrow limits goes to the
+    narrow entry with or without wide=True (plan_prioritized's rule).  Beyond them improve_schedules, audit_schedules and the
+    searches refuse in Python, in _limits' words, unless wide=True and the shape is inside the wide limits.  plan_prioritized
+    (refuses=False) never does: it hands the shape to the entry the keyword names, and the library refuses."""
+    if H <= MAX_SIDE and W <= MAX_SIDE and T <= MAX_HORIZON:
+        return "narrow"
+    if not refuses:
+        return "wide" if wide else "narrow"
+    return "wide" if wide and H <= WIDE_MAX_SIDE and W <= WIDE_MAX_SIDE and T <= WIDE_MAX_HORIZON else "refuse"
+
+
+def _limits(who, H, W, T, N=None, max_nodes=None, levels=None, wide=False, keyword=False):
+    """The shape refusal of improve_schedules, audit_schedules, cbs_cases, ecbs_cases, ecbs_cases_wide and of solve_cases'
+    early check, in the name of `who`: MagatNativeError naming what the caller takes and what it got.  N, max_nodes, levels: given
+    where the caller has that limit.  wide: the wide forms' limits apply.  keyword: the caller takes wide= itself (the message
+    says what the keyword would lift, and N has a refusal of its own behind the shape's)."""
+    side, horizon = (WIDE_MAX_SIDE, WIDE_MAX_HORIZON) if wide else (MAX_SIDE, MAX_HORIZON)
+    takes, got = ["maps up to %d x %d" % (side, side), "horizons up to %d" % horizon], ["%d x %d" % (H, W), "%d" % T]
+    bad = _route(H, W, T, wide) == "refuse"
+    name = who + "(wide=True)" if keyword and wide else who
+    if keyword:
+        tail = "" if wide else (" (wide=True takes maps up to %d x %d and horizons up to %d)"
+                                % (WIDE_MAX_SIDE, WIDE_MAX_SIDE, WIDE_MAX_HORIZON))
+    else:
+        tail = "" if wide else " (it has no wide form)"
+        for value, text, least, most in ((N, "%d agents", 0, MAX_AGENTS_AUDIT), (max_nodes, "1..%d nodes per case", 1, MAX_NODES_CBS),
+                                         (levels, "1..%d levels", 1, MAX_LEVELS_ECBS)):
+            if value is not None:
+                takes.append(text % most)
+                got.append("%d" % value)
+                bad = bad or not least <= value <= most
+    if bad:
+        raise nat.MagatNativeError("%s takes %s and %s, not %s%s" % (name, ", ".join(takes[:-1]), takes[-1], " / ".join(got), tail))
+    if keyword and N is not None and N > MAX_AGENTS_AUDIT:
+        raise nat.MagatNativeError("%s takes at most %d agents per case, not %d" % (who, MAX_AGENTS_AUDIT, N))
 
 
 def plan_prioritized(obstacle_map, start, goal, order=None, horizon=None, wide=False):
@@ -110,33 +148,23 @@ def plan_prioritized(obstacle_map, start, goal, order=None, horizon=None, wide=F
     workspace of horizon * 6 * 64 ceil(H / 64) * (1, 2 or 4 words >= W / 64) * 8 bytes per case.  wide=False refuses H or W
     above 64 and horizons above 256 as before.
     Stream ordered, no host synchronisation."""
-    start, goal = _dev_i32(start, "start"), _dev_i32(goal, "goal")
-    if not isinstance(obstacle_map, torch.Tensor) or not obstacle_map.is_cuda:
-        raise nat.MagatNativeError("obstacle_map must be a device tensor (no CPU fallback)")
-    m = obstacle_map.to(torch.uint8).contiguous()
-    assert start.dim() == 3 and start.shape[2] == 2 and goal.shape == start.shape, "start and goal must be (C,N,2)"
-    C, N, _ = start.shape
-    assert m.dim() in (2, 3) and (m.dim() == 2 or m.shape[0] == C), "obstacle_map must be (H,W) or (C,H,W)"
-    H, W = m.shape[-2], m.shape[-1]
+    m, batched, start, goal, C, N, H, W = sh.dev_cases(obstacle_map, start, goal)
     if order is not None:
-        order = _dev_i32(order, "order")
+        order = sh.dev_i32(order, "order")
         assert tuple(order.shape) == (C, N), "order must be (C,N)"
     T = default_horizon(H, W, N, wide) if horizon is None else int(horizon)
     dev = start.device
     lib = nat.lib()
-    to_wide = bool(wide) and (H > MAX_SIDE or W > MAX_SIDE or T > MAX_HORIZON)
+    to_wide = _route(H, W, T, wide, refuses=False) == "wide"
     paths = torch.empty(C, N, T, 2, dtype=torch.int32, device=dev)
     lengths = torch.empty(C, N, dtype=torch.int32, device=dev)
     makespan = torch.empty(C, dtype=torch.int32, device=dev)
     solved = torch.empty(C, dtype=torch.uint8, device=dev)
     failed = torch.empty(C, dtype=torch.int32, device=dev)
-    ws_bytes = lib.magat_sim_mapf_wide_workspace_bytes(C, H, W, T) if to_wide else lib.magat_sim_mapf_workspace_bytes(C, T)
-    ws = torch.empty(max(int(ws_bytes), 8), dtype=torch.uint8, device=dev)
-    entry = "magat_sim_mapf_plan_wide" if to_wide else "magat_sim_mapf_plan"
-    with torch.cuda.device(dev):
-        nat.check(getattr(lib, entry)(nat.ptr(m), 1 if m.dim() == 3 else 0, H, W, nat.ptr(start), nat.ptr(goal),
-                                      nat.ptr(order), nat.ptr(paths), nat.ptr(lengths), nat.ptr(makespan), nat.ptr(solved),
-                                      nat.ptr(failed), nat.ptr(ws), ws.numel(), C, N, T, nat.current_stream(dev)), entry)
+    ws = sh.scratch(lib.magat_sim_mapf_wide_workspace_bytes(C, H, W, T) if to_wide else lib.magat_sim_mapf_workspace_bytes(C, T), dev)
+    sh.call(dev, "magat_sim_mapf_plan_wide" if to_wide else "magat_sim_mapf_plan", nat.ptr(m), batched, H, W, nat.ptr(start),
+            nat.ptr(goal), nat.ptr(order), nat.ptr(paths), nat.ptr(lengths), nat.ptr(makespan), nat.ptr(solved), nat.ptr(failed),
+            nat.ptr(ws), ws.numel(), C, N, T)
     return dict(paths=paths, lengths=lengths, goal=goal, start=start, makespan=makespan, solved=solved, failed_agent=failed)
 
 
@@ -167,39 +195,23 @@ def improve_schedules(obstacle_map, res, iterations=32, neighbourhood=4, wide=Fa
     raises MagatNativeError.
     Stream ordered, no host synchronisation."""
     paths = res["paths"]
-    if not isinstance(obstacle_map, torch.Tensor) or not obstacle_map.is_cuda or not paths.is_cuda:
-        raise nat.MagatNativeError("obstacle_map and the schedules must be device tensors (no CPU fallback)")
-    m = obstacle_map.to(torch.uint8).contiguous()
-    assert paths.dim() == 4 and paths.shape[3] == 2, "paths must be (C,N,T,2)"
-    C, N, T, _ = paths.shape
-    assert m.dim() in (2, 3) and (m.dim() == 2 or m.shape[0] == C), "obstacle_map must be (H,W) or (C,H,W)"
-    H, W = m.shape[-2], m.shape[-1]
-    to_wide = H > MAX_SIDE or W > MAX_SIDE or T > MAX_HORIZON
-    if to_wide and not wide:
-        raise nat.MagatNativeError("improve_schedules takes maps up to %d x %d and horizons up to %d, not %d x %d / %d "
-                                   "(wide=True takes maps up to %d x %d and horizons up to %d)"
-                                   % (MAX_SIDE, MAX_SIDE, MAX_HORIZON, H, W, T, WIDE_MAX_SIDE, WIDE_MAX_SIDE, WIDE_MAX_HORIZON))
-    if H > WIDE_MAX_SIDE or W > WIDE_MAX_SIDE or T > WIDE_MAX_HORIZON:
-        raise nat.MagatNativeError("improve_schedules(wide=True) takes maps up to %d x %d and horizons up to %d, not %d x %d / %d"
-                                   % (WIDE_MAX_SIDE, WIDE_MAX_SIDE, WIDE_MAX_HORIZON, H, W, T))
+    m, batched, C, N, T, H, W = sh.dev_schedules(obstacle_map, paths)
+    _limits("improve_schedules", H, W, T, wide=bool(wide), keyword=True)
+    to_wide = _route(H, W, T, wide) == "wide"
     dev = paths.device
     out = {key: value for key, value in res.items() if key != "T"}
-    out["paths"] = _dev_i32(paths, "paths").clone()
-    out["lengths"] = _dev_i32(res["lengths"], "lengths").clone()
-    out["makespan"] = _dev_i32(res["makespan"], "makespan").clone()
+    out["paths"] = sh.dev_i32(paths, "paths").clone()
+    out["lengths"] = sh.dev_i32(res["lengths"], "lengths").clone()
+    out["makespan"] = sh.dev_i32(res["makespan"], "makespan").clone()
     solved = res["solved"].to(torch.uint8).contiguous()
     assert tuple(out["lengths"].shape) == (C, N) and out["makespan"].numel() == C and solved.numel() == C
     extra = torch.empty(4, C, dtype=torch.int32, device=dev)
     lib = nat.lib()
-    ws_bytes = (lib.magat_sim_mapf_improve_wide_workspace_bytes(C, H, W, N, T) if to_wide
-                else lib.magat_sim_mapf_improve_workspace_bytes(C, N, T))
-    ws = torch.empty(max(int(ws_bytes), 8), dtype=torch.uint8, device=dev)
-    entry = "magat_sim_mapf_improve_wide" if to_wide else "magat_sim_mapf_improve"
-    with torch.cuda.device(dev):
-        nat.check(getattr(lib, entry)(nat.ptr(m), 1 if m.dim() == 3 else 0, H, W, nat.ptr(solved), nat.ptr(out["paths"]),
-                                      nat.ptr(out["lengths"]), nat.ptr(out["makespan"]), nat.ptr(extra[0]), nat.ptr(extra[1]),
-                                      nat.ptr(extra[2]), nat.ptr(extra[3]), nat.ptr(ws), ws.numel(), C, N, T, int(iterations),
-                                      int(neighbourhood), nat.current_stream(dev)), entry)
+    ws = sh.scratch(lib.magat_sim_mapf_improve_wide_workspace_bytes(C, H, W, N, T) if to_wide
+                    else lib.magat_sim_mapf_improve_workspace_bytes(C, N, T), dev)
+    sh.call(dev, "magat_sim_mapf_improve_wide" if to_wide else "magat_sim_mapf_improve", nat.ptr(m), batched, H, W, nat.ptr(solved),
+            nat.ptr(out["paths"]), nat.ptr(out["lengths"]), nat.ptr(out["makespan"]), nat.ptr(extra[0]), nat.ptr(extra[1]),
+            nat.ptr(extra[2]), nat.ptr(extra[3]), nat.ptr(ws), ws.numel(), C, N, T, int(iterations), int(neighbourhood))
     out.update(flowtime_before=extra[0], flowtime_after=extra[1], accepted=extra[2], status=extra[3])
     return out
 
@@ -227,25 +239,11 @@ def audit_schedules(obstacle_map, res, wide=False):
     larger one to magat_sim_mapf_audit_wide (csrc/sim_mapf_audit_wide.hip) - the same rule, one workgroup per case.  At most
     4096 agents per case.  Stream ordered, no host synchronisation."""
     paths = res["paths"]
-    if not isinstance(obstacle_map, torch.Tensor) or not obstacle_map.is_cuda or not paths.is_cuda:
-        raise nat.MagatNativeError("obstacle_map and the schedules must be device tensors (no CPU fallback)")
-    m = obstacle_map.to(torch.uint8).contiguous()
-    assert paths.dim() == 4 and paths.shape[3] == 2, "paths must be (C,N,T,2)"
-    C, N, T, _ = paths.shape
-    assert m.dim() in (2, 3) and (m.dim() == 2 or m.shape[0] == C), "obstacle_map must be (H,W) or (C,H,W)"
-    H, W = m.shape[-2], m.shape[-1]
-    to_wide = H > MAX_SIDE or W > MAX_SIDE or T > MAX_HORIZON
-    if to_wide and not wide:
-        raise nat.MagatNativeError("audit_schedules takes maps up to %d x %d and horizons up to %d, not %d x %d / %d "
-                                   "(wide=True takes maps up to %d x %d and horizons up to %d)"
-                                   % (MAX_SIDE, MAX_SIDE, MAX_HORIZON, H, W, T, WIDE_MAX_SIDE, WIDE_MAX_SIDE, WIDE_MAX_HORIZON))
-    if H > WIDE_MAX_SIDE or W > WIDE_MAX_SIDE or T > WIDE_MAX_HORIZON:
-        raise nat.MagatNativeError("audit_schedules(wide=True) takes maps up to %d x %d and horizons up to %d, not %d x %d / %d"
-                                   % (WIDE_MAX_SIDE, WIDE_MAX_SIDE, WIDE_MAX_HORIZON, H, W, T))
-    if N > MAX_AGENTS_AUDIT:
-        raise nat.MagatNativeError("audit_schedules takes at most %d agents per case, not %d" % (MAX_AGENTS_AUDIT, N))
-    paths = _dev_i32(paths, "paths")
-    lengths, start, goal = _dev_i32(res["lengths"], "lengths"), _dev_i32(res["start"], "start"), _dev_i32(res["goal"], "goal")
+    m, batched, C, N, T, H, W = sh.dev_schedules(obstacle_map, paths)
+    _limits("audit_schedules", H, W, T, N, wide=bool(wide), keyword=True)
+    to_wide = _route(H, W, T, wide) == "wide"
+    paths = sh.dev_i32(paths, "paths")
+    lengths, start, goal = sh.dev_i32(res["lengths"], "lengths"), sh.dev_i32(res["start"], "start"), sh.dev_i32(res["goal"], "goal")
     assert tuple(lengths.shape) == (C, N) and tuple(start.shape) == (C, N, 2) and tuple(goal.shape) == (C, N, 2)
     solved = res["solved"].to(torch.uint8).contiguous() if res.get("solved") is not None else None
     assert solved is None or solved.numel() == C
@@ -255,15 +253,11 @@ def audit_schedules(obstacle_map, res, wide=False):
     dist = torch.empty(C, N, dtype=torch.int32, device=dev)
     extra = torch.empty(4, C, dtype=torch.int32, device=dev)
     lib = nat.lib()
-    ws_bytes = (lib.magat_sim_mapf_audit_wide_workspace_bytes(C, H, W, N, T) if to_wide
-                else lib.magat_sim_mapf_audit_workspace_bytes(C, N, T))
-    ws = torch.empty(max(int(ws_bytes), 8), dtype=torch.uint8, device=dev)
-    entry = "magat_sim_mapf_audit_wide" if to_wide else "magat_sim_mapf_audit"
-    with torch.cuda.device(dev):
-        nat.check(getattr(lib, entry)(nat.ptr(m), 1 if m.dim() == 3 else 0, H, W, nat.ptr(solved), nat.ptr(paths), nat.ptr(lengths),
-                                      nat.ptr(start), nat.ptr(goal), nat.ptr(status), nat.ptr(fault), nat.ptr(dist),
-                                      nat.ptr(extra[0]), nat.ptr(extra[1]), nat.ptr(extra[2]), nat.ptr(extra[3]), nat.ptr(ws),
-                                      ws.numel(), C, N, T, nat.current_stream(dev)), entry)
+    ws = sh.scratch(lib.magat_sim_mapf_audit_wide_workspace_bytes(C, H, W, N, T) if to_wide
+                    else lib.magat_sim_mapf_audit_workspace_bytes(C, N, T), dev)
+    sh.call(dev, "magat_sim_mapf_audit_wide" if to_wide else "magat_sim_mapf_audit", nat.ptr(m), batched, H, W, nat.ptr(solved),
+            nat.ptr(paths), nat.ptr(lengths), nat.ptr(start), nat.ptr(goal), nat.ptr(status), nat.ptr(fault), nat.ptr(dist),
+            nat.ptr(extra[0]), nat.ptr(extra[1]), nat.ptr(extra[2]), nat.ptr(extra[3]), nat.ptr(ws), ws.numel(), C, N, T)
     return dict(status=status, fault=fault, dist=dist, flowtime_bound=extra[0], makespan_bound=extra[1], flowtime=extra[2],
                 makespan=extra[3])
 
@@ -290,11 +284,21 @@ def certified_pack(res, audit, w):
     return pack
 
 
-def _cbs_limits(H, W, T, N, max_nodes):
-    if H > MAX_SIDE or W > MAX_SIDE or T > MAX_HORIZON or N > MAX_AGENTS_AUDIT or not 1 <= max_nodes <= MAX_NODES_CBS:
-        raise nat.MagatNativeError("cbs_cases takes maps up to %d x %d, horizons up to %d, %d agents and 1..%d nodes per case, not "
-                                   "%d x %d / %d / %d / %d (it has no wide form)"
-                                   % (MAX_SIDE, MAX_SIDE, MAX_HORIZON, MAX_AGENTS_AUDIT, MAX_NODES_CBS, H, W, T, N, max_nodes))
+def _tree_search(entry, cases, T, ws_args, tail):
+    """One launch of a tree search - `entry`, with its workspace sized by entry_workspace_bytes(*ws_args) - over `cases`
+    (sh.dev_cases' tuple) with horizon T; tail: the entry's integers behind T.  Returns cbs_cases' dict."""
+    m, batched, start, goal, C, N, H, W = cases
+    dev = start.device
+    paths = torch.empty(C, N, T, 2, dtype=torch.int32, device=dev)
+    lengths = torch.empty(C, N, dtype=torch.int32, device=dev)
+    solved = torch.empty(C, dtype=torch.uint8, device=dev)
+    extra = torch.empty(7, C, dtype=torch.int32, device=dev)
+    ws = sh.scratch(getattr(nat.lib(), entry + "_workspace_bytes")(*ws_args), dev)
+    sh.call(dev, entry, nat.ptr(m), batched, H, W, nat.ptr(start), nat.ptr(goal), nat.ptr(paths), nat.ptr(lengths), nat.ptr(extra[0]),
+            nat.ptr(solved), nat.ptr(extra[1]), nat.ptr(extra[2]), nat.ptr(extra[3]), nat.ptr(extra[4]), nat.ptr(extra[5]),
+            nat.ptr(extra[6]), nat.ptr(ws), ws.numel(), C, N, T, *tail)
+    return dict(paths=paths, lengths=lengths, goal=goal, start=start, makespan=extra[0], solved=solved, status=extra[1],
+                flowtime=extra[2], lower_bound=extra[3], nodes=extra[4], expanded=extra[5], horizon_hit=extra[6])
 
 
 def cbs_cases(obstacle_map, start, goal, horizon=None, max_nodes=256):
@@ -317,31 +321,12 @@ def cbs_cases(obstacle_map, start, goal, horizon=None, max_nodes=256):
     No focal search (that is ecbs_cases), and no pruning by an incumbent, disjoint splitting or conflict prioritisation either.
     Limits: H, W <= 64, horizon <= 256, N <= 4096 - anything else raises MagatNativeError; there is no wide form yet.
     Stream ordered, no host synchronisation."""
-    start, goal = _dev_i32(start, "start"), _dev_i32(goal, "goal")
-    if not isinstance(obstacle_map, torch.Tensor) or not obstacle_map.is_cuda:
-        raise nat.MagatNativeError("obstacle_map must be a device tensor (no CPU fallback)")
-    m = obstacle_map.to(torch.uint8).contiguous()
-    assert start.dim() == 3 and start.shape[2] == 2 and goal.shape == start.shape, "start and goal must be (C,N,2)"
-    C, N, _ = start.shape
-    assert m.dim() in (2, 3) and (m.dim() == 2 or m.shape[0] == C), "obstacle_map must be (H,W) or (C,H,W)"
-    H, W = m.shape[-2], m.shape[-1]
+    cases = sh.dev_cases(obstacle_map, start, goal)
+    C, N, H, W = cases[4:]
     T = default_horizon(H, W, N) if horizon is None else int(horizon)
     max_nodes = int(max_nodes)
-    _cbs_limits(H, W, T, N, max_nodes)
-    dev = start.device
-    paths = torch.empty(C, N, T, 2, dtype=torch.int32, device=dev)
-    lengths = torch.empty(C, N, dtype=torch.int32, device=dev)
-    solved = torch.empty(C, dtype=torch.uint8, device=dev)
-    extra = torch.empty(7, C, dtype=torch.int32, device=dev)
-    lib = nat.lib()
-    ws = torch.empty(max(int(lib.magat_sim_mapf_cbs_workspace_bytes(C, N, T, max_nodes)), 8), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        nat.check(lib.magat_sim_mapf_cbs(nat.ptr(m), 1 if m.dim() == 3 else 0, H, W, nat.ptr(start), nat.ptr(goal), nat.ptr(paths),
-                                         nat.ptr(lengths), nat.ptr(extra[0]), nat.ptr(solved), nat.ptr(extra[1]), nat.ptr(extra[2]),
-                                         nat.ptr(extra[3]), nat.ptr(extra[4]), nat.ptr(extra[5]), nat.ptr(extra[6]), nat.ptr(ws),
-                                         ws.numel(), C, N, T, max_nodes, nat.current_stream(dev)), "magat_sim_mapf_cbs")
-    return dict(paths=paths, lengths=lengths, goal=goal, start=start, makespan=extra[0], solved=solved, status=extra[1],
-                flowtime=extra[2], lower_bound=extra[3], nodes=extra[4], expanded=extra[5], horizon_hit=extra[6])
+    _limits("cbs_cases", H, W, T, N, max_nodes)
+    return _tree_search("magat_sim_mapf_cbs", cases, T, (C, N, T, max_nodes), (max_nodes,))
 
 
 def _w_milli(w, who):
@@ -351,15 +336,6 @@ def _w_milli(w, who):
     if w_milli > MAX_W_MILLI_ECBS:
         raise ValueError("%s: w must be at most %g, not %r" % (who, MAX_W_MILLI_ECBS / 1000.0, w))
     return w_milli
-
-
-def _ecbs_limits(H, W, T, N, max_nodes, levels):
-    if (H > MAX_SIDE or W > MAX_SIDE or T > MAX_HORIZON or N > MAX_AGENTS_AUDIT or not 1 <= max_nodes <= MAX_NODES_CBS
-            or not 1 <= levels <= MAX_LEVELS_ECBS):
-        raise nat.MagatNativeError("ecbs_cases takes maps up to %d x %d, horizons up to %d, %d agents, 1..%d nodes per case and 1..%d "
-                                   "levels, not %d x %d / %d / %d / %d / %d (it has no wide form)"
-                                   % (MAX_SIDE, MAX_SIDE, MAX_HORIZON, MAX_AGENTS_AUDIT, MAX_NODES_CBS, MAX_LEVELS_ECBS, H, W, T, N,
-                                      max_nodes, levels))
 
 
 def ecbs_cases(obstacle_map, start, goal, w=1.5, horizon=None, max_nodes=256, levels=4):
@@ -377,41 +353,12 @@ def ecbs_cases(obstacle_map, start, goal, w=1.5, horizon=None, max_nodes=256, le
     Limits: H, W <= 64, horizon <= 256, N <= 4096, max_nodes and levels as above - anything else raises MagatNativeError, a w
     below 1 or above 1048.576 ValueError; the wide form is ecbs_cases_wide.  Stream ordered, no host synchronisation."""
     w_milli = _w_milli(w, "ecbs_cases")
-    start, goal = _dev_i32(start, "start"), _dev_i32(goal, "goal")
-    if not isinstance(obstacle_map, torch.Tensor) or not obstacle_map.is_cuda:
-        raise nat.MagatNativeError("obstacle_map must be a device tensor (no CPU fallback)")
-    m = obstacle_map.to(torch.uint8).contiguous()
-    assert start.dim() == 3 and start.shape[2] == 2 and goal.shape == start.shape, "start and goal must be (C,N,2)"
-    C, N, _ = start.shape
-    assert m.dim() in (2, 3) and (m.dim() == 2 or m.shape[0] == C), "obstacle_map must be (H,W) or (C,H,W)"
-    H, W = m.shape[-2], m.shape[-1]
+    cases = sh.dev_cases(obstacle_map, start, goal)
+    C, N, H, W = cases[4:]
     T = default_horizon(H, W, N) if horizon is None else int(horizon)
     max_nodes, levels = int(max_nodes), int(levels)
-    _ecbs_limits(H, W, T, N, max_nodes, levels)
-    dev = start.device
-    paths = torch.empty(C, N, T, 2, dtype=torch.int32, device=dev)
-    lengths = torch.empty(C, N, dtype=torch.int32, device=dev)
-    solved = torch.empty(C, dtype=torch.uint8, device=dev)
-    extra = torch.empty(7, C, dtype=torch.int32, device=dev)
-    lib = nat.lib()
-    ws = torch.empty(max(int(lib.magat_sim_mapf_ecbs_workspace_bytes(C, N, T, max_nodes, levels)), 8), dtype=torch.uint8, device=dev)
-    with torch.cuda.device(dev):
-        nat.check(lib.magat_sim_mapf_ecbs(nat.ptr(m), 1 if m.dim() == 3 else 0, H, W, nat.ptr(start), nat.ptr(goal), nat.ptr(paths),
-                                          nat.ptr(lengths), nat.ptr(extra[0]), nat.ptr(solved), nat.ptr(extra[1]), nat.ptr(extra[2]),
-                                          nat.ptr(extra[3]), nat.ptr(extra[4]), nat.ptr(extra[5]), nat.ptr(extra[6]), nat.ptr(ws),
-                                          ws.numel(), C, N, T, max_nodes, w_milli, levels, nat.current_stream(dev)),
-                  "magat_sim_mapf_ecbs")
-    return dict(paths=paths, lengths=lengths, goal=goal, start=start, makespan=extra[0], solved=solved, status=extra[1],
-                flowtime=extra[2], lower_bound=extra[3], nodes=extra[4], expanded=extra[5], horizon_hit=extra[6])
-
-
-def _ecbs_wide_limits(H, W, T, N, max_nodes, levels):
-    if (H > WIDE_MAX_SIDE or W > WIDE_MAX_SIDE or T > WIDE_MAX_HORIZON or N > MAX_AGENTS_AUDIT or not 1 <= max_nodes <= MAX_NODES_CBS
-            or not 1 <= levels <= MAX_LEVELS_ECBS):
-        raise nat.MagatNativeError("ecbs_cases_wide takes maps up to %d x %d, horizons up to %d, %d agents, 1..%d nodes per case and "
-                                   "1..%d levels, not %d x %d / %d / %d / %d / %d"
-                                   % (WIDE_MAX_SIDE, WIDE_MAX_SIDE, WIDE_MAX_HORIZON, MAX_AGENTS_AUDIT, MAX_NODES_CBS, MAX_LEVELS_ECBS, H,
-                                      W, T, N, max_nodes, levels))
+    _limits("ecbs_cases", H, W, T, N, max_nodes, levels)
+    return _tree_search("magat_sim_mapf_ecbs", cases, T, (C, N, T, max_nodes, levels), (max_nodes, w_milli, levels))
 
 
 def ecbs_cases_wide(obstacle_map, start, goal, w=1.5, horizon=None, max_nodes=256, levels=4):
@@ -430,35 +377,38 @@ def ecbs_cases_wide(obstacle_map, start, goal, w=1.5, horizon=None, max_nodes=25
     message that names them, a w below 1 or above 1048.576 ValueError, CPU tensors MagatNativeError.
     Stream ordered, no host synchronisation; one launch."""
     w_milli = _w_milli(w, "ecbs_cases_wide")
-    start, goal = _dev_i32(start, "start"), _dev_i32(goal, "goal")
-    if not isinstance(obstacle_map, torch.Tensor) or not obstacle_map.is_cuda:
-        raise nat.MagatNativeError("obstacle_map must be a device tensor (no CPU fallback)")
-    m = obstacle_map.to(torch.uint8).contiguous()
-    assert start.dim() == 3 and start.shape[2] == 2 and goal.shape == start.shape, "start and goal must be (C,N,2)"
-    C, N, _ = start.shape
-    assert m.dim() in (2, 3) and (m.dim() == 2 or m.shape[0] == C), "obstacle_map must be (H,W) or (C,H,W)"
-    H, W = m.shape[-2], m.shape[-1]
+    m, batched, start, goal, C, N, H, W = cases = sh.dev_cases(obstacle_map, start, goal)
     T = default_horizon(H, W, N, wide=True) if horizon is None else int(horizon)
     max_nodes, levels = int(max_nodes), int(levels)
-    _ecbs_wide_limits(H, W, T, N, max_nodes, levels)
-    if H <= MAX_SIDE and W <= MAX_SIDE and T <= MAX_HORIZON:
+    _limits("ecbs_cases_wide", H, W, T, N, max_nodes, levels, wide=True)
+    if _route(H, W, T, True) == "narrow":
         return ecbs_cases(m, start, goal, w=w, horizon=T, max_nodes=max_nodes, levels=levels)
-    dev = start.device
-    paths = torch.empty(C, N, T, 2, dtype=torch.int32, device=dev)
-    lengths = torch.empty(C, N, dtype=torch.int32, device=dev)
-    solved = torch.empty(C, dtype=torch.uint8, device=dev)
-    extra = torch.empty(7, C, dtype=torch.int32, device=dev)
-    lib = nat.lib()
-    ws = torch.empty(max(int(lib.magat_sim_mapf_ecbs_wide_workspace_bytes(C, H, W, N, T, max_nodes, levels)), 8), dtype=torch.uint8,
-                     device=dev)
-    with torch.cuda.device(dev):
-        nat.check(lib.magat_sim_mapf_ecbs_wide(nat.ptr(m), 1 if m.dim() == 3 else 0, H, W, nat.ptr(start), nat.ptr(goal),
-                                               nat.ptr(paths), nat.ptr(lengths), nat.ptr(extra[0]), nat.ptr(solved), nat.ptr(extra[1]),
-                                               nat.ptr(extra[2]), nat.ptr(extra[3]), nat.ptr(extra[4]), nat.ptr(extra[5]),
-                                               nat.ptr(extra[6]), nat.ptr(ws), ws.numel(), C, N, T, max_nodes, w_milli, levels,
-                                               nat.current_stream(dev)), "magat_sim_mapf_ecbs_wide")
-    return dict(paths=paths, lengths=lengths, goal=goal, start=start, makespan=extra[0], solved=solved, status=extra[1],
-                flowtime=extra[2], lower_bound=extra[3], nodes=extra[4], expanded=extra[5], horizon_hit=extra[6])
+    return _tree_search("magat_sim_mapf_ecbs_wide", cases, T, (C, H, W, N, T, max_nodes, levels), (max_nodes, w_milli, levels))
+
+
+# the flag an adoption adds -> (the prefix of its other keys, whether a solved case is replaced only by a smaller flowtime)
+_ADOPTION = {"optimal": ("cbs_", False), "bounded": ("ecbs_", True)}
+
+
+def _adopt(res, sub, flag):
+    """A tree search's schedules put into a result - solve_cases(optimal=) with flag "optimal", solve_cases(bounded=) and
+    adopt_bounded with "bounded".  Where sub["status"] == 0 (and, by the flag's rule, the case in `res` is unsolved or has a larger
+    flowtime) sub's paths, lengths and makespan replace the case's, solved becomes 1 and failed_agent -1 (where `res` has that
+    key).  Returns a new dict with every key of `res` but `T`, plus <prefix>status, <prefix>bound (sub's lower_bound where
+    horizon_hit == 0, else -1), <prefix>nodes and the flag, (C,) bool: status 0.  Tensor ops only."""
+    prefix, only_better = _ADOPTION[flag]
+    done = sub["status"] == 0
+    take = done & ((res["solved"] == 0) | ((res["lengths"] - 1).sum(1) > sub["flowtime"])) if only_better else done
+    out = {key: value for key, value in res.items() if key != "T"}
+    out.update(paths=torch.where(take[:, None, None, None], sub["paths"], res["paths"]),
+               lengths=torch.where(take[:, None], sub["lengths"], res["lengths"]),
+               makespan=torch.where(take, sub["makespan"], res["makespan"]),
+               solved=torch.where(take, torch.ones_like(res["solved"]), res["solved"]))
+    if "failed_agent" in res:
+        out["failed_agent"] = torch.where(take, torch.full_like(res["failed_agent"], -1), res["failed_agent"])
+    bound = torch.where(sub["horizon_hit"] == 0, sub["lower_bound"], torch.full_like(sub["lower_bound"], -1))
+    out.update({prefix + "status": sub["status"], prefix + "bound": bound, prefix + "nodes": sub["nodes"], flag: done})
+    return out
 
 
 def adopt_bounded(res, sub):
@@ -473,18 +423,7 @@ def adopt_bounded(res, sub):
     if tuple(res["paths"].shape) != tuple(sub["paths"].shape):
         raise ValueError("adopt_bounded: res and sub must hold the same cases with the same horizon, not paths of %s and %s"
                          % (tuple(res["paths"].shape), tuple(sub["paths"].shape)))
-    done = sub["status"] == 0
-    take = done & ((res["solved"] == 0) | ((res["lengths"] - 1).sum(1) > sub["flowtime"]))
-    out = {key: value for key, value in res.items() if key != "T"}
-    out.update(paths=torch.where(take[:, None, None, None], sub["paths"], res["paths"]),
-               lengths=torch.where(take[:, None], sub["lengths"], res["lengths"]),
-               makespan=torch.where(take, sub["makespan"], res["makespan"]),
-               solved=torch.where(take, torch.ones_like(res["solved"]), res["solved"]))
-    if "failed_agent" in res:
-        out["failed_agent"] = torch.where(take, torch.full_like(res["failed_agent"], -1), res["failed_agent"])
-    bound = torch.where(sub["horizon_hit"] == 0, sub["lower_bound"], torch.full_like(sub["lower_bound"], -1))
-    out.update(ecbs_status=sub["status"], ecbs_bound=bound, ecbs_nodes=sub["nodes"], bounded=done)
-    return out
+    return _adopt(res, sub, "bounded")
 
 
 def solve_cases(obstacle_map, start, goal, horizon=None, retries=8, wide=False, improve=0, optimal=None, bounded=None, bounded_nodes=256,
@@ -526,16 +465,17 @@ def solve_cases(obstacle_map, start, goal, horizon=None, retries=8, wide=False, 
     One host synchronisation per round (the read of `solved`), one more for T."""
     if certify is not None and not float(certify) >= 1.0:
         raise ValueError("solve_cases: certify must be at least 1, not %r" % (certify,))
+    search = None      # the search behind the plan, as _limits takes it: (who, max_nodes, levels)
     if bounded is not None:
         if optimal is not None:
             raise ValueError("solve_cases: bounded and optimal exclude each other")
         _w_milli(bounded, "solve_cases(bounded=)")
-        if isinstance(obstacle_map, torch.Tensor) and obstacle_map.dim() >= 2 and getattr(start, "ndim", 0) == 3:
-            H, W, N = obstacle_map.shape[-2], obstacle_map.shape[-1], start.shape[1]      # refused before anything is planned
-            _ecbs_limits(H, W, default_horizon(H, W, N, wide) if horizon is None else int(horizon), N, int(bounded_nodes), MAX_LEVELS_ECBS)
-    if optimal is not None and isinstance(obstacle_map, torch.Tensor) and obstacle_map.dim() >= 2 and getattr(start, "ndim", 0) == 3:
+        search = ("ecbs_cases", int(bounded_nodes), MAX_LEVELS_ECBS)
+    elif optimal is not None:
+        search = ("cbs_cases", int(optimal), None)
+    if search is not None and isinstance(obstacle_map, torch.Tensor) and obstacle_map.dim() >= 2 and getattr(start, "ndim", 0) == 3:
         H, W, N = obstacle_map.shape[-2], obstacle_map.shape[-1], start.shape[1]      # refused before anything is planned
-        _cbs_limits(H, W, default_horizon(H, W, N, wide) if horizon is None else int(horizon), N, int(optimal))
+        _limits(search[0], H, W, default_horizon(H, W, N, wide) if horizon is None else int(horizon), N, *search[1:])
     res = plan_prioritized(obstacle_map, start, goal, None, horizon, wide)
     C, N, _ = res["start"].shape
     dev = res["start"].device
@@ -558,26 +498,12 @@ def solve_cases(obstacle_map, start, goal, horizon=None, retries=8, wide=False, 
         res = improve_schedules(obstacle_map, res, iterations=int(improve), wide=wide)
     cbs_bound = None
     if optimal is not None:
-        opt = cbs_cases(obstacle_map, res["start"], res["goal"], horizon=T, max_nodes=int(optimal))
-        done = opt["status"] == 0
-        res = dict(res, paths=torch.where(done[:, None, None, None], opt["paths"], res["paths"]),
-                   lengths=torch.where(done[:, None], opt["lengths"], res["lengths"]),
-                   makespan=torch.where(done, opt["makespan"], res["makespan"]),
-                   solved=torch.where(done, torch.ones_like(res["solved"]), res["solved"]),
-                   failed_agent=torch.where(done, torch.full_like(res["failed_agent"], -1), res["failed_agent"]))
-        cbs_bound = torch.where(opt["horizon_hit"] == 0, opt["lower_bound"], torch.full_like(opt["lower_bound"], -1))
-        res.update(cbs_status=opt["status"], cbs_bound=cbs_bound, cbs_nodes=opt["nodes"], optimal=done)
+        res = _adopt(res, cbs_cases(obstacle_map, res["start"], res["goal"], horizon=T, max_nodes=int(optimal)), "optimal")
+        cbs_bound = res["cbs_bound"]
     if bounded is not None:
-        sub = ecbs_cases(obstacle_map, res["start"], res["goal"], w=bounded, horizon=T, max_nodes=int(bounded_nodes))
-        done = sub["status"] == 0
-        take = done & ((res["solved"] == 0) | ((res["lengths"] - 1).sum(1) > sub["flowtime"]))
-        res = dict(res, paths=torch.where(take[:, None, None, None], sub["paths"], res["paths"]),
-                   lengths=torch.where(take[:, None], sub["lengths"], res["lengths"]),
-                   makespan=torch.where(take, sub["makespan"], res["makespan"]),
-                   solved=torch.where(take, torch.ones_like(res["solved"]), res["solved"]),
-                   failed_agent=torch.where(take, torch.full_like(res["failed_agent"], -1), res["failed_agent"]))
-        cbs_bound = torch.where(sub["horizon_hit"] == 0, sub["lower_bound"], torch.full_like(sub["lower_bound"], -1))
-        res.update(ecbs_status=sub["status"], ecbs_bound=cbs_bound, ecbs_nodes=sub["nodes"], bounded=done)
+        res = _adopt(res, ecbs_cases(obstacle_map, res["start"], res["goal"], w=bounded, horizon=T, max_nodes=int(bounded_nodes)),
+                     "bounded")
+        cbs_bound = res["ecbs_bound"]
     if certify is not None:
         audit = audit_schedules(obstacle_map, res, wide=wide)
         if cbs_bound is not None:

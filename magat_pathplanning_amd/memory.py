@@ -23,19 +23,14 @@ HIP only: CPU tensors raise MagatNativeError.  minibatch never waits for the dev
 import torch
 
 from . import _native as nat
+from . import _sim_host as sh
 from . import mapf
 from .expert import MAX_AGENT_STEPS, bad_move_message, expert_radius, expert_schedule
-from .simulator import GUIDANCE_MODES, _dev_i32, batched_fov_states, batched_gso, replayed_semi_states
+from .simulator import GUIDANCE_MODES, batched_fov_states, batched_gso, replayed_semi_states
 
 MAX_SIDE = 256               # a stored cell is row << 8 | col
 NO_ROW = 0x7fffffff          # the error flag's value while every index has been in range
 PICK_KEYS = ("case", "step", "pos", "target", "action", "goal", "radii", "map")      # the outputs of the pick launch
-
-
-def _device_tensor(t, name):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise nat.MagatNativeError("%s must be a device tensor (no CPU fallback)" % name)
-    return t
 
 
 class ExpertMemory:
@@ -69,7 +64,7 @@ class ExpertMemory:
         if dev.type != "cuda":
             raise nat.MagatNativeError("ExpertMemory lives on the device (no CPU fallback), not on %s" % (dev,))
         if shared_map is not None:
-            _device_tensor(shared_map, "shared_map")
+            sh.dev_tensor(shared_map, "shared_map")
             if tuple(shared_map.shape) != (H, W):
                 raise ValueError("shared_map must be (%d, %d), not %s" % (H, W, tuple(shared_map.shape)))
             dev = shared_map.device
@@ -106,12 +101,10 @@ class ExpertMemory:
         are packed from `lengths`, not from the padding, so appends with different Lmax leave the state one append of their
         concatenation leaves.  Reads back once (twice when T is None); not for the hot path.  Returns the number of samples
         added."""
-        for t, name in ((paths, "paths"), (lengths, "lengths"), (goal, "goal"), (makespan, "makespan")):
-            _device_tensor(t, name)
+        paths, lengths = sh.dev_i32(paths, "paths"), sh.dev_i32(lengths, "lengths")
+        goal, makespan = sh.dev_i32(goal, "goal"), sh.dev_i32(makespan, "makespan").reshape(-1)
         if obstacle_map is not None:
-            _device_tensor(obstacle_map, "obstacle_map")
-        paths, lengths = _dev_i32(paths, "paths"), _dev_i32(lengths, "lengths")
-        goal, makespan = _dev_i32(goal, "goal"), _dev_i32(makespan, "makespan").reshape(-1)
+            sh.dev_tensor(obstacle_map, "obstacle_map")
         N, H, W, cap = self.N, self.H, self.W, self.max_length
         if paths.dim() != 4 or paths.shape[3] != 2 or paths.shape[1] != N or paths.shape[2] < 1:
             raise nat.MagatNativeError("ExpertMemory.append: paths must be (C,%d,Lmax,2), not %s" % (N, tuple(paths.shape)))
@@ -217,7 +210,7 @@ class ExpertMemory:
                 raise ValueError("ExpertMemory.minibatch: give M or indices")
             indices = torch.randint(self._samples, (int(M),), generator=generator, device=dev)
         else:
-            _device_tensor(indices, "indices")
+            sh.dev_tensor(indices, "indices")
             if indices.dtype != torch.int64 or indices.dim() != 1 or not indices.is_contiguous() or indices.numel() == 0:
                 raise nat.MagatNativeError("indices must be a contiguous, non-empty (M,) int64 device tensor")
             if M is not None and int(M) != indices.numel():
@@ -239,12 +232,10 @@ class ExpertMemory:
                     raise ValueError("ExpertMemory.minibatch: out[%r] must be a contiguous %s device tensor of shape %s (a dict of "
                                      "an earlier call with the same M)" % (key, dtype, shape))
                 b[key] = t
-        with torch.cuda.device(dev):
-            nat.check(nat.lib().magat_sim_expert_pick(
-                nat.ptr(self._cells), nat.ptr(self.lengths), nat.ptr(self.goal), nat.ptr(self.makespan), nat.ptr(self.radii),
-                nat.ptr(self.cum), nat.ptr(self.maps), nat.ptr(indices), nat.ptr(b["case"]), nat.ptr(b["step"]), nat.ptr(b["pos"]),
-                nat.ptr(b["target"]), nat.ptr(b["action"]), nat.ptr(b["goal"]), nat.ptr(b["radii"]), nat.ptr(b.get("map")),
-                nat.ptr(self.flag), self.cases, N, self.max_length, H, W, M, nat.current_stream(dev)), "magat_sim_expert_pick")
+        sh.call(dev, "magat_sim_expert_pick", nat.ptr(self._cells), nat.ptr(self.lengths), nat.ptr(self.goal), nat.ptr(self.makespan),
+                nat.ptr(self.radii), nat.ptr(self.cum), nat.ptr(self.maps), nat.ptr(indices), nat.ptr(b["case"]), nat.ptr(b["step"]),
+                nat.ptr(b["pos"]), nat.ptr(b["target"]), nat.ptr(b["action"]), nat.ptr(b["goal"]), nat.ptr(b["radii"]),
+                nat.ptr(b.get("map")), nat.ptr(self.flag), self.cases, N, self.max_length, H, W, M)
         if self.maps is None:
             b["map"] = self.shared_map
         if self.replay:

@@ -15,8 +15,8 @@ import numpy as np
 import torch
 
 from . import _native as nat
-from .simulator import (GUIDANCE_MODES, POLICIES, _dev_i32, _Workspace, batched_fov_states, batched_gso, move_needs_wide,
-                        new_agent_view)
+from . import _sim_host as sh
+from .simulator import GUIDANCE_MODES, POLICIES, batched_fov_states, batched_gso, move_needs_wide, new_agent_view
 
 RADIUS_MAX_STEPS = 64           # batched_connect_radius' growth limit
 
@@ -62,17 +62,8 @@ class EpisodePool:
             raise ValueError("slots must be in 1 .. %d (the number of cases), got %d" % (start.shape[0], int(slots)))
         if not isinstance(maxstep, torch.Tensor) and int(maxstep) < 1:
             raise ValueError("every maxstep must be >= 1, got %d" % int(maxstep))
-        self.q_start, self.q_goal = _dev_i32(start, "start"), _dev_i32(goal, "goal")
-        if not isinstance(obstacle_map, torch.Tensor) or not obstacle_map.is_cuda:
-            raise nat.MagatNativeError("obstacle_map must be a device tensor (no CPU fallback)")
-        self.q_map = obstacle_map.to(torch.uint8).contiguous()
-        assert self.q_start.dim() == 3 and self.q_start.shape[2] == 2 and self.q_goal.shape == self.q_start.shape, \
-            "start and goal must be (C,N,2)"
-        C, N, _ = self.q_start.shape
+        self.q_map, batched, self.q_start, self.q_goal, C, N, H, W = sh.dev_cases(obstacle_map, start, goal)
         dev = self.q_start.device
-        batched = self.q_map.dim() == 3
-        assert self.q_map.dim() in (2, 3) and (not batched or self.q_map.shape[0] == C), "obstacle_map must be (H,W) or (C,H,W)"
-        H, W = self.q_map.shape[-2], self.q_map.shape[-1]
         B = int(slots)
         if not 1 <= B <= C:
             raise ValueError("slots must be in 1 .. %d (the number of cases), got %d" % (C, B))
@@ -97,7 +88,7 @@ class EpisodePool:
         self.policy = POLICIES[action_select]
         self.comm_radius, self.symmetric_norm, self.FOV = float(comm_radius), bool(symmetric_norm), int(FOV)
         self.guidance, self.wide, self.seed = guidance, bool(wide), int(seed) & 0xFFFFFFFFFFFFFFFF
-        self._guide_ws = _Workspace()
+        self._guide_ws = sh._Workspace()
         i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)      # noqa: E731
         self.pos, self.goal = i32(B, N, 2), i32(B, N, 2)
         self.map = torch.zeros(B, H, W, dtype=torch.uint8, device=dev) if batched else self.q_map
@@ -120,13 +111,10 @@ class EpisodePool:
         self._traj_len = i32(C) if record else None
         self._uniforms = torch.zeros(B, N, dtype=torch.float64, device=dev)
         self._to_wide = self.wide and move_needs_wide(H, W, N)
-        self._move_ws = None
-        if self._to_wide:
-            self._move_ws = torch.empty(max(int(nat.lib().magat_sim_move_wide_workspace_bytes(B, H, W, N)), 8), dtype=torch.uint8,
-                                        device=dev)
+        self._move_ws = sh.scratch(nat.lib().magat_sim_move_wide_workspace_bytes(B, H, W, N), dev) if self._to_wide else None
         d = nat.SimPoolDesc()
         d.q_map, d.q_start, d.q_goal, d.q_maxstep = (t.data_ptr() for t in (self.q_map, self.q_start, self.q_goal, self.q_maxstep))
-        d.map_batched, d.H, d.W, d.C, d.B, d.N = 1 if batched else 0, H, W, C, B, N
+        d.map_batched, d.H, d.W, d.C, d.B, d.N = batched, H, W, C, B, N
         d.first_step, d.record, d.traj_cells, d.radius_max_steps = self.first_step, 1 if record else 0, self.traj_cells, RADIUS_MAX_STEPS
         d.comm_radius = self.comm_radius
         d.slot_case, d.slot_step, d.slot_maxstep = self.slot_case.data_ptr(), self.slot_step.data_ptr(), self.slot_maxstep.data_ptr()
@@ -150,8 +138,7 @@ class EpisodePool:
         s.actions_out, s.moves_out, s.flags_out = self.actions.data_ptr(), self.moves.data_ptr(), self.flags.data_ptr()
         s.done_out, s.flowtime_out, s.makespan_out = d.done, d.flowtime, d.makespan
         self._step_desc = s
-        with torch.cuda.device(dev):      # the first fill: every slot takes a case, radii included
-            nat.check(nat.lib().magat_sim_pool_turn(ctypes.byref(d), 1, nat.current_stream(dev)), "magat_sim_pool_turn")
+        sh.call(dev, "magat_sim_pool_turn", ctypes.byref(d), 1)      # the first fill: every slot takes a case, radii included
 
     def gso(self, dtype=torch.float64):
         """getGSO for every slot, with the radius its case grew to at the refill."""
@@ -164,32 +151,19 @@ class EpisodePool:
     def step(self, logits=None, actions=None, uniforms=None):
         """move() for every slot that holds a case, then the turn: result rows and refills.  Returns nothing."""
         B, N, dev = self.B, self.N, self.dev
-        assert (logits is None) != (actions is None), "give logits or actions"
-        lg = None if logits is None else logits.reshape(B * N, 5).contiguous().float()
-        ac = None if actions is None else _dev_i32(actions, "actions").reshape(B * N)
+        lg, ac = sh.dev_actions(logits, actions, B, N)
         policy = self.policy if lg is not None else 0
-        lib = nat.lib()
-        with torch.cuda.device(dev):
-            st = nat.current_stream(dev)
-            if policy and uniforms is None:
-                uniforms = self._uniforms
-                nat.check(lib.magat_sim_pool_uniforms(nat.ptr(self.slot_case), nat.ptr(self.slot_step), nat.ptr(uniforms),
-                                                      self.seed, B, N, st), "magat_sim_pool_uniforms")
-            if uniforms is not None:
-                if not uniforms.is_cuda or uniforms.dtype != torch.float64 or uniforms.numel() != B * N:
-                    raise nat.MagatNativeError("uniforms must be a (B,N) float64 device tensor")
-                uniforms = uniforms.contiguous()
-            s = self._step_desc
-            s.logits, s.actions_in = nat.ptr(lg), nat.ptr(ac)
-            s.policy, s.uniforms = policy, nat.ptr(uniforms)
-            slots = (nat.ptr(self.slot_case), nat.ptr(self.slot_step), nat.ptr(self.slot_maxstep), nat.ptr(self.over),
-                     nat.ptr(self.sticky))
-            if self._to_wide:
-                nat.check(lib.magat_sim_pool_step_wide(ctypes.byref(s), *slots, nat.ptr(self._move_ws), self._move_ws.numel(), st),
-                          "magat_sim_pool_step_wide")
-            else:
-                nat.check(lib.magat_sim_pool_step(ctypes.byref(s), *slots, st), "magat_sim_pool_step")
-            nat.check(lib.magat_sim_pool_turn(ctypes.byref(self._desc), 0, st), "magat_sim_pool_turn")
+        if policy and uniforms is None:
+            uniforms = self._uniforms
+            sh.call(dev, "magat_sim_pool_uniforms", nat.ptr(self.slot_case), nat.ptr(self.slot_step), nat.ptr(uniforms), self.seed, B, N)
+        if uniforms is not None:
+            uniforms = sh.dev_uniforms(uniforms, B, N)
+        s = self._step_desc
+        s.logits, s.actions_in = nat.ptr(lg), nat.ptr(ac)
+        s.policy, s.uniforms = policy, nat.ptr(uniforms)
+        sh.call(dev, "magat_sim_pool_step", ctypes.byref(s), nat.ptr(self.slot_case), nat.ptr(self.slot_step), nat.ptr(self.slot_maxstep),
+                nat.ptr(self.over), nat.ptr(self.sticky), ws=self._move_ws)
+        sh.call(dev, "magat_sim_pool_turn", ctypes.byref(self._desc), 0)
 
     def finished(self):
         """True once every case is retired (reads one word back: synchronises)."""

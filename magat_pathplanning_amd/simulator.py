@@ -22,14 +22,8 @@ import ctypes
 import torch
 
 from . import _native as nat
-
-
-def _dev_i32(t, name):
-    if not isinstance(t, torch.Tensor) or not t.is_cuda:
-        raise nat.MagatNativeError("%s must be a device tensor (no CPU fallback)" % name)
-    if t.dtype != torch.int32:
-        t = t.to(torch.int32)
-    return t.contiguous()
+from . import _sim_host as sh
+from ._sim_host import _Workspace, dev_i32 as _dev_i32      # noqa: F401  (the names other modules and tools import from here)
 
 
 def batched_connect_radius(pos, comm_radius, max_steps=64, return_steps=False):
@@ -41,10 +35,8 @@ def batched_connect_radius(pos, comm_radius, max_steps=64, return_steps=False):
     B, N, _ = pos.shape
     radii = torch.empty(B, dtype=torch.float64, device=pos.device)
     steps = torch.empty(B, dtype=torch.int32, device=pos.device)
-    with torch.cuda.device(pos.device):
-        nat.check(nat.lib().magat_sim_connect_radius(nat.ptr(pos), float(comm_radius), nat.ptr(radii), nat.ptr(steps), B, N,
-                                                     int(max_steps), nat.current_stream(pos.device)),
-                  "magat_sim_connect_radius")
+    sh.call(pos.device, "magat_sim_connect_radius", nat.ptr(pos), float(comm_radius), nat.ptr(radii), nat.ptr(steps), B, N,
+            int(max_steps))
     return (radii, steps) if return_steps else radii
 
 
@@ -63,19 +55,14 @@ def batched_gso(pos, comm_radius, symmetric_norm=False, normalize=True, dtype=to
         radii = comm_radius.contiguous()
         S = torch.empty(B, N, N, dtype=dtype, device=pos.device)
         lam = torch.empty(B, dtype=torch.float64, device=pos.device)
-        with torch.cuda.device(pos.device):
-            nat.check(nat.lib().magat_sim_gso_radii(nat.ptr(pos), nat.ptr(radii), 1 if symmetric_norm else 0,
-                                                    1 if normalize else 0, nat.ptr(S), int(dtype == torch.float64),
-                                                    nat.ptr(lam), B, N, nat.current_stream(pos.device)),
-                      "magat_sim_gso_radii")
+        sh.call(pos.device, "magat_sim_gso_radii", nat.ptr(pos), nat.ptr(radii), 1 if symmetric_norm else 0, 1 if normalize else 0,
+                nat.ptr(S), int(dtype == torch.float64), nat.ptr(lam), B, N)
         return (S, lam) if return_lambda else S
     B, N, _ = pos.shape
     S = torch.empty(B, N, N, dtype=dtype, device=pos.device)
     lam = torch.empty(B, dtype=torch.float64, device=pos.device)
-    with torch.cuda.device(pos.device):
-        nat.check(nat.lib().magat_sim_gso(nat.ptr(pos), float(comm_radius), 1 if symmetric_norm else 0,
-                                          1 if normalize else 0, nat.ptr(S), int(dtype == torch.float64), nat.ptr(lam),
-                                          B, N, nat.current_stream(pos.device)), "magat_sim_gso")
+    sh.call(pos.device, "magat_sim_gso", nat.ptr(pos), float(comm_radius), 1 if symmetric_norm else 0, 1 if normalize else 0,
+            nat.ptr(S), int(dtype == torch.float64), nat.ptr(lam), B, N)
     return (S, lam) if return_lambda else S
 
 
@@ -97,19 +84,14 @@ GUIDE_CANVAS = 64               # csrc/sim_guidance.hip: the narrow form's searc
 MOVE_LDS_BYTES = 160 * 1024     # csrc/sim_frontend.hip: the narrow move step keeps 4 H W + 16 N bytes in LDS
 
 
-class _Workspace:
-    """A cached device buffer for the wide kernels: reallocated only when a call needs more than it holds."""
-
-    def __init__(self):
-        self.buf = None
-
-    def get(self, nbytes, device):
-        if self.buf is None or self.buf.device != device or self.buf.numel() < nbytes:
-            self.buf = torch.empty(max(int(nbytes), 8), dtype=torch.uint8, device=device)
-        return self.buf
-
-
 _guide_workspaces = {}          # device -> _Workspace, for batched_fov_states calls that bring none
+
+
+def _guide_workspace(workspace, B, N, H, W, FOV, device):
+    """The open lists of magat_sim_guided_states_wide / magat_sim_replayed_states_wide: in `workspace`, or in the device's own"""
+    if workspace is None:
+        workspace = _guide_workspaces.setdefault(device, _Workspace())
+    return workspace.get(nat.lib().magat_sim_guided_states_wide_workspace_bytes(B, N, H, W, FOV), device)
 
 
 def guided_needs_wide(H, W, FOV):
@@ -150,14 +132,9 @@ def batched_fov_states(obstacle_map, pos, goal, FOV=9, guidance="Project_G", age
     if guidance not in GUIDANCE_MODES:
         raise ValueError("guidance must be one of %s, got %r" % (sorted(GUIDANCE_MODES), guidance))
     pos, goal = _dev_i32(pos, "pos"), _dev_i32(goal, "goal")
-    if not isinstance(obstacle_map, torch.Tensor) or not obstacle_map.is_cuda:
-        raise nat.MagatNativeError("obstacle_map must be a device tensor (no CPU fallback)")
-    m = obstacle_map.to(torch.uint8).contiguous()
     B, N, _ = pos.shape
     assert goal.shape == pos.shape
-    batched = m.dim() == 3
-    assert m.dim() in (2, 3) and (not batched or m.shape[0] == B)
-    H, W = m.shape[-2], m.shape[-1]
+    m, batched, H, W = sh.dev_map(obstacle_map, B)
     guided = GUIDANCE_MODES[guidance]
     if guided is not None and guided[0] == nat.GUIDE_SEMI:
         half = int(FOV) // 2
@@ -168,26 +145,14 @@ def batched_fov_states(obstacle_map, pos, goal, FOV=9, guidance="Project_G", age
             raise nat.MagatNativeError("agent_view must be a contiguous uint8 device tensor of shape %s (it is updated in "
                                        "place)" % ((B, N, H + 2 * half, W + 2 * half),))
     x = torch.empty(B, N, 3, FOV + 2, FOV + 2, dtype=torch.float32, device=pos.device)
-    with torch.cuda.device(pos.device):
-        if guided is None:
-            nat.check(nat.lib().magat_sim_fov_states(nat.ptr(m), 1 if batched else 0, H, W, nat.ptr(pos), nat.ptr(goal),
-                                                     nat.ptr(x), FOV, B, N, nat.current_stream(pos.device)),
-                      "magat_sim_fov_states")
-        elif wide and guided[0] != nat.GUIDE_LOCAL and guided_needs_wide(H, W, FOV):
-            lib = nat.lib()
-            if workspace is None:
-                workspace = _guide_workspaces.setdefault(pos.device, _Workspace())
-            ws = workspace.get(lib.magat_sim_guided_states_wide_workspace_bytes(B, N, H, W, FOV), pos.device)
-            nat.check(lib.magat_sim_guided_states_wide(nat.ptr(m), 1 if batched else 0, H, W, nat.ptr(pos), nat.ptr(goal),
-                                                       nat.ptr(x), FOV, B, N, guided[0], guided[1],
-                                                       nat.ptr(agent_view) if guided[0] == nat.GUIDE_SEMI else None,
-                                                       nat.ptr(ws), ws.numel(), nat.current_stream(pos.device)),
-                      "magat_sim_guided_states_wide")
-        else:
-            nat.check(nat.lib().magat_sim_guided_states(nat.ptr(m), 1 if batched else 0, H, W, nat.ptr(pos), nat.ptr(goal),
-                                                        nat.ptr(x), FOV, B, N, guided[0], guided[1],
-                                                        nat.ptr(agent_view) if guided[0] == nat.GUIDE_SEMI else None,
-                                                        nat.current_stream(pos.device)), "magat_sim_guided_states")
+    if guided is None:
+        sh.call(pos.device, "magat_sim_fov_states", nat.ptr(m), batched, H, W, nat.ptr(pos), nat.ptr(goal), nat.ptr(x), FOV, B, N)
+        return x
+    ws = None
+    if wide and guided[0] != nat.GUIDE_LOCAL and guided_needs_wide(H, W, FOV):
+        ws = _guide_workspace(workspace, B, N, H, W, FOV, pos.device)
+    sh.call(pos.device, "magat_sim_guided_states", nat.ptr(m), batched, H, W, nat.ptr(pos), nat.ptr(goal), nat.ptr(x), FOV, B, N,
+            guided[0], guided[1], nat.ptr(agent_view) if guided[0] == nat.GUIDE_SEMI else None, ws=ws)
     return x
 
 
@@ -207,14 +172,9 @@ def replayed_semi_states(obstacle_map, pos, goal, history, FOV=9, guidance="Semi
     if guidance not in GUIDANCE_MODES or GUIDANCE_MODES[guidance] is None or GUIDANCE_MODES[guidance][0] != nat.GUIDE_SEMI:
         raise ValueError("replayed_semi_states: guidance must be 'SemiLG_S' or 'SemiLG_SD', got %r" % (guidance,))
     pos, goal = _dev_i32(pos, "pos"), _dev_i32(goal, "goal")
-    if not isinstance(obstacle_map, torch.Tensor) or not obstacle_map.is_cuda:
-        raise nat.MagatNativeError("obstacle_map must be a device tensor (no CPU fallback)")
-    m = obstacle_map.to(torch.uint8).contiguous()
     B, N, _ = pos.shape
     assert goal.shape == pos.shape
-    batched = m.dim() == 3
-    assert m.dim() in (2, 3) and (not batched or m.shape[0] == B)
-    H, W = m.shape[-2], m.shape[-1]
+    m, batched, H, W = sh.dev_map(obstacle_map, B)
     keys = set(history)
     if not {"case", "step"} <= keys or ("table" in keys) == bool(keys & {"cells", "lengths", "goal"}):
         raise ValueError("replayed_semi_states: history holds case, step and either table or cells, lengths, goal - not %s"
@@ -243,19 +203,9 @@ def replayed_semi_states(obstacle_map, pos, goal, history, FOV=9, guidance="Semi
         d.cells, d.lengths, d.goal = cells.data_ptr(), lengths.data_ptr(), hgoal.data_ptr()
         d.cases, d.Lcap = cases, cells.shape[2]
     x = torch.empty(B, N, 3, FOV + 2, FOV + 2, dtype=torch.float32, device=pos.device)
-    with torch.cuda.device(pos.device):
-        lib = nat.lib()
-        if wide and guided_needs_wide(H, W, FOV):
-            if workspace is None:
-                workspace = _guide_workspaces.setdefault(pos.device, _Workspace())
-            ws = workspace.get(lib.magat_sim_guided_states_wide_workspace_bytes(B, N, H, W, FOV), pos.device)
-            nat.check(lib.magat_sim_replayed_states_wide(nat.ptr(m), 1 if batched else 0, H, W, nat.ptr(pos), nat.ptr(goal),
-                                                         nat.ptr(x), FOV, B, N, ctypes.byref(d), nat.ptr(ws), ws.numel(),
-                                                         nat.current_stream(pos.device)), "magat_sim_replayed_states_wide")
-        else:
-            nat.check(lib.magat_sim_replayed_states(nat.ptr(m), 1 if batched else 0, H, W, nat.ptr(pos), nat.ptr(goal), nat.ptr(x),
-                                                    FOV, B, N, ctypes.byref(d), nat.current_stream(pos.device)),
-                      "magat_sim_replayed_states")
+    ws = _guide_workspace(workspace, B, N, H, W, FOV, pos.device) if wide and guided_needs_wide(H, W, FOV) else None
+    sh.call(pos.device, "magat_sim_replayed_states", nat.ptr(m), batched, H, W, nat.ptr(pos), nat.ptr(goal), nat.ptr(x), FOV, B, N,
+            ctypes.byref(d), ws=ws)
     return x
 
 
@@ -267,34 +217,23 @@ def batched_move(obstacle_map, pos, logits=None, actions=None, goal=None, wide=F
     The cell grid lives in LDS, 4 H W + 16 N bytes <= 160 KB (about 200 x 200); wide=True takes maps up to 256 x 256 with up to
     4096 agents: a shape inside the LDS limit keeps its kernel, a larger one goes to magat_sim_move_wide, the same rules with the
     grid in a device workspace of 4 B H W bytes (`workspace`, a _Workspace the caller keeps, or a fresh buffer)."""
+    m = sh.dev_u8(obstacle_map, "obstacle_map")
     if pos.dtype != torch.int32 or not pos.is_cuda or not pos.is_contiguous():
         raise nat.MagatNativeError("pos must be a contiguous int32 device tensor (it is updated in place)")
-    assert (logits is None) != (actions is None), "give logits or actions"
     B, N, _ = pos.shape
     dev = pos.device
-    m = obstacle_map.to(torch.uint8).contiguous()
-    if not m.is_cuda:
-        raise nat.MagatNativeError("obstacle_map must be a device tensor (no CPU fallback)")
-    batched = m.dim() == 3
     H, W = m.shape[-2], m.shape[-1]
-    lg = None if logits is None else logits.reshape(B * N, 5).contiguous().float()
-    ac = None if actions is None else _dev_i32(actions, "actions").reshape(B * N)
+    lg, ac = sh.dev_actions(logits, actions, B, N)
     gl = None if goal is None else _dev_i32(goal, "goal")
     a_out = torch.empty(B, N, dtype=torch.int32, device=dev)
     mv = torch.empty(B, N, 2, dtype=torch.int8, device=dev)
     reached = torch.empty(B, N, dtype=torch.uint8, device=dev) if gl is not None else None
     flags = torch.empty(B, dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        if wide and move_needs_wide(H, W, N):
-            lib = nat.lib()
-            ws = (workspace or _Workspace()).get(lib.magat_sim_move_wide_workspace_bytes(B, H, W, N), dev)
-            nat.check(lib.magat_sim_move_wide(nat.ptr(lg), nat.ptr(ac), nat.ptr(m), 1 if batched else 0, H, W, nat.ptr(pos),
-                                              nat.ptr(gl), nat.ptr(a_out), nat.ptr(mv), nat.ptr(reached), nat.ptr(flags), B, N,
-                                              nat.ptr(ws), ws.numel(), nat.current_stream(dev)), "magat_sim_move_wide")
-        else:
-            nat.check(nat.lib().magat_sim_move(nat.ptr(lg), nat.ptr(ac), nat.ptr(m), 1 if batched else 0, H, W, nat.ptr(pos),
-                                               nat.ptr(gl), nat.ptr(a_out), nat.ptr(mv), nat.ptr(reached), nat.ptr(flags), B, N,
-                                               nat.current_stream(dev)), "magat_sim_move")
+    ws = None
+    if wide and move_needs_wide(H, W, N):
+        ws = (workspace or _Workspace()).get(nat.lib().magat_sim_move_wide_workspace_bytes(B, H, W, N), dev)
+    sh.call(dev, "magat_sim_move", nat.ptr(lg), nat.ptr(ac), nat.ptr(m), 1 if m.dim() == 3 else 0, H, W, nat.ptr(pos), nat.ptr(gl),
+            nat.ptr(a_out), nat.ptr(mv), nat.ptr(reached), nat.ptr(flags), B, N, ws=ws)
     return dict(actions=a_out, moves=mv, reached=None if reached is None else reached.bool(), flags=flags)
 
 
@@ -322,9 +261,7 @@ class BatchedEpisode:
             raise ValueError("guidance must be one of %s, got %r" % (sorted(GUIDANCE_MODES), guidance))
         self.pos = _dev_i32(pos, "pos").clone()
         self.goal = _dev_i32(goal, "goal")
-        if not isinstance(obstacle_map, torch.Tensor) or not obstacle_map.is_cuda:
-            raise nat.MagatNativeError("obstacle_map must be a device tensor (no CPU fallback)")
-        self.map = obstacle_map.to(torch.uint8).contiguous()
+        self.map = sh.dev_u8(obstacle_map, "obstacle_map")
         B, N, _ = self.pos.shape
         dev = self.pos.device
         self.B, self.N, self.dev = B, N, dev
@@ -373,16 +310,12 @@ class BatchedEpisode:
         """move(actionVec, currentstep) for every instance; returns `done` (B,) int32 = allReachGoal as the reference
         returns it (evaluated before the move).  No host synchronisation."""
         B, N, dev = self.B, self.N, self.dev
-        assert (logits is None) != (actions is None), "give logits or actions"
-        lg = None if logits is None else logits.reshape(B * N, 5).contiguous().float()
-        ac = None if actions is None else _dev_i32(actions, "actions").reshape(B * N)
+        lg, ac = sh.dev_actions(logits, actions, B, N)
         policy = self.policy if lg is not None else 0
         if policy and uniforms is None:
             uniforms = torch.rand(B, N, dtype=torch.float64, device=dev, generator=self.generator)
         if uniforms is not None:
-            if not uniforms.is_cuda or uniforms.dtype != torch.float64 or uniforms.numel() != B * N:
-                raise nat.MagatNativeError("uniforms must be a (B,N) float64 device tensor")
-            uniforms = uniforms.contiguous()
+            uniforms = sh.dev_uniforms(uniforms, B, N)
         d = nat.SimStepDesc()
         d.logits, d.actions_in, d.map = nat.ptr(lg), nat.ptr(ac), nat.ptr(self.map)
         d.map_batched = 1 if self.map.dim() == 3 else 0
@@ -393,14 +326,9 @@ class BatchedEpisode:
         d.currentstep, d.maxstep = self.currentstep, self.maxstep
         d.actions_out, d.moves_out, d.flags_out = nat.ptr(self.actions), nat.ptr(self.moves), nat.ptr(self.flags)
         d.done_out, d.flowtime_out, d.makespan_out = nat.ptr(self.done), nat.ptr(self.flowtime), nat.ptr(self.makespan)
-        import ctypes
-        with torch.cuda.device(dev):
-            if self.wide and move_needs_wide(d.H, d.W, N):
-                lib = nat.lib()
-                ws = self._move_ws.get(lib.magat_sim_move_wide_workspace_bytes(B, d.H, d.W, N), dev)
-                nat.check(lib.magat_sim_step_wide(ctypes.byref(d), nat.ptr(ws), ws.numel(), nat.current_stream(dev)),
-                          "magat_sim_step_wide")
-            else:
-                nat.check(nat.lib().magat_sim_step(ctypes.byref(d), nat.current_stream(dev)), "magat_sim_step")
+        ws = None
+        if self.wide and move_needs_wide(d.H, d.W, N):
+            ws = self._move_ws.get(nat.lib().magat_sim_move_wide_workspace_bytes(B, d.H, d.W, N), dev)
+        sh.call(dev, "magat_sim_step", ctypes.byref(d), ws=ws)
         self.currentstep += 1
         return self.done
