@@ -52,8 +52,9 @@ extern "C" {
                                      normalises the Q columns of the maps and writes the normalised rows of X into the workspace
                                      (magat_gat_workspace_bytes and the CSR sizes grow by B N G floats), then the KeyQuery graph
                                      kernels on them (128 features beyond 105 agents and N > 128: the generic CSR score and hop
-                                     kernels).  The bf16 and the
-                                     training entry points answer MAGAT_ERR_UNSUPPORTED, as does any call with P != 1 or G != F. */
+                                     kernels).  The bf16 entry points and magat_gat_train_forward_f32 / _backward_f32 answer
+                                     MAGAT_ERR_UNSUPPORTED, as does any call with P != 1 or G != F; training runs through the
+                                     pair of its own, magat_gat_train_forward_cos_f32 / _backward_cos_f32 (below). */
 
 int magat_abi_version(void);
 /* 0 = release build.  1 = EXPERIMENT build: at least one source was compiled with timing-experiment switches (*_WHATIF_*:
@@ -235,6 +236,28 @@ int magat_gat_train_backward_f32(const float* dYpre, const float* X, const float
                                  const int* rowptr, const int* colidx, const int* cscptr, const int* cscsrc,
                                  const int* cscpos, long long nnz, float* dZ, float* dXd, float* datt, int B, int N,
                                  int G, int F, int K, int P, int mode, void* stream);
+/* The same pair for attentionMode 'GAT_Similarity' (P = E = 1, F = G, float32): cosine scores are KeyQuery scores of normalised
+ * operands, so the forward runs the KeyQuery launches behind the normalisation kernel and keeps what that kernel did, and the
+ * backward runs the KeyQuery backward on the normalised rows and pushes the two score gradients back through the normalisation.
+ * `packed`: KeyQuery's layout (magat_gat_pack_weights with either mode), NC = G + K*G, score columns at 0, U_k at G + k*G.
+ * Forward, beyond the outputs above: Xhat [M][G] = x_m / max(|x_m|, 1e-9) and norms [2][M] = the unclamped |x_m|, then |q_m|
+ * (float32 sums of squares).  AFTER THE CALL THE SCORE COLUMNS OF Z HOLD q^_m = q_m / max(|q_m|, 1e-9), NOT q_m.
+ * Backward: per row and v in {x, q}, c = max(n, 1e-9):  dv = (1/c) (dv^ - (dv^ . v^) u),  u = v^ (c/n) if n > 0 else 0  - for a
+ * clamped row u is still the true unit vector (what torch's cosine_similarity differentiates to), for a zero row dv = dv^ 1e9.
+ * dXd and the score columns of dZ leave the call as gradients wrt x and q; the caller's two GEMMs are the KeyQuery ones.
+ * Refusals before anything is launched, in the order and with the codes of the pair above: NULL pointers (Xhat and norms too),
+ * B, N, K <= 0 or nnz < 0, then G outside {16,32,64,128,256} and N > 8190 MAGAT_ERR_UNSUPPORTED, then more than 2^31 - 1 rows or
+ * workgroups MAGAT_ERR_BAD_SHAPE.  The pair above keeps answering MAGAT_ERR_UNSUPPORTED for MAGAT_MODE_SIMILARITY.  Launch tags:
+ * gat_maps_gemm, gat_prepare (both normalisation kernels), gat_graph; the forward counts in a form counter of its own (25,
+ * numbered in the library: MAGAT_FORMS below stays what ABI 9 was built against). */
+int magat_gat_train_forward_cos_f32(const float* X, const int* rowptr, const int* colidx, long long nnz, const float* packed,
+                                    const float* bias, float* Ypre, float* att, float* Z, float* T, float* Xhat, float* norms,
+                                    int* cscptr, int* cscsrc, int* cscpos, int* csctmp, int B, int N, int G, int K,
+                                    void* stream);
+int magat_gat_train_backward_cos_f32(const float* dYpre, const float* Xhat, const float* Z, const float* att, const float* T,
+                                     const float* norms, const int* rowptr, const int* colidx, const int* cscptr,
+                                     const int* cscsrc, const int* cscpos, long long nnz, float* dZ, float* dXd, float* datt,
+                                     int B, int N, int G, int K, void* stream);
 
 /* Backward of the non-attentional graph filter (GraphFilterBatch / BatchLSIGF, graphML.py:5485-5700).  The layer is linear in
  * x and in the taps:  Y = b + sum_k A^k X H_k^T  (A = row operator of "x @ S"), so  dU_k = (A^T)^k dY  is the forward hop

@@ -25,7 +25,7 @@ TAG_ACTIONS = 12
 # magat_form_count ids (include/magat_hip.h MAGAT_FORM_*)
 FORMS = {"head_longk": 0, "head_splitk": 1, "gat_pack": 2, "gat_persist": 3, "gat_hsplit": 4, "chain_persist": 5,
          "head_compress": 6, "guard_one": 7, "csr_fused": 8, "gat_mid": 9, "chain_lat": 10, "head_lat": 11, "guard_lat": 12, "stem_lat": 13, "actions_tail": 14, "gnn_dense": 15, "sim_guided": 16, "sim_expert": 17, "sim_mapf": 18, "sim_mapf_lns": 19, "sim_mapf_audit": 20, "sim_mapf_cbs": 21, "sim_mapf_ecbs": 22,
-         "chain_tile16": 23, "sim_replay": 24}
+         "chain_tile16": 23, "sim_replay": 24, "gat_cos_train": 25}
 TAG_GNN_DENSE = 25
 TAG_SIM_GUIDED = 26
 TAG_SIM_EXPERT = 27
@@ -144,6 +144,8 @@ _SIGNATURES = {
     "magat_gat_forward_csr_bf16": (_I, [_P, _P, _P, ctypes.c_longlong, _P, _P, _P, _I, _P, _P, _Z] + [_I] * 8 + [_P]),
     "magat_gat_train_forward_f32": (_I, [_P, _P, _P, ctypes.c_longlong] + [_P] * 10 + [_I] * 7 + [_P]),
     "magat_gat_train_backward_f32": (_I, [_P] * 10 + [ctypes.c_longlong] + [_P] * 3 + [_I] * 7 + [_P]),
+    "magat_gat_train_forward_cos_f32": (_I, [_P, _P, _P, ctypes.c_longlong] + [_P] * 12 + [_I] * 4 + [_P]),
+    "magat_gat_train_backward_cos_f32": (_I, [_P] * 11 + [ctypes.c_longlong] + [_P] * 3 + [_I] * 4 + [_P]),
     "magat_gso_csr_workspace_bytes": (_Z, [_I, _I]),
     "magat_gso_csr_build": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.c_longlong, _P, _P, _Z, _I, _I, _P]),
     "magat_gso_csr_build_phase": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.c_longlong, _P, _P, _Z, _I, _I, _I, _P]),

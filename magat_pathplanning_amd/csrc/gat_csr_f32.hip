@@ -1149,10 +1149,11 @@ extern "C" int magat_gat_forward_csc_bf16_f32out(const uint16_t* X, const int* r
 
 // Training forward: the split-form forward on float32 MFMA maps that keeps what the backward
 // (gat_train.hip) needs - Z, the attention values and the hop intermediates T_k
-extern "C" int magat_gat_train_forward_f32(const float* X, const int* rowptr, const int* colidx, long long nnz,
-                                           const float* packed, const float* bias, float* Ypre, float* att, float* Z,
-                                           float* T, int* cscptr, int* cscsrc, int* cscpos, int* csctmp, int B, int N,
-                                           int G, int F, int K, int P, int mode, void* stream) {
+// (Xhat, norms: GAT_Similarity's form, magat_gat_train_forward_cos_f32 - mode is KeyQuery then, P = 1)
+static int train_forward(const float* X, const int* rowptr, const int* colidx, long long nnz, const float* packed,
+                         const float* bias, float* Ypre, float* att, float* Z, float* T, int* cscptr, int* cscsrc, int* cscpos,
+                         int* csctmp, int B, int N, int G, int F, int K, int P, int mode, void* stream, float* Xhat = nullptr,
+                         float* norms = nullptr) {
   if (!X || !rowptr || !packed || !Ypre || !att || !Z || !cscptr || !cscsrc || !cscpos || !csctmp) return MAGAT_ERR_NULL;
   if (nnz > 0 && !colidx) return MAGAT_ERR_NULL;
   if (K > 2 && !T) return MAGAT_ERR_NULL;
@@ -1171,6 +1172,12 @@ extern "C" int magat_gat_train_forward_f32(const float* X, const int* rowptr, co
   // split GEMM (the maps are 5 % of a training step either way)
   int rc = magat_gat_maps_gemm(X, packed, Z, (int)M, G, L.NC, L.NC, stream, 0, nullptr, 1);
   if (rc != MAGAT_OK) return rc;
+  if (Xhat) {      // cosine scores = KeyQuery scores of the normalised operands: q^ in place in Z, x^ in Xhat, the norms kept
+    magat_form_note(MAGAT_FORM_GAT_COS_TRAIN);
+    rc = magat_gat_cos_prepare(X, Z, Xhat, M, G, L.qoff, L.NC, 0, stream, nullptr, norms);
+    if (rc != MAGAT_OK) return rc;
+    X = Xhat;      // (read below for the scores' x_i only: the taps come from Z)
+  }
   CsrParams p = {};
   p.X = X; p.Z = Z; p.rowptr = rowptr; p.colidx = colidx; p.cscptr = cscptr; p.cscsrc = cscsrc; p.cscpos = cscpos;
   p.att = att; p.bias = bias; p.Y = Ypre; p.ldy = P * F;
@@ -1200,4 +1207,24 @@ extern "C" int magat_gat_train_forward_f32(const float* X, const int* rowptr, co
     if (rc != MAGAT_OK) return rc;
   }
   return MAGAT_OK;
+}
+
+extern "C" int magat_gat_train_forward_f32(const float* X, const int* rowptr, const int* colidx, long long nnz,
+                                           const float* packed, const float* bias, float* Ypre, float* att, float* Z,
+                                           float* T, int* cscptr, int* cscsrc, int* cscpos, int* csctmp, int B, int N,
+                                           int G, int F, int K, int P, int mode, void* stream) {
+  return train_forward(X, rowptr, colidx, nnz, packed, bias, Ypre, att, Z, T, cscptr, cscsrc, cscpos, csctmp, B, N, G, F, K, P,
+                       mode, stream);
+}
+
+// GAT_Similarity's training forward (P = 1, F = G): the same launches on (Xhat, Z) behind gat_cos_prepare_kernel, which also
+// keeps the two norms of every row for the backward (magat_gat_train_backward_cos_f32, gat_train.hip).  After the call the score
+// columns of Z hold q^, not q.
+extern "C" int magat_gat_train_forward_cos_f32(const float* X, const int* rowptr, const int* colidx, long long nnz,
+                                               const float* packed, const float* bias, float* Ypre, float* att, float* Z,
+                                               float* T, float* Xhat, float* norms, int* cscptr, int* cscsrc, int* cscpos,
+                                               int* csctmp, int B, int N, int G, int K, void* stream) {
+  if (!Xhat || !norms) return MAGAT_ERR_NULL;
+  return train_forward(X, rowptr, colidx, nnz, packed, bias, Ypre, att, Z, T, cscptr, cscsrc, cscpos, csctmp, B, N, G, G, K, 1,
+                       MAGAT_MODE_KEYQUERY, stream, Xhat, norms);
 }

@@ -1049,7 +1049,8 @@ __global__ void head_mean_relu_kernel(const float* __restrict__ ytmp, float* __r
 template <int G>
 __global__ __launch_bounds__(256) void gat_cos_prepare_kernel(const float* __restrict__ X, float* __restrict__ Z,
                                                               float* __restrict__ Xhat, long long M, int qoff, int zrow,
-                                                              long long zts, const int* __restrict__ run_if) {
+                                                              long long zts, const int* __restrict__ run_if,
+                                                              float* __restrict__ norms) {      // [2][M] or null: |x_m|, |q_m| unclamped (training)
   if (run_if && *run_if == 0) return;      // (predicated form: inside the range guard's re-run behind the one-launch cosine kernel)
   constexpr int LPR = G / 4;          // lanes per row: 4 .. 64, a row never straddles two waves
   constexpr int RPB = 256 / LPR;      // rows per workgroup step
@@ -1068,7 +1069,12 @@ __global__ __launch_bounds__(256) void gat_cos_prepare_kernel(const float* __res
       sx += __shfl_xor(sx, o, 64);
       sq += __shfl_xor(sq, o, 64);
     }
-    const float ix = 1.f / fmaxf(sqrtf(sx), 1e-9f), iq = 1.f / fmaxf(sqrtf(sq), 1e-9f);
+    const float nx = sqrtf(sx), nq = sqrtf(sq);
+    const float ix = 1.f / fmaxf(nx, 1e-9f), iq = 1.f / fmaxf(nq, 1e-9f);
+    if (norms && sub == 0) {
+      norms[m] = nx;
+      norms[M + m] = nq;
+    }
     x *= ix;
     q *= iq;
     *reinterpret_cast<f32x4*>(Xhat + m * G + 4 * sub) = x;
@@ -1192,7 +1198,7 @@ int magat_gat_maps_gemm(const float* X, const float* packed, float* Z, int M, in
 }
 
 int magat_gat_cos_prepare(const float* X, float* Z, float* Xhat, long long M, int G, int qoff, int ldz, long long ntile_stride,
-                          void* stream, const int32_t* run_if) {
+                          void* stream, const int32_t* run_if, float* norms) {
   if (!X || !Z || !Xhat) return MAGAT_ERR_NULL;
   if (M <= 0 || !supported_width(G) || (qoff % G) || (ldz & 3)) return MAGAT_ERR_BAD_SHAPE;
   hipStream_t st = static_cast<hipStream_t>(stream);
@@ -1203,7 +1209,7 @@ int magat_gat_cos_prepare(const float* X, float* Z, float* Xhat, long long M, in
   const int zrow = ntile_stride ? 128 : ldz;
   const int pid = magat_prof_begin(run_if ? MAGAT_TAG_RANGE_GUARD : MAGAT_TAG_GAT_PREPARE, st);
   MAGAT_WIDTH_SWITCH(G, hipLaunchKernelGGL((gat_cos_prepare_kernel<WW>), dim3((unsigned)blocks), dim3(256), 0, st, X, Z, Xhat, M,
-                                           qoff, zrow, ntile_stride, reinterpret_cast<const int*>(run_if)));
+                                           qoff, zrow, ntile_stride, reinterpret_cast<const int*>(run_if), norms));
   magat_prof_end(pid, st);
   return magat_check_launch();
 }

@@ -2,6 +2,7 @@
 // forward kernels and lives with them in gat_csr_f32.hip).
 #include "magat_common.h"
 #include "gat_pack.h"
+#include "gat_cos_parts.h"
 
 // =====================================================================================================
 // Training support: forward that keeps what the backward needs, and the
@@ -14,6 +15,8 @@
 //     dE_ij = a_ij (dA_ij - sum_j' a_ij' dA_ij')
 //     KeyQuery: dX_i += sum_j dE_ij q_j,  dQ_j = sum_i dE_ij x_i
 //     modified: g_ij = dE_ij * lrelu'(c1_j + c2_i),  dc2_i = sum_j g_ij,  dc1_j = sum_i g_ij
+//     GAT_Similarity (magat_gat_train_backward_cos_f32): KeyQuery on the normalised rows (X = Xhat, Z's score columns = q^),
+//     then dXd and dQ go back through the normalisation in place (gat_cos_backward_kernel, gat_cos_parts.h)
 // =====================================================================================================
 namespace {
 
@@ -292,6 +295,33 @@ extern "C" int magat_gat_train_backward_f32(const float* dYpre, const float* X, 
   if (rc != MAGAT_OK) return rc;
   MAGAT_WIDTH_SWITCH(G, rc = launch_rows<WW>(bwd_scores_cols_kernel<WW>, p, 1, st));
   return rc;
+}
+
+extern "C" int magat_gat_train_backward_cos_f32(const float* dYpre, const float* Xhat, const float* Z, const float* att,
+                                                const float* T, const float* norms, const int* rowptr, const int* colidx,
+                                                const int* cscptr, const int* cscsrc, const int* cscpos, long long nnz,
+                                                float* dZ, float* dXd, float* datt, int B, int N, int G, int K, void* stream) {
+  if (!dYpre || !Xhat || !Z || !att || !norms || !rowptr || !cscptr || !cscsrc || !cscpos || !dZ || !dXd || !datt)
+    return MAGAT_ERR_NULL;
+  if (nnz > 0 && !colidx) return MAGAT_ERR_NULL;
+  if (K > 2 && !T) return MAGAT_ERR_NULL;
+  if (B <= 0 || N <= 0 || nnz < 0 || K <= 0) return MAGAT_ERR_BAD_SHAPE;
+  if (!supported_width(G) || N > 8190) return MAGAT_ERR_UNSUPPORTED;      // (N: the limit of the forward that made the CSC view)
+  const long long M = (long long)B * N;
+  if (M > 0x7fffffffLL || (K > 1 && rows_grid(B, N, 1) > 0x7fffffffLL)) return MAGAT_ERR_BAD_SHAPE;
+  int rc = magat_gat_train_backward_f32(dYpre, Xhat, Z, att, T, rowptr, colidx, cscptr, cscsrc, cscpos, nnz, dZ, dXd, datt, B, N,
+                                        G, G, K, 1, MAGAT_MODE_KEYQUERY, stream);
+  if (rc != MAGAT_OK || K == 1) return rc;      // (K = 1: no scores - dXd and the score columns of dZ are zero, and stay so)
+  hipStream_t st = static_cast<hipStream_t>(stream);
+  const PackLayout L = pack_layout(G, G, K, 1, MAGAT_MODE_KEYQUERY);
+  const int rpb = 256 / (G / 4);
+  long long blocks = (M + rpb - 1) / rpb;
+  if (blocks > 2048) blocks = 2048;      // (memory-bound: the workgroups stride over the rest)
+  const int pid = magat_prof_begin(MAGAT_TAG_GAT_PREPARE, st);
+  MAGAT_WIDTH_SWITCH(G, hipLaunchKernelGGL((gat_cos_backward_kernel<WW>), dim3((unsigned)blocks), dim3(256), 0, st, Xhat, Z, norms,
+                                           dXd, dZ, M, L.NC, L.qoff));
+  magat_prof_end(pid, st);
+  return magat_check_launch();
 }
 
 extern "C" int magat_gnn_backward_csr_f32(const float* dY, const int* rowptr, const int* colidx, const float* vals,

@@ -59,10 +59,11 @@ void magat_form_note(int id);      // which form a launch took (MAGAT_FORM_*; pr
 #define MAGAT_FORM_SIM_MAPF_ECBS 22   // magat_sim_mapf_ecbs launched its one-wave-per-case kernel
 #define MAGAT_FORM_CHAIN_TILE16 23   // magat_block_full launched the form with layer3.conv2 on 16-row tiles (option CHAIN_TILE16)
 #define MAGAT_FORM_SIM_REPLAY 24     // magat_sim_replayed_states or its wide form launched (SemiLG from the schedule; tag MAGAT_TAG_SIM_GUIDED)
-#define MAGAT_FORMS_TABLE 25
+#define MAGAT_FORM_GAT_COS_TRAIN 25  // magat_gat_train_forward_cos_f32 launched (GAT_Similarity's training forward; one count per call)
+#define MAGAT_FORMS_TABLE 26
 static_assert(MAGAT_PROF_TAGS_ALL >= MAGAT_PROF_TAGS && MAGAT_FORMS_ALL >= MAGAT_FORMS, "internal tag / form tables");
 static_assert(MAGAT_PROF_TAGS_TABLE > MAGAT_TAG_SIM_MAPF_ECBS && MAGAT_PROF_TAGS_TABLE >= MAGAT_PROF_TAGS_ALL &&
-              MAGAT_FORMS_TABLE > MAGAT_FORM_SIM_REPLAY && MAGAT_FORMS_TABLE >= MAGAT_FORMS_ALL, "internal tag / form tables");
+              MAGAT_FORMS_TABLE > MAGAT_FORM_GAT_COS_TRAIN && MAGAT_FORMS_TABLE >= MAGAT_FORMS_ALL, "internal tag / form tables");
 
 // the move step with per-instance counters (sim_frontend.hip: sim_move_kernel), launched for the case pool's entries (sim_pool.hip)
 struct magat_sim_pool_slots {
@@ -218,7 +219,8 @@ int magat_gat_maps_gemm(const float* X, const float* packed, float* Z, int M, in
 // divided by max(|.|, 1e-9) in place and Xhat [M][G] = X[m] / max(|X[m]|, 1e-9) is written; the KeyQuery graph kernels then form
 // cosine scores from (Xhat, Z).  Z addressing as magat_gat_maps_gemm's (ldz, ntile_stride); G a supported width.
 int magat_gat_cos_prepare(const float* X, float* Z, float* Xhat, long long M, int G, int qoff, int ldz, long long ntile_stride,
-                          void* stream, const int32_t* run_if = nullptr);      // run_if: the launch is a no-op unless *run_if != 0
+                          void* stream, const int32_t* run_if = nullptr,      // run_if: the launch is a no-op unless *run_if != 0
+                          float* norms = nullptr);      // [2][M] or null: the unclamped |X[m]| and |Q[m]| (the training forward keeps them)
 
 // fp32 -> three bf16 planes (round-to-nearest-even each)
 __device__ __forceinline__ unsigned short magat_bf16_rne(float v) {

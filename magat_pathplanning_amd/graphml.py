@@ -7,7 +7,9 @@ the layer evaluates the same algebra with differentiable torch ops on whatever d
 tensors live on -- that composite exists for backward only and is never used for inference.  On GPU tensors the
 training forward and backward of the graph part run on the HIP kernels too (_GatTrainFunction); the composite then only
 serves CPU tensors (the gloo / host tests) and requests for the dense attention tensor under autograd.
-GraphFilterBatchSimilarityAttentional (attentionMode 'GAT_Similarity') has no HIP backward: under autograd it always takes the composite.
+GraphFilterBatchSimilarityAttentional (attentionMode 'GAT_Similarity') takes the composite under autograd by default; with
+hip_backward=True its training step runs on the HIP kernels as well (_GatCosTrainFunction: the KeyQuery training kernels on the
+normalised operands, and one kernel that takes the score gradients back through the normalisation).
 """
 import math
 import os
@@ -493,6 +495,83 @@ class _GatTrainFunction(torch.autograd.Function):
         return dX, grads[0], grads[1], grads[2], grads[3], dbias, None, None, None, None
 
 
+_COS_TRAIN_WIDTHS = (16, 32, 64, 128, 256)
+_COS_TRAIN_MAX_N = 8190
+
+
+class _GatCosTrainFunction(torch.autograd.Function):
+    """HIP forward + backward of GraphFilterBatchSimilarityAttentional for training (P = E = 1, pre-activation output):
+    magat_gat_train_forward_cos_f32 / magat_gat_train_backward_cos_f32.  Kept for the backward: the normalised rows Xhat, the two
+    norms of every row, Z (whose score columns hold the normalised q), the attention values, the hop results and the structure.
+    mixer and weight_bias are never read by this mode and are no inputs here: their gradients stay None, as in the reference."""
+
+    @staticmethod
+    def forward(ctx, X, weight, taps, bias, rowptr, colidx, nnz, layer):
+        lib = nat.lib()
+        B, N, G = X.shape
+        K = layer.K
+        if G not in _COS_TRAIN_WIDTHS or N > _COS_TRAIN_MAX_N:
+            raise nat.MagatNativeError("GAT_Similarity with hip_backward=True: %d features on graphs of %d agents are outside the "
+                                       "training kernels (feature widths %s, N <= %d)" % (G, N, _COS_TRAIN_WIDTHS, _COS_TRAIN_MAX_N))
+        dev, M = X.device, B * N
+        Xc = X.detach().contiguous().float()
+        with torch.cuda.device(dev):
+            stream = nat.current_stream(dev)
+            packed = _packed_weights(layer, dev, stream, G, G, K, 1, nat.MODE_SIMILARITY)
+            NC = _packed_cols(layer.attentionMode, G, G, K, 1)
+            Ypre = torch.empty(M, G, dtype=torch.float32, device=dev)
+            att = torch.empty(1, max(nnz, 1), dtype=torch.float32, device=dev)
+            Z = torch.empty(M, NC, dtype=torch.float32, device=dev)
+            T = torch.empty(max(K - 2, 0), M, G, dtype=torch.float32, device=dev) if K > 2 else None
+            Xhat = torch.empty(M, G, dtype=torch.float32, device=dev)
+            norms = torch.empty(2, M, dtype=torch.float32, device=dev)
+            cscptr = torch.empty(B * (N + 1), dtype=torch.int32, device=dev)
+            csc = torch.empty(3, max(nnz, 1), dtype=torch.int32, device=dev)
+            b1 = None if bias is None else bias.detach().reshape(-1).contiguous().float()
+            nat.check(lib.magat_gat_train_forward_cos_f32(
+                nat.ptr(Xc), nat.ptr(rowptr), nat.ptr(colidx), nnz, nat.ptr(packed), nat.ptr(b1), nat.ptr(Ypre), nat.ptr(att),
+                nat.ptr(Z), nat.ptr(T), nat.ptr(Xhat), nat.ptr(norms), nat.ptr(cscptr), nat.ptr(csc[0]), nat.ptr(csc[1]),
+                nat.ptr(csc[2]), B, N, G, K, stream), "magat_gat_train_forward_cos_f32")
+        ctx.layer, ctx.nnz, ctx.dims = layer, nnz, (B, N, G, K, NC)
+        ctx.has_bias = bias is not None
+        ctx.save_for_backward(Xc, Xhat, norms, Z, att, T if T is not None else torch.empty(0, device=dev), rowptr, colidx,
+                              cscptr, csc, packed, weight, taps)
+        return Ypre
+
+    @staticmethod
+    def backward(ctx, dYpre):
+        lib = nat.lib()
+        Xc, Xhat, norms, Z, att, T, rowptr, colidx, cscptr, csc, packed, weight, taps = ctx.saved_tensors
+        B, N, G, K, NC = ctx.dims
+        dev, M = Xc.device, B * N
+        dY = dYpre.contiguous().float()
+        with torch.cuda.device(dev):
+            stream = nat.current_stream(dev)
+            dZ = torch.empty(M, NC, dtype=torch.float32, device=dev)
+            dXd = torch.empty(M, G, dtype=torch.float32, device=dev)
+            datt = torch.empty(1, max(ctx.nnz, 1), dtype=torch.float32, device=dev)
+            nat.check(lib.magat_gat_train_backward_cos_f32(
+                nat.ptr(dY), nat.ptr(Xhat), nat.ptr(Z), nat.ptr(att), nat.ptr(T if T.numel() else None), nat.ptr(norms),
+                nat.ptr(rowptr), nat.ptr(colidx), nat.ptr(cscptr), nat.ptr(csc[0]), nat.ptr(csc[1]), ctx.nnz, nat.ptr(dZ),
+                nat.ptr(dXd), nat.ptr(datt), B, N, G, K, stream), "magat_gat_train_backward_cos_f32")
+        Bt = packed[:NC * G].view(NC, G)
+        # the caller's two GEMMs, as for KeyQuery (dZ's score columns are gradients wrt q = W x now): dX = dXd + dZ Bt, dBt = dZ^T X
+        dX = (dXd + _gemm_nt(dZ, Bt.t().contiguous(), dev)).view(B, N, G)
+        dBt = _gemm_nt(dZ.t().contiguous(), Xc.view(M, G).t().contiguous(), dev)
+        grads = [None, None]
+        params = [weight, taps]
+        need = [i for i, t in enumerate(params) if t.requires_grad]
+        if need:
+            with torch.enable_grad():
+                leaves = [t.detach().requires_grad_(True) for t in params]
+                Bt_t, _ = pack_torch(leaves[0], None, None, leaves[1], ctx.layer.attentionMode)      # (the column bias is constant zero)
+                got = torch.autograd.grad([Bt_t], [leaves[i] for i in need], [dBt], allow_unused=True)
+            for i, g in zip(need, got):
+                grads[i] = g
+        dbias = dY.sum(dim=0).view(G, 1) if ctx.has_bias else None
+        return dX, grads[0], grads[1], dbias, None, None, None, None
+
+
 def _composite(layer, x, S):
     """Differentiable torch-op evaluation (training only).  x (B,G,N); S (B,1,N,N)."""
     B, G, N = x.shape
@@ -770,17 +849,21 @@ class GraphFilterBatchSimilarityAttentional(GraphFilterBatchAttentional):
     (P,E,2F), weight_bias (P,E,F), weight (P,E,F,G), filterWeight (P,F,E,K,G), bias (F,1); mixer and weight_bias are never read.
     The reference reshapes weight into (G,G) and the input into (B,P,E,G,N,1): F == G is required here at construction, and
     P * E != 1 raises RuntimeError in forward, where the reference's reshape raises it.  Inference: the KeyQuery kernels behind
-    one normalisation kernel (MAGAT_MODE_SIMILARITY, float32 storage only); under autograd always the torch composite - the
-    HIP backward is not built for this mode."""
+    one normalisation kernel (MAGAT_MODE_SIMILARITY, float32 storage only).  Under autograd: the torch composite by default;
+    with hip_backward=True (constructor keyword and public attribute, not part of the state_dict) a device input takes the HIP
+    training kernels instead - _GatCosTrainFunction, feature widths 16 .. 256 and N <= 8190, anything else raises
+    MagatNativeError.  CPU tensors and return_attention = True keep the composite either way."""
 
     _similarity = True
-    _hip_backward = False
+    _hip_backward = False        # (the base class's route through _GatTrainFunction: its entry points refuse this mode)
+    hip_backward = False
 
     def __init__(self, G, F, K, P, E=1, bias=True, nonlinearity=nn.functional.relu, concatenate=True,
-                 attentionMode="GAT_Similarity"):
+                 attentionMode="GAT_Similarity", hip_backward=False):
         if G != F:
             raise NotImplementedError("GAT_Similarity needs F == G (the reference reshapes W (P,E,F,G) into (1,P,E,G,G))")
         super().__init__(G, F, K, P, E, bias, nonlinearity, concatenate, "GAT_Similarity")
+        self.hip_backward = bool(hip_backward)
 
     def _register_parameters(self, bias):
         # (state_dict order: mixer, weight_bias, weight, filterWeight, bias)
@@ -808,7 +891,24 @@ class GraphFilterBatchSimilarityAttentional(GraphFilterBatchAttentional):
 
     def forward(self, x):
         self._check_forward(x.shape[0], self.N if self.S is not None else x.shape[2])
+        if (self.hip_backward and x.is_cuda and not self.return_attention and torch.is_grad_enabled() and
+                (x.requires_grad or any(p.requires_grad for p in self.parameters()))):
+            return self._forward_hip_train(x)
         return super().forward(x)
+
+    def _forward_hip_train(self, x):
+        """Training on the GPU with hip_backward: HIP forward + backward of the layer (CSR kernels), ReLU in torch."""
+        B, Gin, Nin = x.shape
+        assert self.S is not None, "addGSO must be called before forward"
+        N = self.N
+        if Nin < N:
+            x = torch.cat((x, torch.zeros(B, Gin, N - Nin, dtype=x.dtype, device=x.device)), dim=2)
+        rowptr, colidx, nnz = dense_gso_to_csr(_gso3(self.S, B, N, x.device), self_loops=self.edge_rule)
+        Ypre = _GatCosTrainFunction.apply(x.permute(0, 2, 1).contiguous(), self.weight, self.filterWeight, self.bias, rowptr,
+                                          colidx, nnz, self)
+        y = torch.relu(Ypre.view(B, N, self.F)).permute(0, 2, 1)      # (one head: concatenation and mean are the same rows)
+        self.aij = None
+        return y[:, :, :Nin] if Nin < N else y
 
 
 class _GnnTrainFunction(torch.autograd.Function):

@@ -587,9 +587,12 @@ class DecentralPlannerGATNet(_PlannerBase):
                                       % (config.attentionMode,))
         layer_cls = {"GAT_origin": GraphFilterBatchAttentional_Origin,
                      "GAT_Similarity": GraphFilterBatchSimilarityAttentional}.get(config.attentionMode, GraphFilterBatchAttentional)
+        # optional key (not in the reference's configs), read for 'GAT_Similarity' only: True takes that layer's training step
+        # to the HIP kernels (GraphFilterBatchSimilarityAttentional.hip_backward); default False, the torch composite
+        extra = {"hip_backward": bool(getattr(config, "gat_hip_backward", False))} if config.attentionMode == "GAT_Similarity" else {}
         self.GFL = nn.Sequential(layer_cls(
             self.F[0], self.F[1], self.K[0], self.P[0], self.E, self.bias,
-            concatenate=config.AttentionConcat, attentionMode=config.attentionMode))
+            concatenate=config.AttentionConcat, attentionMode=config.attentionMode, **extra))
         # optional key (not in the reference's configs): HBM storage type inside the GAT layer at inference,
         # 'fp32' (default, the 1e-4 parity path) or 'bf16' (BASELINE config 5)
         storage = getattr(config, "gat_storage", "fp32")
