@@ -732,6 +732,39 @@ int magat_bn_train_backward_f32(const float* x, const float* y, const float* dy,
                                 const float* gamma, const float* save_mean, const float* save_invstd, int relu, float* dgamma,
                                 float* dbeta, float* workspace, void* stream);
 
+/* Training of the action head and the loss (head_loss.hip; additive behind ABI 9): the LAST Linear of actionsMLP (width -> the
+ * reference's 5 action logits), log-softmax and the loss in one pass over the head's input rows, their backward in one more.
+ *   mode 0  nn.CrossEntropyLoss():  loss = mean_r(-log p[r, t_r]),  dlogits = (p - onehot) / M
+ *   mode 1  the reference's graphs/losses/label_smoothing.py LabelSmoothing(5, smoothing) (LogSoftmax + KLDivLoss summed): with
+ *           q = smoothing / 4 off the target and 1 - smoothing on it,  loss = sum_r sum_c q_rc (log q_rc - log p_rc)  - a SUM
+ *           over the rows that carries the target's entropy term; a class with q = 0 contributes 0.  dlogits = p - q
+ * magat_head_loss_forward_f32: logits [M][5] = X W^T + b (X rows ldx >= width floats apart, W [5][width], b [5] or NULL), the
+ *   stable log-sum-exp (row maximum subtracted), dlogits [M][5] = d loss / d logits for grad_loss = 1, row_loss [M] (or NULL) and
+ *   loss [1].  target [M] int64; one outside 0..4 is never used as an index: its row's loss and its dlogits row are NaN (and so
+ *   the total), no other row changes.
+ * magat_head_loss_backward_f32: with g = *grad_loss (a DEVICE scalar, read on the device)  dX [M][lddx] = g dlogits W,
+ *   dW [5][width] = g dlogits^T X,  db [5] = g sum_r dlogits  (each nullable).
+ * magat_action_loss_f32: the same loss and dlogits (nullable) on logits [M][ld >= 5] that something else produced.
+ * Float32 arithmetic; every cross-row sum (loss, dW, db) adds per-workgroup partials in a fixed order in double: deterministic,
+ * no atomics.  Two launches per call, no host synchronisation, no allocation.  workspace:
+ * magat_head_loss_workspace_floats(M, width) floats, 8-byte aligned (0 = unsupported shape; magat_action_loss_f32 takes the
+ * size of any supported width, e.g. 4).  Checks, before any launch: a NULL required pointer MAGAT_ERR_NULL; M or width <= 0
+ * MAGAT_ERR_BAD_SHAPE; width % 4 != 0 or width > 1024, ldx / lddx / ld below its width, ldx or lddx not a multiple of 4 or X, W,
+ * dX not 16-byte aligned (rows are read in 16-byte pieces), mode outside {0, 1}, smoothing outside [0, 1)
+ * MAGAT_ERR_UNSUPPORTED; then a workspace that is not 8-byte aligned MAGAT_ERR_WORKSPACE.  Profiling tag 33 ("head_loss", one
+ * span per call) - numbered in the library, MAGAT_PROF_TAGS below stays what ABI 9 was built against. */
+size_t magat_head_loss_workspace_floats(long long M, int width);
+int magat_head_loss_forward_f32(const float* X, int ldx, const float* W /*5 x width*/, const float* b /*5 or NULL*/,
+                                const int64_t* target /*M*/, int mode, float smoothing, float* logits /*M x 5*/,
+                                float* dlogits /*M x 5*/, float* row_loss /*M or NULL*/, float* loss /*1*/, float* workspace,
+                                long long M, int width, void* stream);
+int magat_head_loss_backward_f32(const float* dlogits, const float* grad_loss /*device scalar*/, const float* X, int ldx,
+                                 const float* W, float* dX /*M x width or NULL*/, int lddx, float* dW /*5 x width or NULL*/,
+                                 float* db /*5 or NULL*/, float* workspace, long long M, int width, void* stream);
+int magat_action_loss_f32(const float* logits, int ld, const int64_t* target, int mode, float smoothing,
+                          float* dlogits /*or NULL*/, float* row_loss /*or NULL*/, float* loss, float* workspace, long long M,
+                          void* stream);
+
 /* y[M,N] = act(x[M,K] @ w[N,K]^T + b)   (torch.nn.Linear; …bottleneck.py:105,160,229) */
 int magat_linear_f32(const float* x, int ldx, const float* w, const float* b, float* y, int ldy, int M,
                      int N, int K, int relu, void* stream);

@@ -9,6 +9,7 @@ from .mapf import adopt_bounded, audit_schedules, cbs_cases, ecbs_cases, ecbs_ca
 from .simulator import (GUIDANCE_MODES, BatchedEpisode, batched_fov_states, batched_gso, new_agent_view,  # noqa: F401
                         replayed_semi_states)
 from .memory import ExpertMemory, online_expert  # noqa: F401
+from .loss import ActionLoss, head_loss  # noqa: F401
 from .rollout import EpisodePool, evaluate_cases, reference_maxstep, summarize_rollouts  # noqa: F401
 
 __all__ = ["DecentralPlannerGATNet", "DecentralPlannerNet", "DecentralPlannerBottleneckNet", "GraphFilterBatchAttentional", "GraphFilterBatchAttentional_Origin", "GraphFilterBatchSimilarityAttentional", "GraphFilterBatch",
@@ -16,4 +17,4 @@ __all__ = ["DecentralPlannerGATNet", "DecentralPlannerNet", "DecentralPlannerBot
            "pack_schedules", "expert_schedule", "expert_radius", "expert_stats", "expert_samples", "flatten_samples",
            "plan_prioritized", "solve_cases", "solved_pack", "pack_cases", "improve_schedules", "audit_schedules", "certified", "certified_pack", "cbs_cases", "ecbs_cases", "ecbs_cases_wide", "adopt_bounded",
            "generate_cases", "valid_cases", "ExpertMemory", "online_expert",
-           "EpisodePool", "evaluate_cases", "reference_maxstep", "summarize_rollouts"]
+           "EpisodePool", "evaluate_cases", "reference_maxstep", "summarize_rollouts", "ActionLoss", "head_loss"]

@@ -20,7 +20,7 @@ _MODE_IDS = {"KeyQuery": MODE_KEYQUERY, "GAT_modified": MODE_GAT_MODIFIED, "GAT_
 TAGS = {0: "untagged", 1: "conv_first", 2: "layer1.conv1", 3: "layer1.conv2+ds", 4: "layer2.conv1",
         5: "layer2.conv2+ds", 6: "layer3.conv1", 7: "layer3.conv2+ds", 8: "head(avgpool+fc+linear)",
         9: "compressMLP", 10: "gat_maps_gemm", 11: "gat_graph", 12: "actionsMLP", 13: "head_mean",
-        14: "gat_pack", 15: "gso_prepare", 16: "gat_prepare", 17: "range_guard", 18: "layer1.conv2+layer2 (fused)", 19: "gat_layer (one launch)", 20: "gso_to_csr", 21: "gat_cast", 22: "layer3 (fused, pooled)", 23: "layer1.conv2+layer2+layer3 (fused, pooled)", 24: "conv_wgrad", 25: "gnn_dense", 26: "sim_guided", 27: "sim_expert", 28: "sim_mapf", 29: "sim_mapf_lns", 30: "sim_mapf_audit", 31: "sim_mapf_cbs", 32: "sim_mapf_ecbs"}
+        14: "gat_pack", 15: "gso_prepare", 16: "gat_prepare", 17: "range_guard", 18: "layer1.conv2+layer2 (fused)", 19: "gat_layer (one launch)", 20: "gso_to_csr", 21: "gat_cast", 22: "layer3 (fused, pooled)", 23: "layer1.conv2+layer2+layer3 (fused, pooled)", 24: "conv_wgrad", 25: "gnn_dense", 26: "sim_guided", 27: "sim_expert", 28: "sim_mapf", 29: "sim_mapf_lns", 30: "sim_mapf_audit", 31: "sim_mapf_cbs", 32: "sim_mapf_ecbs", 33: "head_loss"}
 TAG_ACTIONS = 12
 # magat_form_count ids (include/magat_hip.h MAGAT_FORM_*)
 FORMS = {"head_longk": 0, "head_splitk": 1, "gat_pack": 2, "gat_persist": 3, "gat_hsplit": 4, "chain_persist": 5,
@@ -34,6 +34,7 @@ TAG_SIM_MAPF_LNS = 29
 TAG_SIM_MAPF_AUDIT = 30
 TAG_SIM_MAPF_CBS = 31
 TAG_SIM_MAPF_ECBS = 32
+TAG_HEAD_LOSS = 33
 GUIDE_LOCAL, GUIDE_GLOBAL, GUIDE_SEMI = 1, 2, 3      # include/magat_hip.h MAGAT_GUIDE_*
 
 _lock = threading.Lock()
@@ -181,6 +182,10 @@ _SIGNATURES = {
     "magat_bn_train_workspace_floats": (_Z, [ctypes.c_longlong, _I]),
     "magat_bn_train_forward_f32": (_I, [_P, _P, ctypes.c_longlong, _I, _P, _P, _P, _P, ctypes.c_float, ctypes.c_float, _I, _P, _P, _P, _P]),
     "magat_bn_train_backward_f32": (_I, [_P, _P, _P, _P, ctypes.c_longlong, _I, _P, _P, _P, _I, _P, _P, _P, _P]),
+    "magat_head_loss_workspace_floats": (_Z, [ctypes.c_longlong, _I]),
+    "magat_head_loss_forward_f32": (_I, [_P, _I, _P, _P, _P, _I, ctypes.c_float, _P, _P, _P, _P, _P, ctypes.c_longlong, _I, _P]),
+    "magat_head_loss_backward_f32": (_I, [_P, _P, _P, _I, _P, _P, _I, _P, _P, _P, ctypes.c_longlong, _I, _P]),
+    "magat_action_loss_f32": (_I, [_P, _I, _P, _I, ctypes.c_float, _P, _P, _P, _P, ctypes.c_longlong, _P]),
     "magat_linear_f32": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "magat_linear_tagged_f32": (_I, [_P, _I, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "magat_gat_set_debug_buffer": (_I, [_P]),

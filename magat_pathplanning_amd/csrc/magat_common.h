@@ -52,7 +52,8 @@ void magat_form_note(int id);      // which form a launch took (MAGAT_FORM_*; pr
 #define MAGAT_TAG_SIM_MAPF_AUDIT 30 // the audit of schedules: conflicts and the flowtime bound (sim_mapf_audit.hip, sim_mapf_audit_wide.hip)
 #define MAGAT_TAG_SIM_MAPF_CBS 31   // conflict-based search: the optimal expert (sim_mapf_cbs.hip)
 #define MAGAT_TAG_SIM_MAPF_ECBS 32  // bounded-suboptimal conflict-based search: focal search on both levels (sim_mapf_ecbs.hip)
-#define MAGAT_PROF_TAGS_TABLE 33
+#define MAGAT_TAG_HEAD_LOSS 33      // the action head's last Linear + loss, forward or backward, and the loss alone (head_loss.hip; one span per call)
+#define MAGAT_PROF_TAGS_TABLE 34
 #define MAGAT_FORM_SIM_MAPF_LNS 19  // magat_sim_mapf_improve launched its one-wave-per-case kernel
 #define MAGAT_FORM_SIM_MAPF_AUDIT 20  // magat_sim_mapf_audit or its wide form launched (one count per call)
 #define MAGAT_FORM_SIM_MAPF_CBS 21    // magat_sim_mapf_cbs launched its one-wave-per-case kernel
@@ -62,7 +63,7 @@ void magat_form_note(int id);      // which form a launch took (MAGAT_FORM_*; pr
 #define MAGAT_FORM_GAT_COS_TRAIN 25  // magat_gat_train_forward_cos_f32 launched (GAT_Similarity's training forward; one count per call)
 #define MAGAT_FORMS_TABLE 26
 static_assert(MAGAT_PROF_TAGS_ALL >= MAGAT_PROF_TAGS && MAGAT_FORMS_ALL >= MAGAT_FORMS, "internal tag / form tables");
-static_assert(MAGAT_PROF_TAGS_TABLE > MAGAT_TAG_SIM_MAPF_ECBS && MAGAT_PROF_TAGS_TABLE >= MAGAT_PROF_TAGS_ALL &&
+static_assert(MAGAT_PROF_TAGS_TABLE > MAGAT_TAG_HEAD_LOSS && MAGAT_PROF_TAGS_TABLE >= MAGAT_PROF_TAGS_ALL &&
               MAGAT_FORMS_TABLE > MAGAT_FORM_GAT_COS_TRAIN && MAGAT_FORMS_TABLE >= MAGAT_FORMS_ALL, "internal tag / form tables");
 
 // the move step with per-instance counters (sim_frontend.hip: sim_move_kernel), launched for the case pool's entries (sim_pool.hip)

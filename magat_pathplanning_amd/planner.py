@@ -19,7 +19,9 @@ Inference (eval / no_grad) runs entirely on the gfx950 kernels behind include/ma
   actionsMLP (+skip inputs) -> magat_conv_gemm_f32          (skip source as second K segment)
 Training (autograd on): the graph layer's forward AND backward run on HIP kernels (graphml._GatTrainFunction,
 _GnnTrainFunction), and so do the convolutions of the ResNet trunks (train_cnn.py: forward, input and weight gradients on the
-float32 matrix-core kernels); BatchNorm / ReLU / pooling and the MLPs train through torch ops on the GPU.
+float32 matrix-core kernels); BatchNorm / ReLU / pooling and the MLPs train through torch ops on the GPU.  training_loss()
+(opt-in) takes the last Linear of actionsMLP and the loss - cross-entropy or the reference's LabelSmoothing - to the kernels of
+loss.py.
 """
 import ctypes
 import hashlib
@@ -282,6 +284,10 @@ class _PlannerBase(nn.Module):
 
     # ------------------------------------------------------------------ training path (torch ops)
     def _forward_autograd(self, x, B, N):
+        return self.actionsMLP(self._head_input(x, B, N))
+
+    def _head_input(self, x, B, N):
+        """Everything of the training forward in front of actionsMLP -> its input rows (B*N, width)."""
         feat = convlayers_forward(self.ConvLayers, x)       # (ResNet trunks: HIP convolution kernels, train_cnn.py)
         feat = feat.view(feat.size(0), -1)
         comp = self.compressMLP(feat)
@@ -295,7 +301,50 @@ class _PlannerBase(nn.Module):
             shared = torch.cat((comp, shared), dim=1)
         elif self.skip == "skipAddGNN":
             shared = torch.add(comp, shared)
-        return self.actionsMLP(shared)
+        return shared
+
+    def training_loss(self, inputTensor, target, label_smoothing=None):
+        """(loss, logits) of one step of the reference's training loop, `logits = net(x); loss = self.loss(logits, target)`
+        (agents/decentralplannerlocal_OnlineExpert_GAT.py:103-107, 556-567), with the last Linear of actionsMLP and the loss on
+        the HIP kernels of loss.py.  Opt-in: net(x) followed by a torch loss behaves as it always did.
+
+        label_smoothing: None reads config.label_smoothing (missing or None there: 0).  0 is nn.CrossEntropyLoss() (a mean),
+        > 0 the reference's LabelSmoothing(5, s) (a sum) - see loss.head_loss.  target: (B*N,) indices or one-hot rows.
+        Training / autograd mode: the training forward up to the input of the LAST Linear of actionsMLP, then loss.head_loss
+        (`logits` comes back detached) - unless a Dropout with p > 0 in training mode follows that Linear (the use_dropout
+        form): then actionsMLP runs as it is and the loss is the torch composite.  Eval mode under no_grad: the HIP inference
+        forward, then loss.ActionLoss."""
+        from . import loss as hl
+        if label_smoothing is None:
+            label_smoothing = getattr(self.config, "label_smoothing", None) or 0.0
+        x, B, N = self._intake(inputTensor)
+        needs_grad = torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters())
+        if not (needs_grad or self.training):
+            logits = self._forward_hip(x, B, N)
+            return hl.ActionLoss(label_smoothing)(logits, target), logits
+        nat.require_device_or_composite(x, "%s in training / autograd mode" % type(self).__name__)
+        rows = self._head_input(x, B, N)
+        mods = list(self.actionsMLP)
+        last = max(i for i, m in enumerate(mods) if isinstance(m, nn.Linear))
+        idle = all(isinstance(m, nn.Dropout) and (m.p == 0 or not m.training) for m in mods[last + 1:])
+        if not idle or mods[last].out_features != hl.CLASSES:
+            logits = self.actionsMLP(rows)
+            return hl.loss_composite(logits, target, label_smoothing), logits
+        for m in mods[:last]:
+            rows = m(rows)
+        return hl.head_loss(rows, mods[last].weight, mods[last].bias, target, label_smoothing)
+
+    def _intake(self, inputTensor):
+        """forward()'s boundary checks (kept inline there: every closed-loop step runs them) -> (x (B*N, 3, W, H), B, N)"""
+        (B, N, C, W, H) = inputTensor.shape
+        x = inputTensor.reshape(B * N, C, W, H).to(torch.device(self.config.device))
+        if self.S is None:
+            raise TypeError("addGSO must be called before forward")
+        side = self.config.FOV + 2
+        if (C, W, H) != (3, side, side):
+            raise RuntimeError("%s built for (3, %d, %d) state maps (config.FOV + 2), got (%d, %d, %d)"
+                               % (type(self).__name__, side, side, C, W, H))
+        return x, B, N
 
     # ------------------------------------------------------------------ inference path (HIP)
     def _walk_dicts(self):
@@ -995,6 +1044,11 @@ class DecentralPlannerBottleneckNet(DecentralPlannerNet):
                             "decentralplanner_bottleneck_SkipAddGNN.py:311 (torch.cat(compressfeature, sharedFeature_stack): "
                             "cat() expects a sequence of tensors); construction and load_state_dict work, forward does not")
         return super().forward(inputTensor)
+
+    def training_loss(self, inputTensor, target, label_smoothing=None):
+        if self.skip == "skipAddGNN":
+            return self.forward(inputTensor)      # (raises: the refusal above)
+        return super().training_loss(inputTensor, target, label_smoothing)
 
     @torch.no_grad()
     def _forward_hip(self, x, B, N):
