@@ -24,6 +24,9 @@
 // the two columns; the other cells: the two rows): feat / comp are BIT-IDENTICAL to the batched kernels' - a planning instance
 // alone and as rows of a 6 400-agent batch give the same logits bit for bit (tests/test_gpu_latency.py).
 #include "magat_common.h"
+#include "encoder_pack.h"
+
+namespace enc = magat_enc;
 
 namespace {
 #include "block_walk.h"
@@ -59,7 +62,7 @@ struct LatParams {
   // GUARD (HEAD only): the encoder's range guard inside this launch - raw state maps, float32 BN-folded weights (encoder pack
   // offsets 0..17), the status block of the workspace (book[0] working flag, [1] re-run count, [2] this forward's flag, [6]
   // arrival counter); null = the guard's predicated launches follow as for every other form
-  const float* x; const float* pk; long long off[18]; int* book;
+  const float* x; const float* pk; long long off[enc::F32_SLOTS]; int* book;
   // STEM: stem weights [32][27] + bias (x the activation scale when folded), layer1.conv1 fragment-major + its bias
   const float* w0; const float* b0; const char* w1f; const float* b1c;
   long long* dbg;      // MAGAT_DEBUG_HOOKS builds: [grid][4 waves][16] cycle stamps (tools/lat_phase_probe.py)
@@ -262,8 +265,8 @@ __device__ void lat_fallback_f32(const LatParams& p, int m, float* L) {
   // stem: conv3x3(3 -> 32, pad 1) + BN + ReLU on 11 x 11; weights [32][c 9 + ty 3 + tx]
   for (int idx = t; idx < 32 * 121; idx += 256) {
     const int co = idx / 121, px = idx - 121 * co, oy = px / 11, ox = px - 11 * oy;
-    const float* wr = pk + p.off[0] + co * 27;
-    float acc = pk[p.off[1] + co];
+    const float* wr = pk + p.off[enc::STEM_W] + co * 27;
+    float acc = pk[p.off[enc::STEM_B] + co];
     for (int c = 0; c < 3; ++c)
       for (int ty = 0; ty < 3; ++ty) {
         const int iy = oy + ty - 1;
@@ -278,17 +281,17 @@ __device__ void lat_fallback_f32(const LatParams& p, int m, float* L) {
   }
   __syncthreads();
   // layer1: conv1 stride 2, conv2 + downsample (1 x 1, stride 2, over the stem map)
-  lat_conv_f32(A0, 32, 11, 2, pk + p.off[2], 288, pk + p.off[3], nullptr, 0, 1, 1, B1, 32);
+  lat_conv_f32(A0, 32, 11, 2, pk + p.off[enc::conv1_w(0)], 288, pk + p.off[enc::conv1_b(0)], nullptr, 0, 1, 1, B1, 32);
   __syncthreads();
-  lat_conv_f32(B1, 32, 6, 1, pk + p.off[4], 288 + 32, pk + p.off[5], A0, 32, 11, 2, Y1, 32);
+  lat_conv_f32(B1, 32, 6, 1, pk + p.off[enc::conv2_w(0)], 288 + 32, pk + p.off[enc::conv2_b(0)], A0, 32, 11, 2, Y1, 32);
   __syncthreads();
-  lat_conv_f32(Y1, 32, 6, 1, pk + p.off[6], 288, pk + p.off[7], nullptr, 0, 1, 1, B2, 64);
+  lat_conv_f32(Y1, 32, 6, 1, pk + p.off[enc::conv1_w(1)], 288, pk + p.off[enc::conv1_b(1)], nullptr, 0, 1, 1, B2, 64);
   __syncthreads();
-  lat_conv_f32(B2, 64, 6, 1, pk + p.off[8], 576 + 32, pk + p.off[9], Y1, 32, 6, 1, Y2, 64);
+  lat_conv_f32(B2, 64, 6, 1, pk + p.off[enc::conv2_w(1)], 576 + 32, pk + p.off[enc::conv2_b(1)], Y1, 32, 6, 1, Y2, 64);
   __syncthreads();
-  lat_conv_f32(Y2, 64, 6, 1, pk + p.off[10], 576, pk + p.off[11], nullptr, 0, 1, 1, B3, 128);
+  lat_conv_f32(Y2, 64, 6, 1, pk + p.off[enc::conv1_w(2)], 576, pk + p.off[enc::conv1_b(2)], nullptr, 0, 1, 1, B3, 128);
   __syncthreads();
-  lat_conv_f32(B3, 128, 6, 1, pk + p.off[12], 1152 + 64, pk + p.off[13], Y2, 64, 6, 1, Y3, 128);
+  lat_conv_f32(B3, 128, 6, 1, pk + p.off[enc::conv2_w(2)], 1152 + 64, pk + p.off[enc::conv2_b(2)], Y2, 64, 6, 1, Y3, 128);
   __syncthreads();
   // AvgPool2d(2) as a sum (the 1/4 lives in the head's weights) -> [cell][channel]
   for (int idx = t; idx < 9 * 128; idx += 256) {
@@ -298,16 +301,16 @@ __device__ void lat_fallback_f32(const LatParams& p, int m, float* L) {
   }
   __syncthreads();
   if (t < 128) {      // head: fc (+ Flatten + Linear) folded, [n_feat][cell 128 + c]
-    const float* wr = pk + p.off[14] + (long long)t * 1152;
-    float acc = pk[p.off[15] + t];
+    const float* wr = pk + p.off[enc::HEAD_W] + (long long)t * 1152;
+    float acc = pk[p.off[enc::HEAD_B] + t];
     for (int k = 0; k < 1152; ++k) acc = __builtin_fmaf(wr[k], PL[k], acc);
     FT[t] = acc;
     p.feat[(long long)m * p.ldfeat + t] = acc;
   }
   __syncthreads();
   if (t < p.ncomp) {      // compressMLP
-    const float* wr = pk + p.off[16] + (long long)t * 128;
-    float acc = pk[p.off[17] + t];
+    const float* wr = pk + p.off[enc::COMP_W] + (long long)t * 128;
+    float acc = pk[p.off[enc::COMP_B] + t];
     for (int k = 0; k < 128; ++k) acc = __builtin_fmaf(wr[k], FT[k], acc);
     p.comp[(long long)m * p.ldcomp + t] = magat_relu(acc);
   }
@@ -736,12 +739,12 @@ int magat_block_lat(const void* in1, const void* in2, const float* wchain, const
 #ifdef MAGAT_DEBUG_HOOKS
   p.dbg = g_lat_dbg;
 #endif
-  for (int i = 0; i < 18; ++i) p.off[i] = 0;
+  for (int i = 0; i < enc::F32_SLOTS; ++i) p.off[i] = 0;
   if (guard) {
     if (!head) return MAGAT_ERR_UNSUPPORTED;
     if (!guard->x || !guard->pack || !guard->off || !guard->book) return MAGAT_ERR_NULL;
     p.x = guard->x; p.pk = guard->pack; p.book = guard->book;
-    for (int i = 0; i < 18; ++i) p.off[i] = guard->off[i];
+    for (int i = 0; i < enc::F32_SLOTS; ++i) p.off[i] = guard->off[i];
     magat_form_note(MAGAT_FORM_GUARD_LAT);
   }
   p.w0 = p.b0 = p.b1c = nullptr; p.w1f = nullptr;

@@ -25,6 +25,27 @@ import torch
 
 BN_EPS = 1e-5
 
+# The slots of the offsets list (magat_encoder_desc.off[]) and the layout of the activation-scale block.  csrc/encoder_pack.h names the
+# same numbers for the kernels' side; tests/test_host_encoder_route.py holds the two against each other.
+SLOT_STEM_W, SLOT_STEM_B = 0, 1
+SLOT_HEAD_W, SLOT_HEAD_B, SLOT_COMP_W, SLOT_COMP_B = 14, 15, 16, 17
+F32_SLOTS = 18                     # slots 0 .. 17: the float32 BN-folded weights
+SLOT_PERMUTED, SLOT_TILE16, SLOTS = 30, 31, 32
+
+
+def slot_conv1_w(l): return 2 + 4 * l         # BasicBlock l = 0..2
+def slot_conv1_b(l): return 3 + 4 * l
+def slot_conv2_w(l): return 4 + 4 * l         # [conv2 | downsample]
+def slot_conv2_b(l): return 5 + 4 * l
+def slot_conv1_f16(l): return 24 + 2 * l      # the same two weights as f16x2 planes
+def slot_conv2_f16(l): return 25 + 2 * l
+def slot_plain_w(i): return 2 + 2 * i         # the plain CNNs: conv i + 1, i = 0..3
+def slot_plain_b(i): return 3 + 2 * i
+
+
+SC_W0, SC_B0, SC_B1, SC_BA, SC_BB, SC_BC, SC_B31, SC_B32 = 0, 864, 896, 928, 960, 1024, 1088, 1216
+SC_SCALES, SC_HEAD_IN, SC_FEAT_IN, SC_FLOATS = 1344, 1349, 1350, 1352
+
 
 def _bn_scale_shift(sd, pre):
     s = sd[pre + ".weight"].double() / torch.sqrt(sd[pre + ".running_var"].double() + BN_EPS)
@@ -42,7 +63,7 @@ def fold_resnet(sd, H=11, W=11, pre="ConvLayers.0", linear=None, compress=None):
     else None.  compress = (weight, bias) of compressMLP.0 or None.
     Returns (pack float32 1-D CPU tensor, offsets list[32], meta dict)."""
     sd = {k: v.detach().cpu() for k, v in sd.items() if k.startswith(pre)}
-    parts, offs = [], [0] * 32
+    parts, offs = [], [0] * SLOTS
     cursor = [0]
 
     def put(slot, t):
@@ -55,8 +76,8 @@ def fold_resnet(sd, H=11, W=11, pre="ConvLayers.0", linear=None, compress=None):
         cursor[0] += t.numel()
 
     s, b = _bn_scale_shift(sd, pre + ".bn1")
-    put(0, sd[pre + ".conv1.weight"].double().reshape(32, 27) * s.view(-1, 1))
-    put(1, b)
+    put(SLOT_STEM_W, sd[pre + ".conv1.weight"].double().reshape(32, 27) * s.view(-1, 1))
+    put(SLOT_STEM_B, b)
     large = (pre + ".layer3.0.conv1.weight") in sd
     nblocks = 3 if large else 2
     clast = 32
@@ -65,8 +86,8 @@ def fold_resnet(sd, H=11, W=11, pre="ConvLayers.0", linear=None, compress=None):
         w1 = sd[bp + ".conv1.weight"]
         cout, cin = w1.shape[0], w1.shape[1]
         s1, b1 = _bn_scale_shift(sd, bp + ".bn1")
-        put(2 + 4 * l, _conv_rows(w1, s1))
-        put(3 + 4 * l, b1)
+        put(slot_conv1_w(l), _conv_rows(w1, s1))
+        put(slot_conv1_b(l), b1)
         s2, b2 = _bn_scale_shift(sd, bp + ".bn2")
         w2 = _conv_rows(sd[bp + ".conv2.weight"], s2)
         if (bp + ".downsample.0.weight") in sd:
@@ -74,8 +95,8 @@ def fold_resnet(sd, H=11, W=11, pre="ConvLayers.0", linear=None, compress=None):
             wd = sd[bp + ".downsample.0.weight"].double().reshape(cout, cin) * sdn.view(-1, 1)
         else:
             wd, bdn = torch.eye(cout, cin, dtype=torch.float64), torch.zeros(cout, dtype=torch.float64)
-        put(4 + 4 * l, torch.cat((w2, wd), dim=1))
-        put(5 + 4 * l, b2 + bdn)
+        put(slot_conv2_w(l), torch.cat((w2, wd), dim=1))
+        put(slot_conv2_b(l), b2 + bdn)
         clast = cout
     Ho, Wo = (H + 2 - 3) // 2 + 1, (W + 2 - 3) // 2 + 1
     Hp, Wp = Ho // 2, Wo // 2
@@ -94,12 +115,12 @@ def fold_resnet(sd, H=11, W=11, pre="ConvLayers.0", linear=None, compress=None):
         W2 = torch.einsum("qc,abyx->qabyxc", fc, eye).reshape(nq * Hp * Wp, Hp, Wp, clast)
         b2 = fcb.repeat_interleave(Hp * Wp)
         n_feat = nq * Hp * Wp
-    put(14, 0.25 * W2)      # the kernel sum-pools 2x2 on load; the 1/4 lives here
-    put(15, b2)
+    put(SLOT_HEAD_W, 0.25 * W2)      # the kernel sum-pools 2x2 on load; the 1/4 lives here
+    put(SLOT_HEAD_B, b2)
     n_comp = 0
     if compress is not None:
-        put(16, compress[0].detach().cpu().double())
-        put(17, compress[1].detach().cpu().double())
+        put(SLOT_COMP_W, compress[0].detach().cpu().double())
+        put(SLOT_COMP_B, compress[1].detach().cpu().double())
         n_comp = compress[0].shape[0]
     pack = torch.cat(parts).to(torch.float32).contiguous()
     if True:
@@ -110,7 +131,7 @@ def fold_resnet(sd, H=11, W=11, pre="ConvLayers.0", linear=None, compress=None):
         n_f32 = pack.numel()
         pairs = []
         for l in range(nblocks):
-            pairs += [(18 + 2 * l, 2 + 4 * l), (19 + 2 * l, 4 + 4 * l)]
+            pairs += [(slot_conv1_f16(l), slot_conv1_w(l)), (slot_conv2_f16(l), slot_conv2_w(l))]
         # As f16x2 planes of the power-of-two-scaled weights followed by the inverse scale ("f16x3" GEMM, in_fmt 4):
         # off[24+2l] = layer(l+1).conv1, off[25+2l] = [conv2|downsample]
         # Each f16 block is followed by a second copy with the K columns of every 32-wide slab permuted for activations
@@ -120,14 +141,14 @@ def fold_resnet(sd, H=11, W=11, pre="ConvLayers.0", linear=None, compress=None):
         perm32 = torch.tensor([16 * (q >> 4) + 8 * ((q & 7) >> 2) + 4 * ((q >> 3) & 1) + (q & 3) for q in range(32)])
         couts = [32, 32, 64, 64, 128, 128]
         for (slot, src), cout in zip(pairs, couts):
-            nxt = sorted(o for o in offs[:18] if o > offs[src])
+            nxt = sorted(o for o in offs[:F32_SLOTS] if o > offs[src])
             end = nxt[0] if nxt else n_f32
             w32 = pack[offs[src]:end]
             blk, _ = split_f16x2(w32)
             pad = (-blk.numel()) % 4
             if pad:
                 blk = torch.cat((blk, torch.zeros(pad)))
-            offs[slot + 6] = cursor_f
+            offs[slot] = cursor_f
             cursor_f += blk.numel()
             raws.append(blk)
             w2d = w32.reshape(cout, -1)
@@ -141,32 +162,32 @@ def fold_resnet(sd, H=11, W=11, pre="ConvLayers.0", linear=None, compress=None):
             cursor_f += blk2.numel()
             raws.append(blk2)
             if slot == pairs[0][0]:
-                offs[30] = offs[slot + 6] + blk.numel()        # first permuted copy (non-zero = copies present)
+                offs[SLOT_PERMUTED] = offs[slot] + blk.numel()        # first permuted copy (non-zero = copies present)
         pack = torch.cat([pack] + raws).contiguous()
     # BasicBlock chain kernel (csrc/block_fused.hip; 6x6 maps only, i.e. the reference's 11x11 input): layer1.conv2+ds,
     # layer2.conv1, layer2.conv2+ds as fragment-major f16 planes, appended to the pack; its float offset goes to meta["chain"]
     chain_off = 0
     if Ho == 6 and Wo == 6 and nblocks >= 2:
         def rows(slot, cout):
-            nxt = sorted(o for o in offs[:18] if o > offs[slot])
+            nxt = sorted(o for o in offs[:F32_SLOTS] if o > offs[slot])
             return pack[offs[slot]:(nxt[0] if nxt else n_f32)].reshape(cout, -1)
-        blocks = [pack_chain_weights(rows(4, 32)[:, :9 * 32 + 32], 32, 32),
-                  pack_chain_weights(rows(6, 64)[:, :9 * 32], 32, 0),
-                  pack_chain_weights(rows(8, 64)[:, :9 * 64 + 32], 64, 32)]
+        blocks = [pack_chain_weights(rows(slot_conv2_w(0), 32)[:, :9 * 32 + 32], 32, 32),
+                  pack_chain_weights(rows(slot_conv1_w(1), 64)[:, :9 * 32], 32, 0),
+                  pack_chain_weights(rows(slot_conv2_w(1), 64)[:, :9 * 64 + 32], 64, 32)]
         chain_off = pack.numel()
         pack = torch.cat([pack] + blocks).contiguous()
     chain3_off = 0
     if chain_off and large:
         def rows3(slot):
-            nxt = sorted(o for o in offs[:18] if o > offs[slot])
+            nxt = sorted(o for o in offs[:F32_SLOTS] if o > offs[slot])
             return pack[offs[slot]:(nxt[0] if nxt else n_f32)].reshape(128, -1)
         chain3_off = pack.numel()
-        blocks3 = pack_block3_weights(rows3(10)[:, :9 * 64], rows3(12)[:, :9 * 128 + 64])
+        blocks3 = pack_block3_weights(rows3(slot_conv1_w(2))[:, :9 * 64], rows3(slot_conv2_w(2))[:, :9 * 128 + 64])
         pack = torch.cat([pack] + blocks3).contiguous()
     # the head once more as f16x2 planes (in_fmt 4): with the layer3 kernel's pooled output the head is a plain valid conv
     # over the pooled map, 5x faster on the split-MFMA kernel than on the float32 matrix cores
-    nxt = sorted(o for o in offs[:18] if o > offs[14])
-    head16, _ = split_f16x2(pack[offs[14]:(nxt[0] if nxt else n_f32)])
+    nxt = sorted(o for o in offs[:F32_SLOTS] if o > offs[SLOT_HEAD_W])
+    head16, _ = split_f16x2(pack[offs[SLOT_HEAD_W]:(nxt[0] if nxt else n_f32)])
     pad = (-head16.numel()) % 4
     if pad:
         head16 = torch.cat((head16, torch.zeros(pad)))
@@ -175,7 +196,7 @@ def fold_resnet(sd, H=11, W=11, pre="ConvLayers.0", linear=None, compress=None):
     # ... and compressMLP's weight the same way (it follows the head on the same kernel)
     comp16_off = 0
     if n_comp > 0:
-        comp16, _ = split_f16x2(pack[offs[16]:offs[16] + n_comp * n_feat])
+        comp16, _ = split_f16x2(pack[offs[SLOT_COMP_W]:offs[SLOT_COMP_W] + n_comp * n_feat])
         pad = (-comp16.numel()) % 4
         if pad:
             comp16 = torch.cat((comp16, torch.zeros(pad)))
@@ -186,27 +207,27 @@ def fold_resnet(sd, H=11, W=11, pre="ConvLayers.0", linear=None, compress=None):
     # order a wave fetches them - no weight slab through LDS there, 1 KB blocks straight into registers
     headfrag_off = compfrag_off = 0
     if chain3_off and n_comp in (32, 64, 128) and n_feat == 128 and clast == 128 and Hp * Wp == 9:
-        nxt = sorted(o for o in offs[:18] if o > offs[14])
-        hrows = pack[offs[14]:(nxt[0] if nxt else n_f32)].reshape(n_feat, Hp * Wp * clast)
+        nxt = sorted(o for o in offs[:F32_SLOTS] if o > offs[SLOT_HEAD_W])
+        hrows = pack[offs[SLOT_HEAD_W]:(nxt[0] if nxt else n_f32)].reshape(n_feat, Hp * Wp * clast)
         # k steps in the long-K head's order (conv_gemm_bf16x6.hip direct kernel, korder 1): 32-channel slab outer, pooled cell
         # inner, two 16-channel k steps per (slab, cell)
         hsteps = [cell * clast + 32 * cs + 16 * ks for cs in range(clast // 32) for cell in range(Hp * Wp) for ks in range(2)]
         headfrag_off = pack.numel()
         pack = torch.cat([pack, pack_frag_natural(hrows, hsteps)]).contiguous()
-        crows = pack[offs[16]:offs[16] + n_comp * n_feat].reshape(n_comp, n_feat)
+        crows = pack[offs[SLOT_COMP_W]:offs[SLOT_COMP_W] + n_comp * n_feat].reshape(n_comp, n_feat)
         compfrag_off = pack.numel()
         pack = torch.cat([pack, pack_frag_natural(crows, [16 * ks for ks in range(n_feat // 16)])]).contiguous()
     # layer1.conv1 fragment-major for the eight-agent-group stem kernel (csrc/block_fused.hip stem8_kernel; 11x11 maps)
     l1frag_off = 0
     if H == 11 and W == 11:
-        nxt = sorted(o for o in offs[:18] if o > offs[2])
-        w1rows = pack[offs[2]:(nxt[0] if nxt else n_f32)][:32 * 288].reshape(32, 288)
+        nxt = sorted(o for o in offs[:F32_SLOTS] if o > offs[slot_conv1_w(0)])
+        w1rows = pack[offs[slot_conv1_w(0)]:(nxt[0] if nxt else n_f32)][:32 * 288].reshape(32, 288)
         l1frag_off = pack.numel()
         pack = torch.cat([pack, pack_chain_weights(w1rows, 32, 0)]).contiguous()
     # layer3.conv2 once more in 16-row fragments, for the large-batch form of the one-launch chain kernel (option CHAIN_TILE16);
     # offs[31] != 0 marks their presence (magat_encoder_desc.off[31])
     if chain3_off:
-        offs[31] = pack.numel()
+        offs[SLOT_TILE16] = pack.numel()
         pack = torch.cat([pack, pack_block3_tile16(blocks3)]).contiguous()
     meta = dict(variant=0 if large else 1, H=H, W=W, n_feat=n_feat, n_comp=n_comp, clast=clast, chain=chain_off,
                 chain3=chain3_off, head16=head16_off, comp16=comp16_off, l1frag=l1frag_off, headfrag=headfrag_off,
@@ -214,7 +235,7 @@ def fold_resnet(sd, H=11, W=11, pre="ConvLayers.0", linear=None, compress=None):
     return pack, offs, meta
 
 
-SCALED_BLOCK_FLOATS = 1352      # magat_hip.h magat_encoder_desc.scaled_off
+SCALED_BLOCK_FLOATS = SC_FLOATS      # magat_hip.h magat_encoder_desc.scaled_off
 
 
 def scale_exponent(m, target_log2=10, lo=-14, hi=24):
@@ -235,7 +256,8 @@ def fold_activation_scales(pack, offs, meta, absmax):
     s1 = scale_exponent(max(a[0], a[1]))
     # the stem's INPUT is not scaled (binary state maps): its scale rides in the stem weights, which the fused stem kernel
     # splits into f16 planes of 16 w - keep 16 w 2^s1 inside the planes' range whatever the calibration batch looked like
-    w0max = float(max(pack[offs[0]:offs[0] + 864].abs().max(), pack[offs[1]:offs[1] + 32].abs().max()))
+    w0max = float(max(pack[offs[SLOT_STEM_W]:offs[SLOT_STEM_W] + 864].abs().max(),
+                      pack[offs[SLOT_STEM_B]:offs[SLOT_STEM_B] + 32].abs().max()))
     if w0max > 0.0:
         s1 = min(s1, 15 - 4 - int(math.ceil(math.log2(w0max))))
     s2 = scale_exponent(max(a[2], a[3]))
@@ -247,26 +269,26 @@ def fold_activation_scales(pack, offs, meta, absmax):
     def seg(slot, n):
         return pack[offs[slot]:offs[slot] + n].double()
     blk = torch.zeros(SCALED_BLOCK_FLOATS, dtype=torch.float64)
-    blk[0:864] = seg(0, 864) * f(s1)
-    blk[864:896] = seg(1, 32) * f(s1)
-    blk[896:928] = seg(3, 32) * f(s1)            # layer1.conv1 bias (its 1 / weight-scale is unchanged: in and out share s1)
-    blk[928:960] = seg(5, 32) * f(s2)            # stage A  (layer1.conv2 + downsample): s1 -> s2
-    blk[960:1024] = seg(7, 64) * f(s2)           # stage B  (layer2.conv1)
-    blk[1024:1088] = seg(9, 64) * f(s3)          # stage C  (layer2.conv2 + downsample): s2 -> s3
-    blk[1088:1216] = seg(11, 128) * f(s3)        # layer3.conv1
-    blk[1216:1344] = seg(13, 128)                # layer3.conv2 + downsample: s3 -> true scale
+    blk[SC_W0:SC_B0] = seg(SLOT_STEM_W, 864) * f(s1)
+    blk[SC_B0:SC_B1] = seg(SLOT_STEM_B, 32) * f(s1)
+    blk[SC_B1:SC_BA] = seg(slot_conv1_b(0), 32) * f(s1)            # layer1.conv1 bias (its 1 / weight-scale is unchanged: in and out share s1)
+    blk[SC_BA:SC_BB] = seg(slot_conv2_b(0), 32) * f(s2)            # stage A  (layer1.conv2 + downsample): s1 -> s2
+    blk[SC_BB:SC_BC] = seg(slot_conv1_b(1), 64) * f(s2)           # stage B  (layer2.conv1)
+    blk[SC_BC:SC_B31] = seg(slot_conv2_b(1), 64) * f(s3)          # stage C  (layer2.conv2 + downsample): s2 -> s3
+    blk[SC_B31:SC_B32] = seg(slot_conv1_b(2), 128) * f(s3)        # layer3.conv1
+    blk[SC_B32:SC_SCALES] = seg(slot_conv2_b(2), 128)                # layer3.conv2 + downsample: s3 -> true scale
     ch, c3 = meta["chain"], meta["chain3"]
     nA, nB, nC = 10240, 18432, 38912             # floats of the three chain weight blocks (block_fused.hip chain_block_bytes)
     n1, n2a, n2b = 73728, 73728, 81920
     sA, sB, sC = float(pack[ch + nA]), float(pack[ch + nA + 4 + nB]), float(pack[ch + nA + 4 + nB + 4 + nC])
     s31, s32 = float(pack[c3 + n1]), float(pack[c3 + n1 + 4 + n2a + 4 + n2b])
-    blk[1344] = sA * f(s2 - s1)
-    blk[1345] = sB
-    blk[1346] = sC * f(s3 - s2)
-    blk[1347] = s31
-    blk[1348] = s32 * f(-s3)
-    blk[1349] = f(e_head)
-    blk[1350] = f(e_feat)
+    blk[SC_SCALES + 0] = sA * f(s2 - s1)
+    blk[SC_SCALES + 1] = sB
+    blk[SC_SCALES + 2] = sC * f(s3 - s2)
+    blk[SC_SCALES + 3] = s31
+    blk[SC_SCALES + 4] = s32 * f(-s3)
+    blk[SC_HEAD_IN] = f(e_head)
+    blk[SC_FEAT_IN] = f(e_feat)
     return blk.to(torch.float32), dict(s1=s1, s2=s2, s3=s3, head_in=e_head, feat_in=e_feat)
 
 
@@ -418,7 +440,7 @@ def fold_default_cnn(sd, H=11, W=11, pre="ConvLayers", compress=None):
     leaves at least one cell (H, W >= 8): the features are 128 * hf * wf wide, (cell, channel)-ordered in the kernels'
     buffers, and the compressMLP columns are permuted here to read them (meta["cells"] = (hf, wf) for other readers)."""
     sd = {k: v.detach().cpu() for k, v in sd.items() if k.startswith(pre)}
-    parts, offs, cursor = [], [0] * 32, [0]
+    parts, offs, cursor = [], [0] * SLOTS, [0]
     hf, wf = default_cnn_cells(H, W)
     if hf < 1 or wf < 1:
         raise ValueError("CNN_mode Default needs maps of at least 8 x 8 (three MaxPool2d(2)); got %d x %d" % (H, W))
@@ -441,19 +463,19 @@ def fold_default_cnn(sd, H=11, W=11, pre="ConvLayers", compress=None):
         s, sh = _bn_scale_shift(sd, "%s.%d" % (pre, ci + 1))
         bias = b * s + sh
         if l == 0:
-            put(0, w.reshape(32, 27) * s.view(-1, 1))
-            put(1, bias)
+            put(SLOT_STEM_W, w.reshape(32, 27) * s.view(-1, 1))
+            put(SLOT_STEM_B, bias)
         else:
-            put(2 + 2 * (l - 1), _conv_rows(w, s))
-            put(3 + 2 * (l - 1), bias)
-    put(14, torch.eye(128, dtype=torch.float64))
+            put(slot_plain_w(l - 1), _conv_rows(w, s))
+            put(slot_plain_b(l - 1), bias)
+    put(SLOT_HEAD_W, torch.eye(128, dtype=torch.float64))
     n_comp = 0
     n_feat = 128 * hf * wf
     if compress is not None:
         cw = compress[0].detach().cpu().double()
         assert cw.shape[1] == n_feat, "compressMLP in_features must equal 128 * pooled cells"
-        put(16, cell_major_columns(cw, hf, wf))
-        put(17, compress[1].detach().cpu().double())
+        put(SLOT_COMP_W, cell_major_columns(cw, hf, wf))
+        put(SLOT_COMP_B, compress[1].detach().cpu().double())
         n_comp = compress[0].shape[0]
     pack = torch.cat(parts).to(torch.float32).contiguous()
     return pack, offs, dict(variant=2, H=H, W=W, n_feat=n_feat, n_comp=n_comp, clast=128, cells=(hf, wf))
@@ -479,7 +501,7 @@ def fold_dilated_cnn(sd, version, H=11, W=11, pre="ConvLayers", compress=None):
     chans = spec["chans"]
     nl = len(chans) - 1
     sd = {k: v.detach().cpu() for k, v in sd.items() if k.startswith(pre)}
-    parts, offs, cursor = [], [0] * 32, [0]
+    parts, offs, cursor = [], [0] * SLOTS, [0]
     hf, wf = dilated_cnn_cells(H, W)
     if hf < 1 or wf < 1:
         raise ValueError("the dilated CNNs need maps of at least 4 x 4; got %d x %d" % (H, W))
@@ -499,20 +521,20 @@ def fold_dilated_cnn(sd, version, H=11, W=11, pre="ConvLayers", compress=None):
         s_, sh = _bn_scale_shift(sd, "%s.%d" % (pre, idx + 1))
         bias = b * s_ + sh
         if l == 0:
-            put(0, w.reshape(32, 27) * s_.view(-1, 1))
-            put(1, bias)
+            put(SLOT_STEM_W, w.reshape(32, 27) * s_.view(-1, 1))
+            put(SLOT_STEM_B, bias)
         else:
-            put(2 + 2 * (l - 1), _conv_rows(w, s_))
-            put(3 + 2 * (l - 1), bias)
+            put(slot_plain_w(l - 1), _conv_rows(w, s_))
+            put(slot_plain_b(l - 1), bias)
         idx += 3 + (1 if l in (1, 3) else 0)
     clast = chans[-1]
-    put(14, torch.eye(clast, dtype=torch.float64))
+    put(SLOT_HEAD_W, torch.eye(clast, dtype=torch.float64))
     n_feat, n_comp = clast * hf * wf, 0
     if compress is not None:
         cw = compress[0].detach().cpu().double()
         assert cw.shape[1] == n_feat, "compressMLP in_features must equal clast * pooled cells"
-        put(16, cell_major_columns(cw, hf, wf, c=clast))
-        put(17, compress[1].detach().cpu().double())
+        put(SLOT_COMP_W, cell_major_columns(cw, hf, wf, c=clast))
+        put(SLOT_COMP_B, compress[1].detach().cpu().double())
         n_comp = compress[0].shape[0]
     pack = torch.cat(parts).to(torch.float32).contiguous()
     return pack, offs, dict(variant=spec["variant"], H=H, W=W, n_feat=n_feat, n_comp=n_comp, clast=clast, cells=(hf, wf))
