@@ -27,6 +27,7 @@
 
 #include "magat_common.h"
 #include "gat_pack.h"
+#include "gat_route.h"
 #include "skinny_rows.h"
 
 namespace {
@@ -1015,8 +1016,6 @@ __global__ __launch_bounds__(256) void gat_rerun_small_kernel(const GatParams p,
   if (p.book) magat_guard_book(p.book);
 }
 
-constexpr long long GAT_RERUN_SMALL_UNITS = 64;      // instances x heads up to which the re-run is this one launch
-
 
 // mean over heads then ReLU (graphML.py:4663-4667)
 __global__ void head_mean_relu_kernel(const float* __restrict__ ytmp, float* __restrict__ y, long long M, int P,
@@ -1084,32 +1083,6 @@ __global__ __launch_bounds__(256) void gat_cos_prepare_kernel(const float* __res
 
 long long* g_gat_dbg = nullptr;   // see magat_gat_set_debug_buffer
 
-size_t gat_lds_bytes(int N, int G, int F, int nwaves) {
-  const int RW = G > F ? G : F;
-  const int lda = N | 1;
-  return sizeof(float) * (2 * (size_t)N * RW + (size_t)N * lda + 2 * ((N + 3) & ~3)) +
-         sizeof(int) * 128 * (size_t)nwaves + sizeof(unsigned) * 4 * (size_t)N + 16;
-}
-
-int gat_block_threads(int N) {
-  if (N <= 16) return 128;
-  if (N <= 32) return 256;
-  if (N <= 64) return 512;
-  return 1024;
-}
-
-// instances per chunk: bounds the hoisted-map intermediate Z (chunk*N*NC floats).  Measured on MI355X
-// (c3, B=512): one big launch beats Infinity-Cache-sized chunks (2.02 TB/s vs 1.85 @96 MB vs 1.23 @32 MB),
-// so the cap only limits workspace (default 2 GiB).
-int gat_chunk_instances(int B, int N, int NC) {
-  const double mb = (double)magat_opt(MAGAT_OPT_GAT_CHUNK_MB);
-  long long per = (long long)N * NC * 4;
-  long long c = (long long)(mb * 1048576.0) / (per > 0 ? per : 1);
-  if (c < 8) c = 8;
-  if (c > B) c = B;
-  return (int)c;
-}
-
 template <int G, int F>
 int launch_gat(const GatParams& p, int blocks, int threads, size_t lds, hipStream_t st, int tag) {
   constexpr int slot = G == 16 ? MAGAT_LDS_GAT16 : G == 32 ? MAGAT_LDS_GAT32 : G == 64 ? MAGAT_LDS_GAT64
@@ -1118,6 +1091,19 @@ int launch_gat(const GatParams& p, int blocks, int threads, size_t lds, hipStrea
     return MAGAT_ERR_LAUNCH;
   const int pid = magat_prof_begin(tag, st);
   hipLaunchKernelGGL((gat_dense_kernel<G, F>), dim3(blocks), dim3(threads), lds, st, p);
+  magat_prof_end(pid, st);
+  return magat_check_launch();
+}
+
+// the guard's one-launch re-run; CO = 5: with the caller's skinny layer in it
+template <int G, int CO>
+int launch_rerun_small(const GatParams& p, const float* packed, const float* cbias, const MagatSkinnyParams& sp, int grid, size_t lds,
+                       hipStream_t st) {
+  constexpr int slot = MAGAT_LDS_GAT_RERUN_S + (G == 32 ? 0 : G == 64 ? 1 : 2) + (CO ? 3 : 0);
+  if (magat_ensure_dyn_lds(reinterpret_cast<const void*>(&gat_rerun_small_kernel<G, CO>), slot, lds) != MAGAT_OK) return MAGAT_ERR_LAUNCH;
+  const int pid = magat_prof_begin(MAGAT_TAG_RANGE_GUARD, st);
+  hipLaunchKernelGGL((gat_rerun_small_kernel<G, CO>), dim3(grid), dim3(256), lds, st, p, packed, cbias, sp);
+  if (CO) magat_form_note(MAGAT_FORM_ACTIONS_TAIL);
   magat_prof_end(pid, st);
   return magat_check_launch();
 }
@@ -1137,10 +1123,6 @@ extern "C" int magat_gat_set_debug_skip(int mask) { g_gat_skip = mask; return MA
 #endif
 
 // hoisted dense maps Z = X @ Bt^T + colbias: bf16x6 split-MFMA GEMM when the shape allows, else fp32 MFMA
-// row stride of the hoisted-map intermediate Z in the dense path: NC + pad.  NC is a multiple of 128 floats at the
-// benchmark shapes (2048 -> 8 KB rows): the tiles a workgroup reads are 512-byte row pieces exactly 8 KB apart, which
-// all land in the same HBM channels; a 128-byte skew per row spreads them.
-static int gat_zpad() { return 32; }      // row skew of Z (floats)
 // float32-MFMA form of the maps (exact fp32 products): the guard's re-run, and the training path
 static int gat_maps_gemm_f32(const float* X, const float* packed, float* Z, int M, int G, int NC, int ldz, void* stream,
                              long long ntile_stride, const int32_t* run_if, int tag) {
@@ -1167,7 +1149,7 @@ __global__ void gat_guard_count_kernel(int* status) {     // see guard_count_ker
 int magat_gat_maps_gemm(const float* X, const float* packed, float* Z, int M, int G, int NC, int ldz, void* stream,
                         long long ntile_stride, int32_t* status, int force_f32) {
   hipStream_t st = static_cast<hipStream_t>(stream);
-  if (!force_f32 && magat_opt(MAGAT_OPT_GAT_SPLIT) && NC % 32 == 0 && G % 32 == 0) {
+  if (!force_f32 && magat_gat::maps_split(magat_opt(MAGAT_OPT_GAT_SPLIT), NC, G)) {
     const int use_f16 = 1;      // (f16x3; the bf16x6 flavour was removed in round 5; the pack's bf16 plane 0 feeds the bf16-storage maps GEMM)
     const bool guard = status && use_f16 && magat_opt(MAGAT_OPT_RANGE_GUARD) != 0;
     magat_conv_gemm_desc d = {};
@@ -1214,16 +1196,36 @@ int magat_gat_cos_prepare(const float* X, float* Z, float* Xhat, long long M, in
   return magat_check_launch();
 }
 
+namespace gr = magat_gat;
+static_assert(gr::MODE_KEYQUERY == MAGAT_MODE_KEYQUERY && gr::MODE_GAT_MODIFIED == MAGAT_MODE_GAT_MODIFIED &&
+              gr::MODE_GAT_ORIGIN == MAGAT_MODE_GAT_ORIGIN && gr::MODE_GNN == MAGAT_MODE_GNN &&
+              gr::MODE_SIMILARITY == MAGAT_MODE_SIMILARITY && gr::kXcd == MAGAT_NUM_XCD, "gat_route.h restates these");
+
+static gr::RouteOpts gat_route_opts() {
+  return {magat_opt(MAGAT_OPT_GAT_MFMA), magat_opt(MAGAT_OPT_GAT_SPLIT), magat_opt(MAGAT_OPT_RANGE_GUARD),
+          magat_opt(MAGAT_OPT_GAT_WIDE_FROM), magat_opt(MAGAT_OPT_GAT_PACK), magat_opt(MAGAT_OPT_GAT_CHUNK_MB)};
+}
+// what route() says about a shape alone: one instance, one head, no attention tensor, Y aligned (no device needed)
+static gr::Route gat_shape_route(int N, int G, int F, int K, int mode, int concat) {
+  gr::RouteIn in = {};
+  in.B = 1; in.N = N; in.G = G; in.F = F; in.K = K; in.P = 1; in.mode = mode; in.concat = concat;
+  in.y_aligned = true; in.opt = gat_route_opts(); in.conv_direct = magat_conv_direct_enabled() != 0; in.cus = 256;
+  return gr::route(in);
+}
+
 // 1 when the LDS-resident dense-GSO kernel covers this shape, 0 when the caller must use the CSR entry point
-extern "C" int magat_gat_dense_supported(int N, int G, int F) {
-  if (N <= 0 || N > 128 || G != F || !supported_width(G)) return 0;
-  return gat_lds_bytes(N, G, F, gat_block_threads(N) / 64) <= 160 * 1024 ? 1 : 0;
+extern "C" int magat_gat_dense_supported(int N, int G, int F) {      // (K = 1: no one-launch form, so the two-launch tiles decide)
+  return gat_shape_route(N, G, F, 1, MAGAT_MODE_KEYQUERY, 1).refusal == gr::REFUSE_NONE ? 1 : 0;
+}
+
+extern "C" int magat_gat_one_launch_supported(int N, int G, int F, int K, int mode, int concat) {
+  const gr::Route r = gat_shape_route(N, G, F, K, mode, concat);
+  return r.refusal == gr::REFUSE_NONE && r.form != gr::TWO_LAUNCH ? 1 : 0;
 }
 
 // (The optional GSO plan of rounds 2-5 - edge masks and an edge-count-balanced instance walk made at addGSO time on a side
 //  stream, magat_gat_gso_plan - was removed in round 6: opt-in, measured 0.5-1.8 % SLOWER per step at c3, never the default.
 //  magat_gat_forward_planned_f32 keeps its signature; its `plan` argument must be NULL.)
-constexpr int GAT_PLAN_WALKERS = 256;     // persistent graph-kernel workgroups (one per CU)
 
 constexpr size_t GAT_STATUS_BYTES = 256;   // status block (range guard of the maps GEMM) at the head of the workspace
 
@@ -1239,43 +1241,173 @@ extern "C" int magat_gat_read_status(const void* workspace, int32_t status_host[
   return MAGAT_OK;
 }
 
+// bytes of the chunk's Z behind the status block
+static size_t gat_z_bytes(int chunk, int N, int ldz) { return magat_align_up((size_t)chunk * N * ldz * sizeof(float), 256); }
+
 extern "C" size_t magat_gat_workspace_bytes(int B, int N, int G, int F, int K, int P, int mode, int concat) {
   if (B <= 0 || N <= 0 || G <= 0 || F <= 0 || K <= 0 || P <= 0) return 0;
-  const PackLayout L = pack_layout(G, F, K, P, mode);
-  const int ldz = L.NC + gat_zpad();
-  const int chunk = gat_chunk_instances(B, N, ldz);
-  size_t bytes = GAT_STATUS_BYTES + magat_align_up((size_t)chunk * N * ldz * sizeof(float), 256);
+  const int ldz = gr::pack_columns(G, F, K, P, mode) + gr::kZpad;
+  const int chunk = gr::gat_chunk_instances(B, N, ldz, magat_opt(MAGAT_OPT_GAT_CHUNK_MB));
+  size_t bytes = GAT_STATUS_BYTES + gat_z_bytes(chunk, N, ldz);
   if (!concat) bytes += magat_align_up((size_t)B * N * P * F * sizeof(float), 256);
   if (mode == MAGAT_MODE_SIMILARITY) bytes += magat_align_up((size_t)B * N * G * sizeof(float), 256);      // the normalised X rows
   return bytes;
 }
 
-static bool gat_one_launch(int N, int G, int F, int K, int mode, int concat) {
-  (void)concat;
-  // GAT_Similarity: the cosine forms of gat_small.hip (N <= 32) and gat_mid.hip, and only with the range guard on - a row too small for the f16 planes
-  // raises its flag and is served by the float32 re-run
-  if (mode == MAGAT_MODE_SIMILARITY)
-    return magat_opt(MAGAT_OPT_GAT_MFMA) && magat_opt(MAGAT_OPT_GAT_SPLIT) && magat_opt(MAGAT_OPT_RANGE_GUARD) != 0 &&
-           (magat_gat_small_supported(N, G, F, K, mode) || magat_gat_mid_supported(N, G, F, K, mode));
-  return magat_opt(MAGAT_OPT_GAT_MFMA) && magat_opt(MAGAT_OPT_GAT_SPLIT) &&
-         (magat_gat_mfma_supported(N, G, F, K, mode) || magat_gat_small_supported(N, G, F, K, mode) ||
-          magat_gat_mid_supported(N, G, F, K, mode));
+namespace {
+// one call of the layer: its arguments, and where its workspace pieces are
+struct GatCall {
+  const float* X; const void* S; int s_is_f64; const float* packed; const float* bias; float* Y; int ldy; float* A_opt;
+  int B, N, G, F, K, P, mode, concat;
+  int32_t* status; float* Z; float* Ytmp; float* Xhat;
+  void* stream;
+  hipStream_t st() const { return static_cast<hipStream_t>(stream); }
+  bool cosine() const { return mode == MAGAT_MODE_SIMILARITY; }
+};
+
+GatParams gat_params(const GatCall& c, const gr::Route& r, const PackLayout& L) {
+  GatParams p;
+  p.order = nullptr;
+  p.rmask_pre = nullptr;
+  p.run_if = r.guard != gr::GUARD_NONE ? c.status : nullptr;      // (read by the re-run's launches only)
+  p.book = nullptr;
+  p.dbg = g_gat_dbg;
+  p.skip = 0;
+#ifdef MAGAT_DEBUG_HOOKS
+  p.skip = g_gat_skip;
+#endif
+  p.X = c.X; p.S = c.S; p.Z = c.Z; p.bias = c.bias; p.A_opt = c.A_opt;
+  p.Y = c.concat ? c.Y : c.Ytmp;
+  p.N = c.N; p.K = c.K; p.P = c.P; p.mode = c.mode; p.concat = c.concat; p.s_is_f64 = c.s_is_f64;
+  p.ldx = c.G; p.ldy = c.concat ? c.ldy : c.P * c.F; p.NC = r.ldz; p.lda_a = c.N | 1;
+  p.qoff = L.qoff; p.uoff = L.uoff; p.c1off = L.c1off; p.c2off = L.c2off;
+  p.origin_mask = (c.mode == MAGAT_MODE_GAT_ORIGIN || c.cosine()) ? 1 : 0;
+  // GAT_Similarity: the graph kernel runs as KeyQuery on the normalised rows gat_cos_prepare_kernel leaves behind the maps GEMM
+  if (c.cosine()) { p.X = c.Xhat; p.mode = MAGAT_MODE_KEYQUERY; }
+  return p;
 }
 
-extern "C" int magat_gat_one_launch_supported(int N, int G, int F, int K, int mode, int concat) {
-  if (N <= 0 || G != F || !supported_width(G) || N > 128) return 0;
-  return gat_one_launch(N, G, F, K, mode, concat) ? 1 : 0;
+int run_one_launch(const GatCall& c, const gr::Route& r, const PackLayout& L) {
+  int* flag = r.guard != gr::GUARD_NONE ? c.status : nullptr;
+  const float* x_scale = reinterpret_cast<const float*>(c.status + 4);
+  const float* frag = c.packed + magat_gat_frag_offset(L.NC, c.G);
+  const float* planes = c.packed + magat_gat_f16_block_offset(L.NC, c.G);
+  float* ypre = c.concat ? nullptr : c.Ytmp;
+  if (r.form == gr::ONE_MFMA)
+    return magat_gat_mfma_forward(c.X, c.G, c.S, c.s_is_f64, nullptr, frag, c.bias, c.Y, c.ldy, c.B, c.N, c.K, c.P, c.concat, flag,
+                                  c.st(), x_scale, c.mode,
+                                  c.mode == MAGAT_MODE_KEYQUERY ? nullptr : frag + (size_t)(c.P * c.G + c.P * c.K * c.F) * c.G, ypre,
+                                  c.P * c.F, r.one);
+  if (r.form == gr::ONE_SMALL)
+    return magat_gat_small_forward(c.X, c.G, c.S, c.s_is_f64, nullptr, planes, L.NC, c.bias, c.Y, c.ldy, c.B, c.N, c.G, c.K, c.P,
+                                   c.concat, flag, c.st(), x_scale, c.cosine() ? 1 : 0, r.one);
+  return magat_gat_mid_forward(c.X, c.G, c.S, c.s_is_f64, planes, L.NC, c.bias, c.Y, c.ldy, c.B, c.N, c.G, c.K, c.P, c.concat, flag,
+                               c.st(), x_scale, ypre, c.P * c.F, c.G == 128 ? frag : nullptr, c.cosine() ? 1 : 0, r.one);
 }
 
-// tail / tail_done: magat_gat_forward_tail_f32 (below)
+// GUARD_ONE / GUARD_ONE_TAIL: final rows straight into Y, the guard's bookkeeping too
+int run_rerun_small(const GatCall& c, const gr::Route& r, const PackLayout& L, GatParams p, const MagatSkinnyParams& sp,
+                    int* tail_done) {
+  p.B = c.B; p.b0 = 0; p.Ymean = c.Y; p.ldym = c.ldy; p.book = reinterpret_cast<int*>(c.status);
+  const bool with_tail = r.guard == gr::GUARD_ONE_TAIL;
+  const size_t lds = gr::gat_rerun_small_lds(c.N, c.G, with_tail ? sp.Cin + sp.C2 : 0);
+  const float* cbias = c.packed + (size_t)L.NC * c.G;
+  auto go = [&](auto width) {
+    constexpr int G = decltype(width)::value;
+    return with_tail ? launch_rerun_small<G, 5>(p, c.packed, cbias, sp, r.rerun_grid, lds, c.st())
+                     : launch_rerun_small<G, 0>(p, c.packed, cbias, sp, r.rerun_grid, lds, c.st());
+  };
+  const int rc = c.G == 32 ? go(std::integral_constant<int, 32>{}) : c.G == 64 ? go(std::integral_constant<int, 64>{})
+                                                                                : go(std::integral_constant<int, 128>{});
+  if (with_tail && tail_done && rc == MAGAT_OK) *tail_done = 1;
+  return rc;
+}
+
+// per chunk: the maps, gat_cos_prepare_kernel for GAT_Similarity, the graph (or slim) kernel
+int run_chunks(const GatCall& c, const gr::Route& r, const PackLayout& L, GatParams p) {
+  const bool rerun = r.rerun();
+  const int gtag = rerun ? MAGAT_TAG_RANGE_GUARD : MAGAT_TAG_GAT_GRAPH;
+  for (int b0 = 0; b0 < c.B; b0 += r.chunk) {
+    const int cb = (c.B - b0) < r.chunk ? (c.B - b0) : r.chunk;
+    const float* Xc = c.X + (size_t)b0 * c.N * c.G;
+    p.zts = r.zts(cb);
+    int rc = rerun ? gat_maps_gemm_f32(Xc, c.packed, c.Z, cb * c.N, c.G, L.NC, r.ldz, c.stream, p.zts, c.status, MAGAT_TAG_RANGE_GUARD)
+                   : magat_gat_maps_gemm(Xc, c.packed, c.Z, cb * c.N, c.G, L.NC, r.ldz, c.stream, p.zts, c.status,
+                                         r.maps == gr::MAPS_F32 ? 1 : 0);
+    if (rc != MAGAT_OK) return rc;
+    if (r.prepare) {
+      rc = magat_gat_cos_prepare(Xc, c.Z, c.Xhat + (size_t)b0 * c.N * c.G, (long long)cb * c.N, c.G, L.qoff, r.ldz, p.zts, c.stream,
+                                 rerun ? c.status : nullptr);
+      if (rc != MAGAT_OK) return rc;
+    }
+    p.B = cb; p.b0 = b0;
+    p.hpb = r.hpb(cb);
+    p.Ymean = r.all_fused ? c.Y : nullptr;
+    p.ldym = c.ldy;
+    p.book = (r.book == gr::BOOK_GRAPH && b0 + r.chunk >= c.B) ? reinterpret_cast<int*>(c.status) : nullptr;
+    const int blocks = r.blocks(cb);
+    if (r.slim) {
+      const size_t slds = gr::gat_slim_lds(c.N);
+      if (magat_ensure_dyn_lds(reinterpret_cast<const void*>(&gat_slim_kernel), MAGAT_LDS_GAT_SLIM, slds) != MAGAT_OK)
+        return MAGAT_ERR_LAUNCH;
+      const int pid = magat_prof_begin(gtag, c.st());
+      hipLaunchKernelGGL(gat_slim_kernel, dim3(blocks), dim3(256), slds, c.st(), p);
+      magat_prof_end(pid, c.st());
+      rc = magat_check_launch();
+    } else
+    switch (c.G) {
+      case 16: rc = launch_gat<16, 16>(p, blocks, r.threads, r.lds, c.st(), gtag); break;
+      case 32: rc = launch_gat<32, 32>(p, blocks, r.threads, r.lds, c.st(), gtag); break;
+      case 64: rc = launch_gat<64, 64>(p, blocks, r.threads, r.lds, c.st(), gtag); break;
+      case 128: rc = launch_gat<128, 128>(p, blocks, r.threads, r.lds, c.st(), gtag); break;
+      case 256: rc = launch_gat<256, 256>(p, blocks, r.threads, r.lds, c.st(), gtag); break;
+      default: rc = MAGAT_ERR_UNSUPPORTED;
+    }
+    if (rc != MAGAT_OK) return rc;
+  }
+  return MAGAT_OK;
+}
+
+int run_head_mean(const GatCall& c, const gr::Route& r) {
+  const long long M = (long long)c.B * c.N;
+  long long blocks = (M * (c.F / 4) + 255) / 256;
+  if (blocks > 4096) blocks = 4096;
+  const int pid = magat_prof_begin(r.rerun() ? MAGAT_TAG_RANGE_GUARD : MAGAT_TAG_HEAD_MEAN, c.st());
+  hipLaunchKernelGGL(head_mean_relu_kernel, dim3((unsigned)blocks), dim3(256), 0, c.st(), c.Ytmp, c.Y, M, c.P, c.F, c.ldy,
+                     r.rerun() ? reinterpret_cast<const int*>(c.status) : nullptr,
+                     r.book == gr::BOOK_MEAN ? reinterpret_cast<int*>(c.status) : nullptr);
+  magat_prof_end(pid, c.st());
+  return magat_check_launch() != MAGAT_OK ? MAGAT_ERR_LAUNCH : MAGAT_OK;
+}
+
+// compute units of the CURRENT device (a cheap attribute query, no cached process-wide value: one process may drive several)
+int gat_device_cus() {
+  int cus = 256, dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess ||
+      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
+    cus = 256;
+  return cus;
+}
+}  // namespace
+
+// Validate, ask gat_route.h which launches the call takes, run them.  tail / tail_done: magat_gat_forward_tail_f32 (below)
 static int gat_forward_impl(const float* X, const void* S, int s_is_f64, const float* packed, const float* bias, float* Y, int ldy,
                             float* A_opt, void* workspace, size_t workspace_bytes, int B, int N, int G, int F, int K, int P,
                             int mode, int concat, const magat_conv_gemm_desc* tail, int* tail_done, void* stream) {
   if (!X || !S || !packed || !Y) return MAGAT_ERR_NULL;
-  if (B <= 0 || N <= 0 || G <= 0 || F <= 0 || K <= 0 || P <= 0) return MAGAT_ERR_BAD_SHAPE;
-  const bool cosine = mode == MAGAT_MODE_SIMILARITY;
-  if ((mode < MAGAT_MODE_KEYQUERY || mode > MAGAT_MODE_GAT_ORIGIN) && !cosine) return MAGAT_ERR_UNSUPPORTED;
-  if (G != F || !supported_width(G) || N > 128 || (cosine && P != 1)) return MAGAT_ERR_UNSUPPORTED;
+  gr::RouteIn in = {};
+  in.B = B; in.N = N; in.G = G; in.F = F; in.K = K; in.P = P; in.mode = mode; in.concat = concat;
+  in.attention = A_opt != nullptr;
+  in.y_aligned = (reinterpret_cast<uintptr_t>(Y) & 15) == 0;
+  MagatSkinnyParams sp{};
+  in.tail = tail && magat_skinny_params(tail, &sp) == MAGAT_OK;
+  in.tail_cout = sp.Cout; in.tail_m = sp.M; in.tail_k = sp.Cin + sp.C2;
+  in.opt = gat_route_opts();
+  in.conv_direct = magat_conv_direct_enabled() != 0;
+  in.cus = gat_device_cus();
+  const gr::Route r = gr::route(in);
+  if (r.refusal == gr::REFUSE_DIMS) return MAGAT_ERR_BAD_SHAPE;
+  if (r.refusal == gr::REFUSE_MODE || r.refusal == gr::REFUSE_SHAPE) return MAGAT_ERR_UNSUPPORTED;
   const int width = concat ? P * F : F;
   if (ldy < width || (ldy & 3)) return MAGAT_ERR_BAD_SHAPE;
   // X rows are read in 16-byte pieces by every form (gat_small / gat_mid, the maps GEMMs and the range guard's float32 re-run
@@ -1285,191 +1417,25 @@ static int gat_forward_impl(const float* X, const void* S, int s_is_f64, const f
   if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255) ||
       workspace_bytes < magat_gat_workspace_bytes(B, N, G, F, K, P, mode, concat))
     return MAGAT_ERR_WORKSPACE;
-  const int threads = gat_block_threads(N);
-  const size_t lds = gat_lds_bytes(N, G, F, threads / 64);
-  // beyond gat_dense_kernel's tiles (128 features: N > 105) only the one-launch form of gat_mid.hip exists, with gat_slim_kernel
-  // as the range guard's float32 re-run; no attention tensor there (the CSR kernels serve such requests)
-  const bool slim = lds > 160 * 1024;
-  if (slim && cosine) return MAGAT_ERR_UNSUPPORTED;      // (128 features on N > 105: the CSR kernels serve GAT_Similarity there)
-  if (slim && !(G == 128 && F == 128 && mode == MAGAT_MODE_KEYQUERY && !A_opt && gat_one_launch(N, G, F, K, mode, concat) &&
-                (reinterpret_cast<uintptr_t>(Y) & 15) == 0))
-    return MAGAT_ERR_UNSUPPORTED;
-  hipStream_t st = static_cast<hipStream_t>(stream);
+  if (r.refusal != gr::REFUSE_NONE) return MAGAT_ERR_UNSUPPORTED;
 
+  GatCall c = {X, S, s_is_f64, packed, bias, Y, ldy, A_opt, B, N, G, F, K, P, mode, concat};
+  c.stream = stream;
+  c.status = static_cast<int32_t*>(workspace);
+  c.Z = reinterpret_cast<float*>(static_cast<char*>(workspace) + GAT_STATUS_BYTES);
+  c.Ytmp = c.Z + gat_z_bytes(r.chunk, N, r.ldz) / sizeof(float);
+  c.Xhat = c.cosine() ? c.Ytmp + (concat ? 0 : magat_align_up((size_t)B * N * P * F * sizeof(float), 256) / sizeof(float)) : nullptr;
   const PackLayout L = pack_layout(G, F, K, P, mode);
-  const int ldz = L.NC + gat_zpad();
-  const int chunk = gat_chunk_instances(B, N, ldz);
-  int32_t* status = static_cast<int32_t*>(workspace);
-  float* Z = reinterpret_cast<float*>(static_cast<char*>(workspace) + GAT_STATUS_BYTES);
-  float* Ytmp = reinterpret_cast<float*>(static_cast<char*>(workspace) + GAT_STATUS_BYTES +
-                                         magat_align_up((size_t)chunk * N * ldz * sizeof(float), 256));
-  GatParams p;
-  p.order = nullptr;
-  p.rmask_pre = nullptr;
-  p.run_if = nullptr;
-  p.book = nullptr;
-  p.dbg = g_gat_dbg;
-  p.skip = 0;
-#ifdef MAGAT_DEBUG_HOOKS
-  p.skip = g_gat_skip;
-#endif
-  p.X = X; p.S = S; p.Z = Z; p.bias = bias; p.A_opt = A_opt;
-  p.Y = concat ? Y : Ytmp;
-  p.N = N; p.K = K; p.P = P; p.mode = mode; p.concat = concat; p.s_is_f64 = s_is_f64;
-  p.ldx = G; p.ldy = concat ? ldy : P * F; p.NC = ldz; p.lda_a = N | 1;
-  p.qoff = L.qoff; p.uoff = L.uoff; p.c1off = L.c1off; p.c2off = L.c2off;
-  p.origin_mask = (mode == MAGAT_MODE_GAT_ORIGIN || cosine) ? 1 : 0;
-  // GAT_Similarity: the graph kernel runs as KeyQuery on the normalised rows gat_cos_prepare_kernel leaves behind the maps GEMM
-  float* Xhat = cosine ? Ytmp + (concat ? 0 : magat_align_up((size_t)B * N * P * F * sizeof(float), 256) / sizeof(float)) : nullptr;
-  if (cosine) { p.X = Xhat; p.mode = MAGAT_MODE_KEYQUERY; }
-
-  // One launch of matrix-core products (gat_mfma.hip) when the shape allows; with the range guard on, the two-launch float32
-  // form below follows in the same stream, every launch of it predicated on the flag the fused kernel raises.
-  bool rerun_only = false;
-  // (the one-launch kernels store Y in 16-byte pieces: a column block at an odd offset of a wider buffer takes the two-launch
-  //  form - or, beyond its tiles, is refused above)
-  if (!A_opt && gat_one_launch(N, G, F, K, mode, concat) && (reinterpret_cast<uintptr_t>(Y) & 15) == 0) {
-    const bool guard = magat_opt(MAGAT_OPT_RANGE_GUARD) != 0;
-    const unsigned* masks = nullptr;
-    const float* frag = packed + magat_gat_frag_offset(L.NC, G);
-    // (128 features: gat_mfma.hip; 32 / 64 features on graphs of at most 32 agents: gat_small.hip, a wave per instance)
-    const int rc = G == 128 && magat_gat_mfma_supported(N, G, F, K, mode)
-        ? magat_gat_mfma_forward(X, G, S, s_is_f64, masks, frag, bias, Y, ldy, B, N, K, P, concat,
-                                 guard ? status : nullptr, st, reinterpret_cast<const float*>(status + 4), mode,
-                                 mode == MAGAT_MODE_KEYQUERY ? nullptr : frag + (size_t)(P * G + P * K * F) * G,
-                                 concat ? nullptr : Ytmp, P * F)
-        : G != 128 && N <= 32
-        ? magat_gat_small_forward(X, G, S, s_is_f64, masks, packed + magat_gat_f16_block_offset(L.NC, G), L.NC, bias, Y, ldy, B,
-                                  N, G, K, P, concat, guard ? status : nullptr, st, reinterpret_cast<const float*>(status + 4),
-                                  cosine ? 1 : 0)
-        // (32 / 64 features on 33 .. 128 agents, 128 features on 103 .. 128: gat_mid.hip, a workgroup of ceil(N / 32) waves per
-        //  instance - round 6)
-        : magat_gat_mid_forward(X, G, S, s_is_f64, packed + magat_gat_f16_block_offset(L.NC, G), L.NC, bias, Y, ldy, B, N, G, K, P,
-                                concat, guard ? status : nullptr, st, reinterpret_cast<const float*>(status + 4),
-                                concat ? nullptr : Ytmp, P * F, G == 128 ? frag : nullptr, cosine ? 1 : 0);
-    if (rc != MAGAT_OK || !guard) return rc;
-    rerun_only = true;
-    p.run_if = status;
-    if (mode == MAGAT_MODE_KEYQUERY && (G == 32 || G == 64 || G == 128) && (long long)B * P <= GAT_RERUN_SMALL_UNITS) {
-      // few instances: the whole float32 form as ONE predicated launch (final rows straight into Y, the guard's bookkeeping too)
-      p.B = B; p.b0 = 0; p.Ymean = Y; p.ldym = ldy; p.book = reinterpret_cast<int*>(status);
-      size_t slds = sizeof(float) * ((size_t)N * (G + 1) + (size_t)N * (N | 1));
-      // the layer that reads this one's rows (the action head: five outputs) in the same launch, when the caller handed it over
-      MagatSkinnyParams sp{};
-      const bool with_tail = tail && magat_skinny_params(tail, &sp) == MAGAT_OK && sp.Cout == 5 && sp.M == B * N &&
-                             (size_t)(sp.Cin + sp.C2) * 5 * sizeof(float) <= 64 * 1024;
-      if (with_tail && (size_t)(sp.Cin + sp.C2) * 5 * sizeof(float) > slds) slds = (size_t)(sp.Cin + sp.C2) * 5 * sizeof(float);
-      const int gi = G == 32 ? 0 : G == 64 ? 1 : 2;
-      const void* fns[2][3] = {{reinterpret_cast<const void*>(&gat_rerun_small_kernel<32, 0>), reinterpret_cast<const void*>(&gat_rerun_small_kernel<64, 0>),
-                                reinterpret_cast<const void*>(&gat_rerun_small_kernel<128, 0>)},
-                               {reinterpret_cast<const void*>(&gat_rerun_small_kernel<32, 5>), reinterpret_cast<const void*>(&gat_rerun_small_kernel<64, 5>),
-                                reinterpret_cast<const void*>(&gat_rerun_small_kernel<128, 5>)}};
-      if (magat_ensure_dyn_lds(fns[with_tail ? 1 : 0][gi], MAGAT_LDS_GAT_RERUN_S + gi + (with_tail ? 3 : 0), slds) != MAGAT_OK) return MAGAT_ERR_LAUNCH;
-      const float* cbias = packed + (size_t)L.NC * G;
-      const int pid = magat_prof_begin(MAGAT_TAG_RANGE_GUARD, st);
-      if (with_tail) {
-        const int tg = (B * N + 15) / 16, grid = tg > B ? tg : B;      // (B x heads <= 64, N <= 128: at most 512 workgroups)
-        if (G == 32) hipLaunchKernelGGL((gat_rerun_small_kernel<32, 5>), dim3(grid), dim3(256), slds, st, p, packed, cbias, sp);
-        else if (G == 64) hipLaunchKernelGGL((gat_rerun_small_kernel<64, 5>), dim3(grid), dim3(256), slds, st, p, packed, cbias, sp);
-        else hipLaunchKernelGGL((gat_rerun_small_kernel<128, 5>), dim3(grid), dim3(256), slds, st, p, packed, cbias, sp);
-        magat_form_note(MAGAT_FORM_ACTIONS_TAIL);
-      } else {
-        if (G == 32) hipLaunchKernelGGL((gat_rerun_small_kernel<32, 0>), dim3(B), dim3(256), slds, st, p, packed, cbias, sp);
-        else if (G == 64) hipLaunchKernelGGL((gat_rerun_small_kernel<64, 0>), dim3(B), dim3(256), slds, st, p, packed, cbias, sp);
-        else hipLaunchKernelGGL((gat_rerun_small_kernel<128, 0>), dim3(B), dim3(256), slds, st, p, packed, cbias, sp);
-      }
-      magat_prof_end(pid, st);
-      if (with_tail && tail_done) *tail_done = 1;
-      return magat_check_launch();
-    }
+  const GatParams p = gat_params(c, r, L);
+  if (r.form != gr::TWO_LAUNCH) {
+    const int rc = run_one_launch(c, r, L);
+    if (rc != MAGAT_OK || r.guard == gr::GUARD_NONE) return rc;
+    if (!r.rerun()) return run_rerun_small(c, r, L, p, sp, tail_done);
   }
-  auto hpb_for = [&](int cb) {
-    int h = 1;
-    if (G >= 64 && P > 1 && lds > 80 * 1024 && cb >= 256) h = P;
-    return h;
-  };
-  bool all_fused = !concat && G >= 64 && !slim;
-  for (int b0 = 0; b0 < B && all_fused; b0 += chunk) all_fused = hpb_for((B - b0) < chunk ? (B - b0) : chunk) == P;
-  for (int b0 = 0; b0 < B; b0 += chunk) {
-    const int cb = (B - b0) < chunk ? (B - b0) : chunk;
-    // Z in 128-column tiles ([tile][cb * N][128]: an instance's Q_p / U_pk tile is ONE contiguous N x 128 run for the
-    // LDS-direct loads, and every workgroup of the maps GEMM writes one contiguous region) when the dense kernel with
-    // 128-wide features consumes it and the f16x3 direct GEMM produces it.
-    const bool ztiles = G == 128 && F == 128 && L.NC % 128 == 0 && magat_conv_direct_enabled() &&
-                        magat_opt(MAGAT_OPT_GAT_SPLIT);
-    p.zts = ztiles ? (long long)cb * N * 128 : 0;
-    // (one chunk is the rule; with several, a clamp in an earlier chunk leaves the flag set only until the next chunk's
-    // own GEMM clears it - status[1] still counts every re-run)
-    int rc = rerun_only ? gat_maps_gemm_f32(X + (size_t)b0 * N * G, packed, Z, cb * N, G, L.NC, ldz, stream, p.zts, status,
-                                            MAGAT_TAG_RANGE_GUARD)
-                        // (GAT_Similarity: float32 MFMA maps - an agent whose features are tiny, |x| ~ 1e-12, is zero in f16
-                        //  planes, and so would be its q_j, whose DIRECTION is what the cosine score reads; nothing to guard then)
-                        : magat_gat_maps_gemm(X + (size_t)b0 * N * G, packed, Z, cb * N, G, L.NC, ldz, stream, p.zts, status,
-                                              cosine ? 1 : 0);
-    if (rc != MAGAT_OK) return rc;
-    if (cosine) {
-      rc = magat_gat_cos_prepare(X + (size_t)b0 * N * G, Z, Xhat + (size_t)b0 * N * G, (long long)cb * N, G, L.qoff, ldz, p.zts,
-                                 stream, rerun_only ? status : nullptr);
-      if (rc != MAGAT_OK) return rc;
-    }
-    p.B = cb; p.b0 = b0;
-    // heads per workgroup: when the LDS tiles allow only one workgroup per CU there is nothing to overlap a
-    // workgroup's loads with, so one workgroup walks all P heads of its instance and prefetches the next head's
-    // Q tile during the current head's compute; needs enough instances to fill the chip.
-    const int hpb = hpb_for(cb);
-    p.hpb = hpb;
-    // mean merge fused into the graph kernel when one workgroup sees all heads of an instance (decided for the whole
-    // call: every chunk must qualify, otherwise the separate kernel merges everything from Ytmp)
-    p.Ymean = all_fused ? Y : nullptr;
-    p.ldym = ldy;
-    // with one workgroup per CU (hpb == P case) the grid is capped at one workgroup per CU and every workgroup walks
-    // several instances, prefetching across the instance boundary as well
-    int inst_slots = (cb + MAGAT_NUM_XCD - 1) / MAGAT_NUM_XCD * MAGAT_NUM_XCD;
-    if (hpb == P && hpb > 1 && inst_slots > GAT_PLAN_WALKERS) inst_slots = GAT_PLAN_WALKERS;
-    // the range guard's predicated re-run: a launch that returns at once still pays for every workgroup it dispatches - with one
-    // workgroup per (instance, head) that was 4096 dispatches, 76 us per forward at BASELINE config 2 (1024 instances of 20
-    // agents; 88 us of a 1.10 ms step went to the guard).  The workgroups walk the instances instead (istride below)
-    if (rerun_only && inst_slots > 128) inst_slots = 128;
-    // (capping the ordinary launches the same way was measured at the published shape - 4096 workgroups of the narrow graph
-    //  kernel, 21.7 us: 23 / 32 / 55 us with 512 / 256 / 128 slots - they are not dispatch-bound)
-    const int blocks = inst_slots * (P / hpb);
-    p.order = nullptr;
-    p.rmask_pre = nullptr;
-    const int gtag = rerun_only ? MAGAT_TAG_RANGE_GUARD : MAGAT_TAG_GAT_GRAPH;
-    // the re-run's last launch does the guard's bookkeeping: the graph kernel of the last chunk, or the head-mean kernel
-    p.book = (rerun_only && b0 + chunk >= B && (concat || all_fused)) ? reinterpret_cast<int*>(status) : nullptr;
-    if (slim) {
-      const size_t slds = sizeof(float) * ((size_t)N * 129 + (size_t)N * (N | 1));
-      if (magat_ensure_dyn_lds(reinterpret_cast<const void*>(&gat_slim_kernel), MAGAT_LDS_GAT_SLIM, slds) != MAGAT_OK)
-        return MAGAT_ERR_LAUNCH;
-      const int sblocks = cb * P < 128 ? cb * P : 128;      // (a no-op launch pays for every workgroup it dispatches)
-      const int pid = magat_prof_begin(gtag, st);
-      hipLaunchKernelGGL(gat_slim_kernel, dim3(sblocks), dim3(256), slds, st, p);
-      magat_prof_end(pid, st);
-      rc = magat_check_launch();
-    } else
-    switch (G) {
-      case 16: rc = launch_gat<16, 16>(p, blocks, threads, lds, st, gtag); break;
-      case 32: rc = launch_gat<32, 32>(p, blocks, threads, lds, st, gtag); break;
-      case 64: rc = launch_gat<64, 64>(p, blocks, threads, lds, st, gtag); break;
-      case 128: rc = launch_gat<128, 128>(p, blocks, threads, lds, st, gtag); break;
-      case 256: rc = launch_gat<256, 256>(p, blocks, threads, lds, st, gtag); break;
-      default: rc = MAGAT_ERR_UNSUPPORTED;
-    }
-    if (rc != MAGAT_OK) return rc;
-  }
-  if (!concat && !all_fused) {
-    const long long M = (long long)B * N;
-    long long blocks = (M * (F / 4) + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    const int pid = magat_prof_begin(rerun_only ? MAGAT_TAG_RANGE_GUARD : MAGAT_TAG_HEAD_MEAN, st);
-    hipLaunchKernelGGL(head_mean_relu_kernel, dim3((unsigned)blocks), dim3(256), 0, st, Ytmp, Y, M, P, F, ldy, p.run_if,
-                       rerun_only ? reinterpret_cast<int*>(status) : nullptr);
-    magat_prof_end(pid, st);
-    if (magat_check_launch() != MAGAT_OK) return MAGAT_ERR_LAUNCH;
-  }
+  const int rc = run_chunks(c, r, L, p);
+  if (rc != MAGAT_OK || !r.head_mean) return rc;
   // (flag -> status[2], re-run count, flag cleared: done by the last workgroup of the re-run's last launch, magat_guard_book)
-  return MAGAT_OK;
+  return run_head_mean(c, r);
 }
 
 extern "C" int magat_gat_forward_planned_f32(const float* X, const void* S, int s_is_f64, const float* packed,

@@ -31,6 +31,7 @@
 
 #include "magat_common.h"
 #include "f16x3.h"
+#include "gat_route.h"
 
 namespace {
 
@@ -780,73 +781,44 @@ __global__ __launch_bounds__(256, 1) void gat_mfma_kernel(const GatMfmaParams p)
   if (p.range_flag && vmax > 65504.f) atomicOr(p.range_flag, 1);
 }
 
-size_t gat_mfma_lds(int N, int ksi) {
-  const size_t sa = 2 * 16 * (size_t)ksi + 16, r8 = ((size_t)N + 7) & ~(size_t)7;
-  return 2 * (size_t)N * 256 + 2 * r8 * sa + 2 * 128 * sa;
-}
 // PACK form: X planes [128], A planes [128][80], U^T planes [128][272]
 constexpr size_t kGatPackLds = 2 * 128 * 256 + 2 * 128 * 80 + 2 * 128 * 272;
 
-// shape classes: (MT, KSI) = (1, 2) N <= 32, (2, 4) N <= 64, (4, 7) N <= 102 (the LDS bound)
-int gat_mfma_class(int N) {
-  if (N <= 0) return -1;
-  const int c = N <= 32 ? 0 : (N <= 64 ? 1 : 2);
-  const int ksi = c == 0 ? 2 : (c == 1 ? 4 : 7);
-  return (N <= 16 * ksi && gat_mfma_lds(N, ksi) <= 160 * 1024) ? c : -1;
-}
-
-// four instances per pass (N <= 32; see the kernel): one workgroup per pack, every head in it
+// four instances per pass (see the kernel): one workgroup per pack, every head in it
 template <int KT, int MODE>
-int launch_pack(const GatMfmaParams& p, int slot, hipStream_t st) {
+int launch_pack(const GatMfmaParams& p, int slot, const magat_gat::OneLaunch& f, hipStream_t st) {
   const void* fn = p.concat ? reinterpret_cast<const void*>(&gat_mfma_kernel<4, 2, KT, true, MODE, true>)
                             : reinterpret_cast<const void*>(&gat_mfma_kernel<4, 2, KT, false, MODE, true>);
   if (magat_ensure_dyn_lds(fn, slot, kGatPackLds) != MAGAT_OK) return MAGAT_ERR_LAUNCH;
-  int cus = 256, dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-    cus = 256;
   GatMfmaParams q = p;
   q.Binst = p.B;
   q.B = (p.B + 3) / 4;
   q.hsplit = 1;
-  const int blocks = q.B < cus ? q.B : cus;
   magat_form_note(MAGAT_FORM_GAT_PACK);
   const int pid = magat_prof_begin(MAGAT_TAG_GAT_LAYER, st);
-  if (p.concat) hipLaunchKernelGGL((gat_mfma_kernel<4, 2, KT, true, MODE, true>), dim3(blocks), dim3(256), kGatPackLds, st, q);
-  else hipLaunchKernelGGL((gat_mfma_kernel<4, 2, KT, false, MODE, true>), dim3(blocks), dim3(256), kGatPackLds, st, q);
+  if (p.concat) hipLaunchKernelGGL((gat_mfma_kernel<4, 2, KT, true, MODE, true>), dim3(f.grid), dim3(256), kGatPackLds, st, q);
+  else hipLaunchKernelGGL((gat_mfma_kernel<4, 2, KT, false, MODE, true>), dim3(f.grid), dim3(256), kGatPackLds, st, q);
   magat_prof_end(pid, st);
   return magat_check_launch();
 }
 
 template <int MT, int KSI, int KT, int MODE>
-int launch(const GatMfmaParams& p, int slot, hipStream_t st) {
-  const size_t lds = gat_mfma_lds(p.N, KSI);
+int launch(const GatMfmaParams& p, int slot, const magat_gat::OneLaunch& f, hipStream_t st) {
+  const size_t lds = magat_gat::gat_mfma_lds(p.N, KSI);
   const void* fn = p.concat ? reinterpret_cast<const void*>(&gat_mfma_kernel<MT, KSI, KT, true, MODE>)
                             : reinterpret_cast<const void*>(&gat_mfma_kernel<MT, KSI, KT, false, MODE>);
   if (magat_ensure_dyn_lds(fn, slot + (p.concat ? 0 : 6) + 12 * MODE, lds) != MAGAT_OK) return MAGAT_ERR_LAUNCH;
-  // compute units of the CURRENT device (a cheap attribute query, no cached process-wide value: one process may drive several)
-  int cus = 256, dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-    cus = 256;
   GatMfmaParams q = p;
-  // A workgroup per (instance, head) pays the instance prologue once per head (12 k + 36 k cycles per unit against 12 k + 36 k P
-  // per instance), but fills a chip that B instances alone leave idle: the cheaper of the two round counts (concat only: the
-  // head mean accumulates in one workgroup's own rows of Y).
-  const long long unsplit = (long long)((p.B + cus - 1) / cus) * (12 + 36 * p.P);
-  const long long split = (long long)(((long long)p.B * p.P + cus - 1) / cus) * (12 + 36);
-  q.hsplit = ((p.concat || p.Ypre) && p.P > 1 && split < unsplit) ? p.P : 1;      // (head mean: through the caller's scratch rows)
-  const long long units = q.hsplit > 1 ? (long long)p.B * p.P : p.B;
-  const int blocks = (int)(units < (long long)cus * q.hsplit ? units : (long long)cus * q.hsplit);
-  if (q.hsplit > 1) magat_form_note(MAGAT_FORM_GAT_HSPLIT);
-  if (units > blocks) magat_form_note(MAGAT_FORM_GAT_PERSIST);
+  q.hsplit = f.hsplit ? p.P : 1;
+  if (f.hsplit) magat_form_note(MAGAT_FORM_GAT_HSPLIT);
+  if (f.persist) magat_form_note(MAGAT_FORM_GAT_PERSIST);
   const int pid = magat_prof_begin(MAGAT_TAG_GAT_LAYER, st);
-  if (p.concat) hipLaunchKernelGGL((gat_mfma_kernel<MT, KSI, KT, true, MODE>), dim3(blocks), dim3(256), lds, st, q);
+  if (p.concat) hipLaunchKernelGGL((gat_mfma_kernel<MT, KSI, KT, true, MODE>), dim3(f.grid), dim3(256), lds, st, q);
   else {
-    hipLaunchKernelGGL((gat_mfma_kernel<MT, KSI, KT, false, MODE>), dim3(blocks), dim3(256), lds, st, q);
+    hipLaunchKernelGGL((gat_mfma_kernel<MT, KSI, KT, false, MODE>), dim3(f.grid), dim3(256), lds, st, q);
     // head split + head mean: relu(mean over the heads) of the scratch rows, summed in head order like the unsplit form's
     // read-add-write of Y (graphML.py:4663-4667)
-    if (q.hsplit > 1 && magat_gat_mean_launch(p.Ypre, p.Y, (long long)p.B * p.N, p.P, 128, p.ldpre, p.ldy, st) != MAGAT_OK) {
+    if (f.hsplit && magat_gat_mean_launch(p.Ypre, p.Y, (long long)p.B * p.N, p.P, 128, p.ldpre, p.ldy, st) != MAGAT_OK) {
       magat_prof_end(pid, st);
       return MAGAT_ERR_LAUNCH;
     }
@@ -856,24 +828,14 @@ int launch(const GatMfmaParams& p, int slot, hipStream_t st) {
 }
 
 template <int MODE>
-int launch_class(const GatMfmaParams& p, int K, hipStream_t st) {
-  const int cls = gat_mfma_class(p.N);
-  // N <= 32: four instances per pass once the batch fills the chip that way (option GAT_PACK, default 1; below that a workgroup
-  // per instance - or per (instance, head) - has the shorter critical path: the closed-loop step of a single instance).  Packed
-  // and unpacked forms produce the same bits for every instance.
-  int cus = 256, dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-    cus = 256;
-  const int pack = magat_opt(MAGAT_OPT_GAT_PACK);
-  if (cls == 0 && pack && (pack >= 2 || (long long)p.B >= 2LL * cus)) {
+int launch_class(const GatMfmaParams& p, int K, const magat_gat::OneLaunch& f, hipStream_t st) {
+  if (f.pack) {
     const int slot = MAGAT_LDS_GATP_0 + 4 * MODE + (K == 3 ? 0 : 2) + (p.concat ? 0 : 1);
-    return K == 3 ? launch_pack<3, MODE>(p, slot, st) : launch_pack<2, MODE>(p, slot, st);
+    return K == 3 ? launch_pack<3, MODE>(p, slot, f, st) : launch_pack<2, MODE>(p, slot, f, st);
   }
-  if (cls == 0) return K == 3 ? launch<1, 2, 3, MODE>(p, MAGAT_LDS_GATM_0, st) : launch<1, 2, 2, MODE>(p, MAGAT_LDS_GATM_0 + 1, st);
-  if (cls == 1) return K == 3 ? launch<2, 4, 3, MODE>(p, MAGAT_LDS_GATM_0 + 2, st) : launch<2, 4, 2, MODE>(p, MAGAT_LDS_GATM_0 + 3, st);
-  if (cls == 2) return K == 3 ? launch<4, 7, 3, MODE>(p, MAGAT_LDS_GATM_0 + 4, st) : launch<4, 7, 2, MODE>(p, MAGAT_LDS_GATM_0 + 5, st);
-  return MAGAT_ERR_UNSUPPORTED;
+  if (f.cls == 0) return K == 3 ? launch<1, 2, 3, MODE>(p, MAGAT_LDS_GATM_0, f, st) : launch<1, 2, 2, MODE>(p, MAGAT_LDS_GATM_0 + 1, f, st);
+  if (f.cls == 1) return K == 3 ? launch<2, 4, 3, MODE>(p, MAGAT_LDS_GATM_0 + 2, f, st) : launch<2, 4, 2, MODE>(p, MAGAT_LDS_GATM_0 + 3, f, st);
+  return K == 3 ? launch<4, 7, 3, MODE>(p, MAGAT_LDS_GATM_0 + 4, f, st) : launch<4, 7, 2, MODE>(p, MAGAT_LDS_GATM_0 + 5, f, st);
 }
 
 }  // namespace
@@ -882,17 +844,15 @@ int launch_class(const GatMfmaParams& p, int K, hipStream_t st) {
 extern "C" int magat_gat_mfma_set_debug_buffer(long long* dev_buf) { g_gat_mfma_dbg = dev_buf; return MAGAT_OK; }
 #endif
 
-int magat_gat_mfma_supported(int N, int G, int F, int K, int mode) {
-  if (mode < MAGAT_MODE_KEYQUERY || mode > MAGAT_MODE_GAT_ORIGIN || G != 128 || F != 128 || (K != 2 && K != 3)) return 0;
-  return gat_mfma_class(N) >= 0 ? 1 : 0;
-}
-
 int magat_gat_mfma_forward(const float* X, int ldx, const void* S, int s_is_f64, const unsigned* rmask_pre,
                            const float* packed_frag, const float* bias, float* Y, int ldy, int B, int N, int K, int P,
                            int concat, int* range_flag, hipStream_t st, const float* x_scale, int mode, const float* kconst,
-                           float* ypre, int ldpre) {
+                           float* ypre, int ldpre, const magat_gat::OneLaunch& form) {
   GatMfmaParams p;
   p.Ypre = (!concat && ypre && ldpre >= 128 * P) ? ypre : nullptr; p.ldpre = ldpre;
+  // (the LDS tiles are those of the class; a head split without concat writes the scratch rows)
+  if (form.cls != magat_gat::gat_mfma_class(N) || (form.pack && form.cls != 0)) return MAGAT_ERR_UNSUPPORTED;
+  if (form.hsplit && !concat && !p.Ypre) return MAGAT_ERR_WORKSPACE;
   p.x_scale = x_scale;
   p.kconst = kconst; p.origin = mode == MAGAT_MODE_GAT_ORIGIN ? 1 : 0;
   p.X = X; p.ldx = ldx; p.S = S; p.s_is_f64 = s_is_f64; p.rmask_pre = rmask_pre;
@@ -904,5 +864,5 @@ int magat_gat_mfma_forward(const float* X, int ldx, const void* S, int s_is_f64,
 #ifdef MAGAT_DEBUG_HOOKS
   p.dbg = g_gat_mfma_dbg;
 #endif
-  return mode == MAGAT_MODE_KEYQUERY ? launch_class<0>(p, K, st) : launch_class<1>(p, K, st);
+  return mode == MAGAT_MODE_KEYQUERY ? launch_class<0>(p, K, form, st) : launch_class<1>(p, K, form, st);
 }

@@ -21,6 +21,7 @@
 // is left - Q / U^T and A planes - is 139 KB: the one-launch form gat_mfma.hip (162 KB per instance, ends at N = 102) cannot reach.
 #include "magat_common.h"
 #include "f16x3.h"
+#include "gat_route.h"
 
 
 #ifdef MAGAT_DEBUG_HOOKS
@@ -86,29 +87,26 @@ constexpr size_t mid_lds() {
   return (XR ? 0 : 2 * ROWS * RS) + (q > u ? q : u) + 2 * ROWS * SA;
 }
 
-constexpr long long MID_HS_MAX_WG = 64;      // head split while instances x heads stay below this many workgroups
+// workgroups of a launch without head split: as many as fit the chip's LDS at once (at most four per CU), they walk the rest
+inline long long mid_blocks(int B, size_t lds, int cus) {
+  long long per_cu = (long long)(magat_gat::kLdsBytes / lds);
+  if (per_cu < 1) per_cu = 1;
+  if (per_cu > 4) per_cu = 4;
+  return B > cus * per_cu ? cus * per_cu : B;
+}
 
 // slot: LDS-attribute slots of the four kernels of this (width, taps, row tiles) class - concat, mean, and the two head-split forms
+// f.hsplit (few instances, the batch-1 step): a workgroup per (instance, head); head-mean then needs the caller's scratch rows
 template <int F, int KT, int NT, bool XR = false>
-int launch_mid(const GatMidParams& p, int concat, int slot, int slot_hs, hipStream_t st) {
+int launch_mid(const GatMidParams& p, int concat, int slot, int slot_hs, const magat_gat::OneLaunch& f, hipStream_t st) {
   constexpr size_t lds = mid_lds<F, NT, XR>();
-  static_assert(lds <= 160 * 1024, "LDS");
+  static_assert(lds <= magat_gat::kLdsBytes, "LDS");
   const void* fn = concat ? reinterpret_cast<const void*>(&gat_mid_kernel<F, KT, NT, true, false, XR>)
                           : reinterpret_cast<const void*>(&gat_mid_kernel<F, KT, NT, false, false, XR>);
   if (magat_ensure_dyn_lds(fn, slot + (concat ? 0 : 1), lds) != MAGAT_OK) return MAGAT_ERR_LAUNCH;
-  int cus = 256, dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-    cus = 256;
-  long long per_cu = (160 * 1024) / (long long)lds;
-  if (per_cu < 1) per_cu = 1;
-  if (per_cu > 4) per_cu = 4;
-  long long blocks = p.B;
-  if (blocks > cus * per_cu) blocks = cus * per_cu;
-  // few instances (the batch-1 step): a workgroup per (instance, head); head-mean then needs the caller's scratch rows
-  const bool hs = p.P > 1 && (long long)p.B * p.P <= MID_HS_MAX_WG && (concat || p.Ypre);
+  const long long blocks = mid_blocks(p.B, lds, f.cus);
   const int pid = magat_prof_begin(MAGAT_TAG_GAT_LAYER, st);
-  if (hs) {
+  if (f.hsplit) {
     const void* fh = concat ? reinterpret_cast<const void*>(&gat_mid_kernel<F, KT, NT, true, true, XR>)
                             : reinterpret_cast<const void*>(&gat_mid_kernel<F, KT, NT, false, true, XR>);
     if (magat_ensure_dyn_lds(fh, slot_hs + (concat ? 0 : 1), lds) != MAGAT_OK) {
@@ -139,19 +137,11 @@ int launch_mid(const GatMidParams& p, int concat, int slot, int slot_hs, hipStre
 }
 
 template <int F, int KT, int NT, bool XR = false>
-int launch_mid_cos(const GatMidParams& p, int slot, hipStream_t st) {
+int launch_mid_cos(const GatMidParams& p, int slot, int cus, hipStream_t st) {
   constexpr size_t lds = mid_lds<F, NT, XR>() + 32 * NT * sizeof(float);      // + qn[ROWS]
-  static_assert(lds <= 160 * 1024, "LDS");
+  static_assert(lds <= magat_gat::kLdsBytes, "LDS");
   if (magat_ensure_dyn_lds(reinterpret_cast<const void*>(&gat_mid_cos_kernel<F, KT, NT, XR>), slot, lds) != MAGAT_OK) return MAGAT_ERR_LAUNCH;
-  int cus = 256, dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-    cus = 256;
-  long long per_cu = (160 * 1024) / (long long)lds;
-  if (per_cu < 1) per_cu = 1;
-  if (per_cu > 4) per_cu = 4;
-  long long blocks = p.B;
-  if (blocks > cus * per_cu) blocks = cus * per_cu;
+  const long long blocks = mid_blocks(p.B, lds, cus);
   const int pid = magat_prof_begin(MAGAT_TAG_GAT_LAYER, st);
   hipLaunchKernelGGL((gat_mid_cos_kernel<F, KT, NT, XR>), dim3((unsigned)blocks), dim3(64 * NT), lds, st, p);
   magat_prof_end(pid, st);
@@ -159,19 +149,19 @@ int launch_mid_cos(const GatMidParams& p, int slot, hipStream_t st) {
   return magat_check_launch();
 }
 template <int F, int KT>
-int launch_mid_cos_nt(const GatMidParams& p, int slot, hipStream_t st) {
+int launch_mid_cos_nt(const GatMidParams& p, int slot, int cus, hipStream_t st) {
   const int nt = (p.N + 31) / 32;
-  if (nt == 2) return launch_mid_cos<F, KT, 2>(p, slot, st);
-  if (nt == 3) return launch_mid_cos<F, KT, 3>(p, slot + 1, st);
-  return launch_mid_cos<F, KT, 4>(p, slot + 2, st);
+  if (nt == 2) return launch_mid_cos<F, KT, 2>(p, slot, cus, st);
+  if (nt == 3) return launch_mid_cos<F, KT, 3>(p, slot + 1, cus, st);
+  return launch_mid_cos<F, KT, 4>(p, slot + 2, cus, st);
 }
 
 template <int F, int KT>
-int launch_mid_nt(const GatMidParams& p, int concat, int slot, hipStream_t st) {
+int launch_mid_nt(const GatMidParams& p, int concat, int slot, const magat_gat::OneLaunch& f, hipStream_t st) {
   const int nt = (p.N + 31) / 32;
-  if (nt == 2) return launch_mid<F, KT, 2>(p, concat, slot, slot + 24, st);
-  if (nt == 3) return launch_mid<F, KT, 3>(p, concat, slot + 2, slot + 26, st);
-  return launch_mid<F, KT, 4>(p, concat, slot + 4, slot + 28, st);
+  if (nt == 2) return launch_mid<F, KT, 2>(p, concat, slot, slot + 24, f, st);
+  if (nt == 3) return launch_mid<F, KT, 3>(p, concat, slot + 2, slot + 26, f, st);
+  return launch_mid<F, KT, 4>(p, concat, slot + 4, slot + 28, f, st);
 }
 
 }  // namespace
@@ -184,26 +174,13 @@ int magat_gat_mean_launch(const float* ypre, float* y, long long M, int P, int F
   return magat_check_launch();
 }
 
-int magat_gat_mid_supported(int N, int G, int F, int K, int mode) {
-  if ((mode != MAGAT_MODE_KEYQUERY && mode != MAGAT_MODE_SIMILARITY) || G != F || (K != 2 && K != 3) || N > 128) return 0;
-  // GAT_Similarity at 128 features: the XR form where its float32 re-run exists (gat_dense_kernel's tiles end at 105 agents)
-  if (G == 128 && mode == MAGAT_MODE_SIMILARITY) return N >= 97 && N <= 105;
-  if (G == 128) {      // (gat_mfma.hip up to 102 agents; option GAT_WIDE_FROM: where this form takes over from the two launches)
-    const int from = magat_opt(MAGAT_OPT_GAT_WIDE_FROM);
-    return N >= (from < 103 ? 103 : from);
-  }
-  return N >= 33 && (G == 32 || G == 64);
-}
-
 // Hs: the f16 planes [2][NC][G] of the layer's pack (packed + magat_gat_f16_block_offset(NC, G))
 int magat_gat_mid_forward(const float* X, int ldx, const void* S, int s_is_f64, const float* Hs, int NC, const float* bias, float* Y,
                           int ldy, int B, int N, int G, int K, int P, int concat, int* range_flag, hipStream_t st,
-                          const float* x_scale, float* ypre, int ldpre, const float* wfrag, int cosine) {
-  if (cosine && (P != 1 || !range_flag || !magat_gat_mid_supported(N, G, G, K, MAGAT_MODE_SIMILARITY))) return MAGAT_ERR_UNSUPPORTED;
-  // (any N of the four-row-tile class is accepted here for G = 128; WHERE this form takes over is the dispatcher's decision,
-  //  magat_gat_mid_supported / option GAT_WIDE_FROM)
-  const bool wide_ok = G == 128 && N >= 97 && N <= 128 && (K == 2 || K == 3);
-  if (!wide_ok && !magat_gat_mid_supported(N, G, G, K, MAGAT_MODE_KEYQUERY)) return MAGAT_ERR_UNSUPPORTED;
+                          const float* x_scale, float* ypre, int ldpre, const float* wfrag, int cosine,
+                          const magat_gat::OneLaunch& form) {
+  // (at most four row tiles, the instantiated widths - 128 features as four row tiles only -, 16-byte reads of the X rows)
+  if (N > 128 || (G != 32 && G != 64 && G != 128) || (G == 128 && N < 97)) return MAGAT_ERR_UNSUPPORTED;
   if ((ldx & 3) || (reinterpret_cast<uintptr_t>(X) & 15)) return MAGAT_ERR_UNSUPPORTED;
   GatMidParams p;
   p.X = X; p.S = S; p.Hs = reinterpret_cast<const unsigned short*>(Hs); p.bias = bias; p.Y = Y;
@@ -217,17 +194,18 @@ int magat_gat_mid_forward(const float* X, int ldx, const void* S, int s_is_f64, 
   p.wfrag = reinterpret_cast<const char*>(wfrag);
   if (G == 128 && !wfrag) return MAGAT_ERR_NULL;
   if (cosine) {      // LDS-attribute slots: three row-tile counts per (width, taps) pair, then the two of the 128-wide form
-    if (G == 128) return K == 3 ? launch_mid_cos<128, 3, 4, true>(p, MAGAT_LDS_GATD_COS_0 + 12, st)
-                                : launch_mid_cos<128, 2, 4, true>(p, MAGAT_LDS_GATD_COS_0 + 13, st);
-    if (G == 32) return K == 3 ? launch_mid_cos_nt<32, 3>(p, MAGAT_LDS_GATD_COS_0, st) : launch_mid_cos_nt<32, 2>(p, MAGAT_LDS_GATD_COS_0 + 3, st);
-    return K == 3 ? launch_mid_cos_nt<64, 3>(p, MAGAT_LDS_GATD_COS_0 + 6, st) : launch_mid_cos_nt<64, 2>(p, MAGAT_LDS_GATD_COS_0 + 9, st);
+    if (G == 128) return K == 3 ? launch_mid_cos<128, 3, 4, true>(p, MAGAT_LDS_GATD_COS_0 + 12, form.cus, st)
+                                : launch_mid_cos<128, 2, 4, true>(p, MAGAT_LDS_GATD_COS_0 + 13, form.cus, st);
+    if (G == 32) return K == 3 ? launch_mid_cos_nt<32, 3>(p, MAGAT_LDS_GATD_COS_0, form.cus, st) : launch_mid_cos_nt<32, 2>(p, MAGAT_LDS_GATD_COS_0 + 3, form.cus, st);
+    return K == 3 ? launch_mid_cos_nt<64, 3>(p, MAGAT_LDS_GATD_COS_0 + 6, form.cus, st) : launch_mid_cos_nt<64, 2>(p, MAGAT_LDS_GATD_COS_0 + 9, form.cus, st);
   }
-  if (G == 128 && !concat && !p.Ypre) return MAGAT_ERR_WORKSPACE;      // (the 128-wide form always merges heads through Ypre)
+  // (the 128-wide form always merges heads through Ypre, a head split without concat too)
+  if ((G == 128 || form.hsplit) && !concat && !p.Ypre) return MAGAT_ERR_WORKSPACE;
   // LDS-attribute slots: 6 per (width, taps) pair (three tile counts x two merges), 24 more for their head-split forms, then the
   // eight of the 128-wide form (taps x merge, + head split)
   if (G == 128)
-    return K == 3 ? launch_mid<128, 3, 4, true>(p, concat, MAGAT_LDS_GATD_0 + 48, MAGAT_LDS_GATD_0 + 52, st)
-                  : launch_mid<128, 2, 4, true>(p, concat, MAGAT_LDS_GATD_0 + 50, MAGAT_LDS_GATD_0 + 54, st);
-  if (G == 32) return K == 3 ? launch_mid_nt<32, 3>(p, concat, MAGAT_LDS_GATD_0, st) : launch_mid_nt<32, 2>(p, concat, MAGAT_LDS_GATD_0 + 6, st);
-  return K == 3 ? launch_mid_nt<64, 3>(p, concat, MAGAT_LDS_GATD_0 + 12, st) : launch_mid_nt<64, 2>(p, concat, MAGAT_LDS_GATD_0 + 18, st);
+    return K == 3 ? launch_mid<128, 3, 4, true>(p, concat, MAGAT_LDS_GATD_0 + 48, MAGAT_LDS_GATD_0 + 52, form, st)
+                  : launch_mid<128, 2, 4, true>(p, concat, MAGAT_LDS_GATD_0 + 50, MAGAT_LDS_GATD_0 + 54, form, st);
+  if (G == 32) return K == 3 ? launch_mid_nt<32, 3>(p, concat, MAGAT_LDS_GATD_0, form, st) : launch_mid_nt<32, 2>(p, concat, MAGAT_LDS_GATD_0 + 6, form, st);
+  return K == 3 ? launch_mid_nt<64, 3>(p, concat, MAGAT_LDS_GATD_0 + 12, form, st) : launch_mid_nt<64, 2>(p, concat, MAGAT_LDS_GATD_0 + 18, form, st);
 }

@@ -1,6 +1,7 @@
 // The packed weights of a graph layer (magat_gat_pack_weights, gat_pack.hip): the ONE definition of their layout, for the kernels
 // that read the pack (gat_f32.hip, gat_csr_f32.hip, gat_train.hip) and the kernels that write it.  Included after magat_common.h.
 #pragma once
+#include "gat_route.h"
 
 // packed GAT weights: [Bt NC*G | colbias NC | pad to 4][bf16x3 planes 3*NC*G u16 | pad to 4 floats][f16x2 planes of
 // Bt * 2^8: 2*NC*G u16][float 2^-8][pad]: float offset of the f16 block
@@ -32,24 +33,21 @@ PackLayout pack_layout(int G, int F, int K, int P, int mode) {
     L.qoff = 0;
     L.uoff = P * G;
     L.c1off = L.c2off = 0;
-    L.NC = P * G + P * K * F;
   } else if (mode == MAGAT_MODE_GNN) {     // filter taps only
     L.qoff = 0;
     L.uoff = 0;
     L.c1off = L.c2off = 0;
-    L.NC = (P * K * F + 31) & ~31;
   } else {
     L.qoff = 0;
     L.uoff = 0;
     L.c1off = P * K * F;
     L.c2off = L.c1off + P;
-    L.NC = (L.c2off + P + 31) & ~31;   // multiple of 32: the maps GEMM can always use the bf16 matrix-core tiles
   }
+  L.NC = magat_gat::pack_columns(G, F, K, P, mode);      // (one definition: the dense route sizes Z by it)
   return L;
 }
 
-// feature widths the graph kernels are instantiated for
-bool supported_width(int w) { return w == 16 || w == 32 || w == 64 || w == 128 || w == 256; }
+using magat_gat::supported_width;      // feature widths the graph kernels are instantiated for
 }  // namespace
 
 // CALL with WW = the width W as a constant expression (W: a supported_width)

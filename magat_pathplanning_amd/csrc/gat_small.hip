@@ -14,6 +14,7 @@
 // L1 hits).  Values beyond the f16 range raise range_flag and the caller's predicated two-launch float32 form rewrites the output.
 #include "magat_common.h"
 #include "f16x3.h"
+#include "gat_route.h"
 
 namespace {
 
@@ -51,7 +52,7 @@ __global__ __launch_bounds__(256, F == 32 ? 2 : 1) void gat_small_cos_kernel(con
 
 
 template <int F, int KT>
-int launch_small(const GatSmallParams& p, int concat, int slot, hipStream_t st, bool cosine = false) {
+int launch_small(const GatSmallParams& p, int concat, int slot, int cus, hipStream_t st, bool cosine = false) {
   constexpr size_t wlds = 128 * (2 * F + 16) + 64 * 80 + 2 * F * 80;
   const size_t lds = 4 * (wlds + (cosine ? 128 : 0));
   if (cosine) concat = 1;
@@ -59,10 +60,6 @@ int launch_small(const GatSmallParams& p, int concat, int slot, hipStream_t st, 
                    : concat ? reinterpret_cast<const void*>(&gat_small_kernel<F, KT, true>)
                           : reinterpret_cast<const void*>(&gat_small_kernel<F, KT, false>);
   if (magat_ensure_dyn_lds(fn, slot + (concat ? 0 : 1), lds) != MAGAT_OK) return MAGAT_ERR_LAUNCH;
-  int cus = 256, dev = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-    cus = 256;
   // a wave per instance, four instances per workgroup
   long long blocks = ((long long)p.B + 3) / 4;
   const long long cap = (long long)cus * (lds <= 80 * 1024 ? 2 : 1);
@@ -77,25 +74,21 @@ int launch_small(const GatSmallParams& p, int concat, int slot, hipStream_t st, 
 
 }  // namespace
 
-int magat_gat_small_supported(int N, int G, int F, int K, int mode) {
-  return (mode == MAGAT_MODE_KEYQUERY || mode == MAGAT_MODE_SIMILARITY) && N >= 1 && N <= 32 && G == F && (G == 32 || G == 64) && (K == 2 || K == 3);
-}
-
 // Hs: the f16 planes [2][NC][G] of the layer's pack (packed + magat_gat_f16_block_offset(NC, G))
 int magat_gat_small_forward(const float* X, int ldx, const void* S, int s_is_f64, const unsigned* rmask_pre, const float* Hs,
                             int NC, const float* bias, float* Y, int ldy, int B, int N, int G, int K, int P, int concat,
-                            int* range_flag, hipStream_t st, const float* x_scale, int cosine) {
-  if (cosine && (P != 1 || !range_flag)) return MAGAT_ERR_UNSUPPORTED;      // (one head; tiny rows are served by the guard's re-run)
-  if (!magat_gat_small_supported(N, G, G, K, MAGAT_MODE_KEYQUERY)) return MAGAT_ERR_UNSUPPORTED;
-  if ((ldx & 3) || (reinterpret_cast<uintptr_t>(X) & 15)) return MAGAT_ERR_UNSUPPORTED;
+                            int* range_flag, hipStream_t st, const float* x_scale, int cosine, const magat_gat::OneLaunch& form) {
+  // (one 32-row tile per wave, the instantiated widths, 16-byte reads of the X rows)
+  if (N > 32 || (G != 32 && G != 64) || (ldx & 3) || (reinterpret_cast<uintptr_t>(X) & 15)) return MAGAT_ERR_UNSUPPORTED;
   GatSmallParams p;
   p.X = X; p.S = S; p.rmask_pre = rmask_pre; p.Hs = reinterpret_cast<const unsigned short*>(Hs); p.bias = bias; p.Y = Y;
   p.B = B; p.N = N; p.P = P; p.NC = NC; p.ldx = ldx; p.ldy = ldy; p.s_is_f64 = s_is_f64;
   p.range_flag = range_flag; p.x_scale = x_scale;
+  const int cus = form.cus;
   if (cosine) {
-    if (G == 32) return K == 3 ? launch_small<32, 3>(p, 1, MAGAT_LDS_GATS_COS_0, st, true) : launch_small<32, 2>(p, 1, MAGAT_LDS_GATS_COS_0 + 1, st, true);
-    return K == 3 ? launch_small<64, 3>(p, 1, MAGAT_LDS_GATS_COS_0 + 2, st, true) : launch_small<64, 2>(p, 1, MAGAT_LDS_GATS_COS_0 + 3, st, true);
+    if (G == 32) return K == 3 ? launch_small<32, 3>(p, 1, MAGAT_LDS_GATS_COS_0, cus, st, true) : launch_small<32, 2>(p, 1, MAGAT_LDS_GATS_COS_0 + 1, cus, st, true);
+    return K == 3 ? launch_small<64, 3>(p, 1, MAGAT_LDS_GATS_COS_0 + 2, cus, st, true) : launch_small<64, 2>(p, 1, MAGAT_LDS_GATS_COS_0 + 3, cus, st, true);
   }
-  if (G == 32) return K == 3 ? launch_small<32, 3>(p, concat, MAGAT_LDS_GATS_0, st) : launch_small<32, 2>(p, concat, MAGAT_LDS_GATS_0 + 2, st);
-  return K == 3 ? launch_small<64, 3>(p, concat, MAGAT_LDS_GATS_0 + 4, st) : launch_small<64, 2>(p, concat, MAGAT_LDS_GATS_0 + 6, st);
+  if (G == 32) return K == 3 ? launch_small<32, 3>(p, concat, MAGAT_LDS_GATS_0, cus, st) : launch_small<32, 2>(p, concat, MAGAT_LDS_GATS_0 + 2, cus, st);
+  return K == 3 ? launch_small<64, 3>(p, concat, MAGAT_LDS_GATS_0 + 4, cus, st) : launch_small<64, 2>(p, concat, MAGAT_LDS_GATS_0 + 6, cus, st);
 }

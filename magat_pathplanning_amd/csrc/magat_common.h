@@ -185,29 +185,32 @@ int magat_gat_csr_fused_forward(const uint16_t* X, const int* rowptr, const int*
                                 int P, hipStream_t st);
 int magat_cast_rows_if(const void* src, void* dst, int to_bf16, long long M, int width, int ld_src, int ld_dst, void* stream,
                        const int32_t* run_if);      // gat_csr_f32.hip: magat_cast_rows, predicated on a device flag (null = always)
-// one-launch KeyQuery layer for small graphs and narrow features (gat_small.hip: N <= 32, G = F in {32, 64}, K = 2 | 3)
-int magat_gat_small_supported(int N, int G, int F, int K, int mode);
+// The one-launch forms of the dense graph layer.  WHICH of them serves a call, and in what form (size class, pack, head split, CU
+// count), is decided by gat_route.h and handed over; they check only what guards their own memory accesses.
+namespace magat_gat { struct OneLaunch; }
+// small graphs and narrow features (gat_small.hip: N <= 32, G = F in {32, 64}, K = 2 | 3)
 int magat_gat_small_forward(const float* X, int ldx, const void* S, int s_is_f64, const unsigned* rmask_pre, const float* Hs,
                             int NC, const float* bias, float* Y, int ldy, int B, int N, int G, int K, int P, int concat,
                             int* range_flag, hipStream_t st, const float* x_scale,
-                            int cosine = 0);      // 1: GAT_Similarity's cosine scores (P = 1, range_flag required: tiny rows raise it)
-// one-launch KeyQuery layer for the published widths on graphs of 33 .. 128 agents (gat_mid.hip: G = F in {32, 64}, K = 2 | 3)
-int magat_gat_mid_supported(int N, int G, int F, int K, int mode);
+                            int cosine,      // 1: GAT_Similarity's cosine scores (P = 1, range_flag required: tiny rows raise it)
+                            const magat_gat::OneLaunch& form);
+// the published widths on graphs of 33 .. 128 agents (gat_mid.hip: G = F in {32, 64}; G = 128 on 97 .. 128 agents; K = 2 | 3)
 int magat_gat_mid_forward(const float* X, int ldx, const void* S, int s_is_f64, const float* Hs, int NC, const float* bias, float* Y,
                           int ldy, int B, int N, int G, int K, int P, int concat, int* range_flag, hipStream_t st,
                           const float* x_scale,
-                          float* ypre = nullptr, int ldpre = 0, const float* wfrag = nullptr,
-                          int cosine = 0);      // 1: GAT_Similarity's cosine scores (P = 1, range_flag required)
-      // head-mean scratch rows [B*N][P F]: lets few instances run a workgroup per head
-// one-launch KeyQuery layer on the matrix cores (gat_mfma.hip)
-int magat_gat_mfma_supported(int N, int G, int F, int K, int mode);
+                          float* ypre, int ldpre,      // head-mean scratch rows [B*N][P F]: lets few instances run a workgroup per head
+                          const float* wfrag,
+                          int cosine,      // 1: GAT_Similarity's cosine scores (P = 1, range_flag required)
+                          const magat_gat::OneLaunch& form);
+// 128 features on the matrix cores (gat_mfma.hip: N <= 102, K = 2 | 3)
 int magat_gat_mfma_forward(const float* X, int ldx, const void* S, int s_is_f64, const unsigned* rmask_pre,
                            const float* packed_frag, const float* bias, float* Y, int ldy, int B, int N, int K, int P,
                            int concat, int* range_flag, hipStream_t st,
-                           const float* x_scale = nullptr,       // device float: power-of-two scale of X's planes (null / 0 = 1)
-                           int mode = MAGAT_MODE_KEYQUERY,       // GAT_modified / GAT_origin: rank-1 scores (packed_frag: the rank-1 block)
-                           const float* kconst = nullptr,        // per head a1 . wb + a2 . wb (device floats), or null
-                           float* ypre = nullptr, int ldpre = 0); // head-mean scratch rows [B*N][>= 128 P]: lets few instances run a workgroup per head
+                           const float* x_scale,       // device float: power-of-two scale of X's planes (null / 0 = 1)
+                           int mode,                   // GAT_modified / GAT_origin: rank-1 scores (packed_frag: the rank-1 block)
+                           const float* kconst,        // per head a1 . wb + a2 . wb (device floats), or null
+                           float* ypre, int ldpre,     // head-mean scratch rows [B*N][>= 128 P]: lets few instances run a workgroup per head
+                           const magat_gat::OneLaunch& form);
 int magat_gat_mean_launch(const float* ypre, float* y, long long M, int P, int F, int ldpre, int ldy, hipStream_t st);      // gat_mid.hip
 
 // hoisted GAT maps Z [M][ldz >= NC] = X [M][G] @ Bt^T + colbias from the packed weights (gat_f32.hip): bf16x6 split when

@@ -117,12 +117,16 @@ def _dense_expect(lib, G, N, K, mode, concat, xoff, place):
     """(rc, form) the header states: form 'one' / 'mid' / 'two'"""
     if xoff:
         return UNSUPPORTED, None
+    # (tests/gat_route_restatement.py: the dispatcher restated; the form does not depend on the batch or the head count)
+    import gat_route_restatement as rr
+    r = rr.route(dict(B=1, N=N, G=G, F=G, K=K, P=1, mode=mode, concat=1 if concat else 0, attention=False, y_aligned=place != "odd",
+                      tail=False, tail_cout=0, tail_m=0, tail_k=0, opt=rr.DEFAULT_OPT, conv_direct=True, cus=256))
     one = bool(lib.magat_gat_one_launch_supported(N, G, G, K, mode, 1 if concat else 0)) and place != "odd"
-    if not lib.magat_gat_dense_supported(N, G, G):       # beyond the two-launch tiles: only the one-launch gat_mid form
-        return (OK, "mid") if one else (UNSUPPORTED, None)
-    if not one:
-        return OK, "two"
-    return OK, ("mid" if (G == 128 and N >= 103) or (G < 128 and N >= 33) else "one")
+    assert one == (r.get("form", "two_launch") != "two_launch")
+    assert bool(lib.magat_gat_dense_supported(N, G, G)) == rr.dense_supported(N, G, G)
+    if r["refusal"] != "none":       # beyond the two-launch tiles: only the one-launch gat_mid form
+        return UNSUPPORTED, None
+    return OK, {"two_launch": "two", "one_mid": "mid"}.get(r["form"], "one")
 
 
 @pytest.mark.parametrize("G,N,mode,K,P,concat,s64,B", DENSE,

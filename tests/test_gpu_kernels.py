@@ -233,7 +233,7 @@ def test_gat_layer_vs_reference_golden(gpu_device, tag_counts, path, want_att):
     """HIP GraphFilterBatchAttentional vs the outputs the real reference produced (tolerance: north star 1e-4;
     observed ~1e-6).  The fixtures' GSOs (oracle/make_golden.py tricky_gso) carry a directed edge pair, 5e-10 / -3e-9
     threshold entries, a NaN, an isolated node and float64 1/lambda_max values.  want_att=False is what inference runs by
-    default - for the shapes the one-launch matrix-core kernel covers (magat_gat_mfma_supported) the test asserts that it
+    default - for the shapes the one-launch matrix-core kernel covers (magat_gat_one_launch_supported) the test asserts that it
     is the kernel that ran; want_att=True also materialises (and checks) the attention tensor, which takes the two-launch
     form."""
     from magat_pathplanning_amd import GraphFilterBatchAttentional, GraphFilterBatchAttentional_Origin

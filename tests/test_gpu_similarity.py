@@ -11,6 +11,7 @@ import pytest
 import torch
 
 from conftest import golden_paths, load_layer_fixture, load_model_fixture
+import gat_route_restatement as rr
 from similarity_restatement import similarity_layer
 
 pytestmark = pytest.mark.gpu
@@ -88,8 +89,9 @@ def test_layer_vs_reference_golden(gpu_device, tag_counts, path, want_att):
     x = torch.from_numpy(z["x"]).to(gpu_device)
     S = torch.from_numpy(z["S"]).to(gpu_device)
     dense = bool(nat.lib().magat_gat_dense_supported(N, G, G))
-    assert dense == (not (G == 128 and N > 105))
+    assert dense == (not (G == 128 and N > 105)) and dense == rr.dense_supported(N, G, G)
     assert bool(nat.lib().magat_gat_one_launch_supported(N, G, G, K, nat.MODE_SIMILARITY, 1)) == _small(N, G, K)
+    assert rr.one_launch_supported(N, G, G, K, rr.SIMILARITY, rr.DEFAULT_OPT) == _small(N, G, K)      # (the dispatcher restated)
     one = _small(N, G, K) and not want_att      # (requests for the attention tensor take the two-launch form)
     tol = 1e-5 * max(1.0, float(np.abs(z["y"]).max()))
     for concat in (True, False):
