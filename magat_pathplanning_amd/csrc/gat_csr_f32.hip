@@ -17,6 +17,9 @@
 
 #include "magat_common.h"
 #include "gat_pack.h"
+#include "gat_csr_route.h"
+
+namespace cr = magat_csr;
 
 namespace {
 
@@ -325,43 +328,6 @@ __global__ void csr_k1_kernel(const CsrParams p) {
   }
 }
 
-
-// Largest N of the entries that transpose the GSO themselves (magat_hip.h: "any N <= 8190"): csr_transpose_kernel keeps
-// 2 N + 2 ints in LDS, under 64 KiB.  (The check once read `bytes > 64 KiB` and let N = 8191 - exactly 64 KiB - through.)
-constexpr int CSR_MAX_N = 8190;
-static_assert((2 * CSR_MAX_N + 2) * sizeof(int) < 64 * 1024 && (2 * (CSR_MAX_N + 1) + 2) * sizeof(int) >= 64 * 1024, "");
-
-struct WsLayout {
-  size_t status, z, cscptr, cscsrc, cscpos, csctmp, att, t0, t1, ytmp, order, xhat, total;
-};
-// the form with the maps inside the graph kernels (gat_csr_fused.hip): bf16 storage + the column view of magat_gso_csr_build
-bool csr_fused_form(size_t esz, bool have_csc, int G, int F, int K, int P, int mode, int concat) {
-  return esz == 2 && have_csc && magat_gat_csr_fused_supported(G, F, K, P, mode, concat);
-}
-WsLayout ws_layout(int B, int N, long long nnz, int G, int F, int K, int P, int mode, int concat,
-                   size_t esz = sizeof(float), bool have_csc = false) {
-  const PackLayout L = pack_layout(G, F, K, P, mode);
-  const bool fused = csr_fused_form(esz, have_csc, G, F, K, P, mode, concat);
-  WsLayout w;
-  size_t o = 0;
-  auto take = [&](size_t bytes) { size_t at = o; o += magat_align_up(bytes, 256); return at; };
-  w.status = take(256);              // range-guard status words of the maps GEMM (first bytes of the workspace)
-  w.z = take(fused ? 0 : (size_t)B * N * L.NC * esz);      // (the fused form has no maps in memory)
-  // (the column view: nothing is reserved for it when the caller brings the one magat_gso_csr_build made)
-  w.cscptr = take(have_csc ? 0 : (size_t)B * (N + 1) * sizeof(int));
-  w.cscsrc = take(have_csc ? 0 : (size_t)nnz * sizeof(int));
-  w.cscpos = take(have_csc ? 0 : (size_t)nnz * sizeof(int));
-  w.csctmp = take(have_csc ? 0 : (size_t)nnz * sizeof(int));
-  w.att = take((size_t)P * nnz * sizeof(float));
-  const size_t tb = K > 2 ? (size_t)B * N * P * F * esz : 0;
-  w.t0 = take(tb);
-  w.t1 = take(K > 3 ? tb : 0);
-  w.ytmp = take(concat ? 0 : (size_t)B * N * P * F * esz);
-  w.order = take(fused ? magat_gat_csr_fused_order_bytes(B, N) : 0);
-  w.xhat = take(mode == MAGAT_MODE_SIMILARITY ? (size_t)B * N * G * sizeof(float) : 0);      // normalised X rows (magat_gat_cos_prepare)
-  w.total = o;
-  return w;
-}
 
 // ---- LDS-tiled forms of the score and hop kernels for N <= 1024 (BASELINE config 5: N = 1000) ------------------------------
 // The per-edge gathers above read every neighbour row from L2 (256-512 B per edge and head: 3.6 GB per c5 step, the
@@ -774,15 +740,13 @@ __global__ __launch_bounds__(1024) void csr_tiled_hop_kernel(const CsrParams p, 
   }
 }
 
-template <typename ST>
-bool csr_tiled_ok(const CsrParams& p, int width, int which) {      // which: 1 = scores, 2 = hop (option CSR_TILED = bit mask)
-  return (magat_opt(MAGAT_OPT_CSR_TILED) & which) && p.N <= 1024 && p.N >= 8 && (width * (int)sizeof(ST)) % 128 == 0;
-}
-template <typename ST, int LPR>
-int launch_tiled(const CsrParams& p, int width, bool scores, hipStream_t st) {
+// The launchers take their grid from the Route (gat_csr_route.h) and refuse one that an unsigned launch cannot express.
+// (the 64-byte-slice tiled form - 512-thread workgroups, two per CU, option CSR_TILED bit 2 of rounds 2-4 - doubled the passes
+//  and their per-row bookkeeping and measured 27 % slower: removed in round 5; LPR = 8 is the one instantiated)
+template <typename ST, int LPR = 8>
+int run_tiled(const CsrParams& p, int width, bool scores, long long grid, hipStream_t st) {
   constexpr int RPS = 64 / LPR;
-  const long long grid = (long long)((p.B + MAGAT_NUM_XCD - 1) / MAGAT_NUM_XCD) * MAGAT_NUM_XCD * p.P;
-  if (grid > 0x7fffffffLL) return MAGAT_ERR_BAD_SHAPE;
+  if (grid > cr::kGridMax) return MAGAT_ERR_BAD_SHAPE;
   const size_t lds = (size_t)((p.N + RPS - 1) / RPS) * 1024 + TILED_SCRATCH;
   const void* fn = scores ? reinterpret_cast<const void*>(&csr_tiled_scores_kernel<ST, LPR>)
                           : reinterpret_cast<const void*>(&csr_tiled_hop_kernel<ST, LPR>);
@@ -797,37 +761,17 @@ int launch_tiled(const CsrParams& p, int width, bool scores, hipStream_t st) {
   magat_prof_end(pid, st);
   return magat_check_launch();
 }
-template <typename ST>
-int run_tiled(const CsrParams& p, int width, bool scores, hipStream_t st) {
-  // (the 64-byte-slice form - 512-thread workgroups, two per CU, option CSR_TILED bit 2 of rounds 2-4 - doubled the passes and
-  //  their per-row bookkeeping and measured 27 % slower: removed in round 5)
-  return launch_tiled<ST, 8>(p, width, scores, st);
-}
-
-template <int G, typename ST = float>
-int run_scores(const CsrParams& p, hipStream_t st) {
-  constexpr int LE = (G / 4) < 8 ? (G / 4) : 8;
-  const int rows = 256 / LE, tiles = (p.N + rows - 1) / rows;
-  const long long grid = (long long)((p.B + MAGAT_NUM_XCD - 1) / MAGAT_NUM_XCD) * MAGAT_NUM_XCD * p.P * tiles;
-  if (grid > 0x7fffffffLL) return MAGAT_ERR_BAD_SHAPE;
+template <typename KFn>
+int run_rows(KFn kern, const CsrParams& p, long long grid, hipStream_t st) {      // the per-edge score and hop kernels
+  if (grid > cr::kGridMax) return MAGAT_ERR_BAD_SHAPE;
   const int pid = magat_prof_begin(MAGAT_TAG_GAT_GRAPH, st);
-  hipLaunchKernelGGL((csr_scores_kernel<G, ST>), dim3((unsigned)grid), dim3(256), 0, st, p);
+  hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), 0, st, p);
   magat_prof_end(pid, st);
   return magat_check_launch();
 }
-template <int F, typename ST = float>
-int run_hop(const CsrParams& p, hipStream_t st) {
-  const int tiles = (p.N + 3) / 4;
-  const long long grid = (long long)((p.B + MAGAT_NUM_XCD - 1) / MAGAT_NUM_XCD) * MAGAT_NUM_XCD * p.P * tiles;
-  if (grid > 0x7fffffffLL) return MAGAT_ERR_BAD_SHAPE;
-  const int pid = magat_prof_begin(MAGAT_TAG_GAT_GRAPH, st);
-  hipLaunchKernelGGL((csr_hop_kernel<F, ST>), dim3((unsigned)grid), dim3(256), 0, st, p);
-  magat_prof_end(pid, st);
-  return magat_check_launch();
-}
-template <int F, typename ST = float>
-int run_k1(const CsrParams& p, hipStream_t st) {
-  hipLaunchKernelGGL((csr_k1_kernel<F, ST>), dim3(2048), dim3(256), 0, st, p);
+template <int F, typename ST>
+int run_k1(const CsrParams& p, long long grid, hipStream_t st) {
+  hipLaunchKernelGGL((csr_k1_kernel<F, ST>), dim3((unsigned)grid), dim3(256), 0, st, p);
   return magat_check_launch();
 }
 
@@ -854,17 +798,6 @@ __global__ void head_mean_relu_csr_kernel(const ST* __restrict__ ytmp, void* __r
   }
 }
 
-
-
-#define MAGAT_CSR_DISPATCH(WIDTH, FN, ST)                   \
-  switch (WIDTH) {                                         \
-    case 16: rc = FN<16, ST>(p, st); break;                \
-    case 32: rc = FN<32, ST>(p, st); break;                \
-    case 64: rc = FN<64, ST>(p, st); break;                \
-    case 128: rc = FN<128, ST>(p, st); break;              \
-    default: rc = FN<256, ST>(p, st);                      \
-  }
-
 // maps GEMM Z = X @ Bt^T + colbias in the storage type: fp32 (fp32 MFMA / bf16x6 split) or bf16 in, bf16 out
 // (one bf16 MFMA product per element pair, fp32 accumulate; weights = plane 0 of the packed bf16x3 block)
 template <typename ST>
@@ -876,7 +809,7 @@ int csr_maps_gemm<float>(const float* X, const float* packed, float* Z, int M, i
 }
 template <>
 int csr_maps_gemm<u16>(const u16* X, const float* packed, u16* Z, int M, int G, const PackLayout& L, void* stream, int32_t*) {
-  if ((L.NC % 32) || (G % 32)) return MAGAT_ERR_UNSUPPORTED;
+  // (NC and G are multiples of 32: the route refuses the call otherwise, REFUSE_BF16_MAPS)
   magat_conv_gemm_desc d = {};
   d.in = reinterpret_cast<const float*>(X);
   d.wt = packed + (((size_t)L.NC * (G + 1) + 3) & ~(size_t)3);     // bf16x3 planes; plane 0 = RNE bf16 of Bt
@@ -887,6 +820,89 @@ int csr_maps_gemm<u16>(const u16* X, const float* packed, u16* Z, int M, int G, 
   return magat_conv_gemm_f32(&d, stream);
 }
 
+int route_rc(const cr::Route& r) {
+  const cr::Code c = cr::refusal_code(r.refusal);
+  return c == cr::CODE_OK ? MAGAT_OK : c == cr::CODE_BAD_SHAPE ? MAGAT_ERR_BAD_SHAPE : MAGAT_ERR_UNSUPPORTED;
+}
+cr::RouteIn route_in(int B, int N, long long nnz, int G, int F, int K, int P, int mode, int concat, size_t esz, bool have_csc,
+                     cr::Pass pass) {
+  cr::RouteIn in = {};
+  in.B = B; in.N = N; in.nnz = nnz; in.G = G; in.F = F; in.K = K; in.P = P; in.mode = mode; in.concat = concat;
+  in.esz = (int)esz; in.have_csc = have_csc; in.pass = pass;
+  in.csr_tiled = magat_opt(MAGAT_OPT_CSR_TILED); in.csr_fused = magat_opt(MAGAT_OPT_CSR_FUSED);
+  return in;
+}
+
+// Where hop h writes: the ping-pong pair of the inference workspace, or block h of the T_k the training forward keeps
+// (T_k for k = K-2-h; `kept` = elements of a block).  Hop h > 0 reads what hop h - 1 wrote.
+struct HopBuffers {
+  void* buf[2];
+  size_t kept;
+  template <typename ST> ST* at(int h) const {
+    return kept ? static_cast<ST*>(buf[0]) + h * kept : static_cast<ST*>(buf[h & 1]);
+  }
+};
+
+// Transposition, scores / K = 1 and hops of a route, for the inference entries and the training forward alike
+template <typename ST>
+int csr_walk(const cr::Route& r, CsrParams p, int G, int F, int* csctmp, const HopBuffers& hb, hipStream_t st) {
+  int rc = MAGAT_OK;
+  if (r.k1 == cr::K1_ALONE) {
+    MAGAT_WIDTH_SWITCH(F, rc = (run_k1<WW, ST>(p, r.grid_k1, st)));
+    return rc;
+  }
+  if (r.transpose) {
+    const int pid = r.transpose_booked ? magat_prof_begin(MAGAT_TAG_GSO_CSR, st) : 0;
+    hipLaunchKernelGGL(csr_transpose_kernel, dim3((unsigned)r.grid_transpose), dim3(256), (size_t)(2 * p.N + 2) * sizeof(int), st,
+                       p.rowptr, p.colidx, const_cast<int*>(p.cscptr), csctmp, p.N);
+    hipLaunchKernelGGL(csr_sort_columns_kernel, dim3((unsigned)r.grid_sort), dim3(256), 0, st, p.rowptr, p.cscptr, csctmp,
+                       const_cast<int*>(p.cscsrc), const_cast<int*>(p.cscpos), p.N, (long long)p.B * p.N);
+    if (r.transpose_booked) magat_prof_end(pid, st);
+    if ((rc = magat_check_launch()) != MAGAT_OK) return rc;
+  }
+  if (r.scores == cr::GRAPH_TILED) rc = run_tiled<ST>(p, G, true, r.grid_scores, st);
+  else if (r.scores == cr::GRAPH_EDGE) MAGAT_WIDTH_SWITCH(G, rc = run_rows((csr_scores_kernel<WW, ST>), p, r.grid_scores, st));
+  if (rc != MAGAT_OK) return rc;
+  if (r.k1 == cr::K1_AFTER_SCORES) {
+    MAGAT_WIDTH_SWITCH(F, rc = (run_k1<WW, ST>(p, r.grid_k1, st)));
+    if (rc != MAGAT_OK) return rc;
+  }
+  // hops k = K-2 .. 0; the first reads U_{K-1} straight out of Z
+  for (int h = 0; h < r.hops; ++h) {
+    p.k = r.hops - 1 - h;
+    p.last = p.k == 0;
+    if (h == 0) {
+      p.Told = p.Z;                          // row (b*N+i): + i*NC, head: + head*K*F
+      p.told_off = p.uoff + (p.K - 1) * F;
+      p.told_ld = p.NC;
+      p.told_head_stride = p.K * F;
+    } else {
+      p.Told = hb.at<ST>(h - 1);
+      p.told_off = 0;
+      p.told_ld = p.P * F;
+      p.told_head_stride = F;
+    }
+    p.Tnew = hb.at<ST>(h);
+    if (r.hop_kind == cr::GRAPH_TILED) rc = run_tiled<ST>(p, F, false, r.grid_hop, st);
+    else MAGAT_WIDTH_SWITCH(F, rc = run_rows((csr_hop_kernel<WW, ST>), p, r.grid_hop, st));
+    if (rc != MAGAT_OK) return rc;
+  }
+  return MAGAT_OK;
+}
+
+CsrParams csr_params(const void* X, const void* Z, const int* rowptr, const int* colidx, const int* cscptr, const int* cscsrc,
+                     const int* cscpos, float* att, const float* bias, void* Y, int ldy, long long nnz, int B, int N, int G, int F,
+                     int K, int P, int mode) {
+  const PackLayout L = pack_layout(G, F, K, P, mode);
+  CsrParams p = {};
+  p.X = X; p.Z = Z; p.rowptr = rowptr; p.colidx = colidx; p.cscptr = cscptr; p.cscsrc = cscsrc; p.cscpos = cscpos;
+  p.att = att; p.bias = bias; p.Y = Y; p.ldy = ldy; p.nnz = nnz;
+  p.B = B; p.N = N; p.K = K; p.P = P; p.mode = mode;
+  p.NC = L.NC; p.qoff = L.qoff; p.uoff = L.uoff; p.c1off = L.c1off; p.c2off = L.c2off;
+  return p;
+}
+
+// Validate, ask gat_csr_route.h which launches the call takes, set up the parameters, walk
 template <typename ST>
 int csr_forward(const ST* X, const int* rowptr, const int* colidx, long long nnz, const float* packed,
                 const float* bias, void* Y, int ldy, float* att_opt, void* workspace, size_t workspace_bytes, int B,
@@ -894,122 +910,69 @@ int csr_forward(const ST* X, const int* rowptr, const int* colidx, long long nnz
                 const float* edge_vals = nullptr, const int* pre_cscptr = nullptr, const int* pre_cscsrc = nullptr,
                 const int* pre_cscpos = nullptr, int y_f32 = 0) {
   if (!X || !rowptr || !packed || !Y || (nnz > 0 && !colidx)) return MAGAT_ERR_NULL;
-  if (B <= 0 || N <= 0 || nnz < 0 || G <= 0 || F <= 0 || K <= 0 || P <= 0) return MAGAT_ERR_BAD_SHAPE;
-  if (mode < MAGAT_MODE_KEYQUERY || mode > MAGAT_MODE_SIMILARITY) return MAGAT_ERR_UNSUPPORTED;
-  const bool gnn = mode == MAGAT_MODE_GNN;     // fixed edge weights (the GSO values) instead of attention
-  // GAT_Similarity: float32 only, one head; the generic score and hop kernels run as KeyQuery on normalised operands
-  const bool cosine = mode == MAGAT_MODE_SIMILARITY;
-  if (cosine && (sizeof(ST) != sizeof(float) || P != 1 || G != F)) return MAGAT_ERR_UNSUPPORTED;
-  if (gnn && (P != 1 || (nnz > 0 && K > 1 && !edge_vals) || (G & 3))) return MAGAT_ERR_BAD_SHAPE;
-  if ((!gnn && G != F) || !supported_width(F)) return MAGAT_ERR_UNSUPPORTED;
-  if (N > CSR_MAX_N) return MAGAT_ERR_UNSUPPORTED;
-  const int width = concat ? P * F : F;
-  if (ldy < width || (ldy & 3)) return MAGAT_ERR_BAD_SHAPE;
-  // X rows are read in 16-byte pieces (the maps GEMMs, the range guard's float32 re-run, the fused bf16 kernels): an X that is
-  // not on a 16-byte boundary is refused before anything is launched (magat_hip.h, "Alignment")
-  if (reinterpret_cast<uintptr_t>(X) & 15) return MAGAT_ERR_UNSUPPORTED;
   const bool have_csc = pre_cscptr && pre_cscsrc && pre_cscpos;     // made by magat_gso_csr_build (once per GSO)
-  const WsLayout w = ws_layout(B, N, nnz, G, F, K, P, mode, concat, sizeof(ST), have_csc);
+  cr::RouteIn in = route_in(B, N, nnz, G, F, K, P, mode, concat, sizeof(ST), have_csc, cr::PASS_INFER);
+  in.ldy = ldy; in.attention = att_opt != nullptr; in.edge_vals = edge_vals != nullptr; in.y_f32 = y_f32 != 0;
+  in.x_aligned = (reinterpret_cast<uintptr_t>(X) & 15) == 0;
+  in.cus = gat_device_cus();
+  const cr::Route r = cr::route(in);
+  if (r.refusal != cr::REFUSE_NONE && r.refusal != cr::REFUSE_BF16_MAPS) return route_rc(r);
+  const cr::Workspace& w = r.ws;
   if (!workspace || (reinterpret_cast<uintptr_t>(workspace) & 255) || workspace_bytes < w.total)
     return MAGAT_ERR_WORKSPACE;
+  if (r.refusal != cr::REFUSE_NONE) return route_rc(r);
   hipStream_t st = static_cast<hipStream_t>(stream);
   char* ws = static_cast<char*>(workspace);
-  const PackLayout L = pack_layout(G, F, K, P, mode);
   ST* Z = reinterpret_cast<ST*>(ws + w.z);
-  int* cscptr = have_csc ? const_cast<int*>(pre_cscptr) : reinterpret_cast<int*>(ws + w.cscptr);
-  int* cscsrc = have_csc ? const_cast<int*>(pre_cscsrc) : reinterpret_cast<int*>(ws + w.cscsrc);
-  int* cscpos = have_csc ? const_cast<int*>(pre_cscpos) : reinterpret_cast<int*>(ws + w.cscpos);
+  const int* cscptr = have_csc ? pre_cscptr : reinterpret_cast<int*>(ws + w.cscptr);
+  const int* cscsrc = have_csc ? pre_cscsrc : reinterpret_cast<int*>(ws + w.cscsrc);
+  const int* cscpos = have_csc ? pre_cscpos : reinterpret_cast<int*>(ws + w.cscpos);
+  const bool gnn = mode == MAGAT_MODE_GNN, cosine = mode == MAGAT_MODE_SIMILARITY;
   float* att = gnn ? const_cast<float*>(edge_vals) : (att_opt ? att_opt : reinterpret_cast<float*>(ws + w.att));
-  ST* tbuf[2] = {reinterpret_cast<ST*>(ws + w.t0), reinterpret_cast<ST*>(ws + w.t1)};
   ST* Ytmp = reinterpret_cast<ST*>(ws + w.ytmp);
 
-  if (csr_fused_form(sizeof(ST), have_csc, G, F, K, P, mode, concat)) {
+  if (r.fused) {
     // maps on the matrix cores inside the score / hop kernels: Q and U never exist in memory (gat_csr_fused.hip)
     return magat_gat_csr_fused_forward(reinterpret_cast<const uint16_t*>(X), rowptr, colidx, cscptr, cscsrc, cscpos, nnz,
-                                                packed + magat_gat_csr_fused_offset(L.NC, G), bias, Y, ldy, y_f32,
+                                                packed + magat_gat_csr_fused_offset(r.NC, G), bias, Y, ldy, y_f32,
                                                 reinterpret_cast<float*>(ws + w.att), att_opt,
-                                                reinterpret_cast<int*>(ws + w.order), B, N, P, st);
+                                                reinterpret_cast<int*>(ws + w.order), B, N, P, (int)r.grid_fused_scores,
+                                                (int)r.grid_fused_hop, st);
     // (MAGAT_ERR_UNSUPPORTED before any launch: result rows / bias not 16-byte aligned, ldy not a multiple of 8 bf16 / 4 float32
     //  elements - magat_hip.h "Alignment" (2); the workspace the caller sized for this form holds no maps, so there is no
     //  fall-through to the unfused kernels)
   }
-  // (GAT_Similarity: float32 MFMA maps, as in gat_f32.hip - the direction of a tiny agent's q_j must survive)
-  int rc = cosine ? magat_gat_maps_gemm(reinterpret_cast<const float*>(X), packed, reinterpret_cast<float*>(Z), B * N, G, L.NC, L.NC,
-                                        stream, 0, nullptr, 1)
-                  : csr_maps_gemm<ST>(X, packed, Z, B * N, G, L, stream, reinterpret_cast<int32_t*>(ws + w.status));
+  const PackLayout L = pack_layout(G, F, K, P, mode);
+  int rc = r.maps == cr::MAPS_F32 ? magat_gat_maps_gemm(reinterpret_cast<const float*>(X), packed, reinterpret_cast<float*>(Z), B * N, G,
+                                                       L.NC, L.NC, stream, 0, nullptr, 1)
+                                  : csr_maps_gemm<ST>(X, packed, Z, B * N, G, L, stream, reinterpret_cast<int32_t*>(ws + w.status));
   if (rc != MAGAT_OK) return rc;
-  if (cosine) {
+  const void* Xs = X;      // what the scores read as x_i (the taps come from Z)
+  if (r.prepare) {
     rc = magat_gat_cos_prepare(reinterpret_cast<const float*>(X), reinterpret_cast<float*>(Z), reinterpret_cast<float*>(ws + w.xhat),
                                (long long)B * N, G, L.qoff, L.NC, 0, stream);
     if (rc != MAGAT_OK) return rc;
-    X = reinterpret_cast<const ST*>(ws + w.xhat);      // (read below for the scores' x_i only: the taps come from Z)
-    mode = MAGAT_MODE_KEYQUERY;
+    Xs = ws + w.xhat;
   }
+  // (the per-head rows of the mean form stay in the storage type)
+  CsrParams p = csr_params(Xs, Z, rowptr, colidx, cscptr, cscsrc, cscpos, att, bias, concat ? Y : static_cast<void*>(Ytmp),
+                           concat ? ldy : P * F, nnz, B, N, G, F, K, P, cosine ? MAGAT_MODE_KEYQUERY : mode);
+  p.concat = concat; p.y_f32 = concat ? y_f32 : 0; p.act_relu = r.act_relu;
+  const HopBuffers hb = {{ws + w.t0, ws + w.t1}, 0};
+  rc = csr_walk<ST>(r, p, G, F, reinterpret_cast<int*>(ws + w.csctmp), hb, st);
+  if (rc != MAGAT_OK || !r.head_mean) return rc;
+  const int pid = magat_prof_begin(MAGAT_TAG_HEAD_MEAN, st);
+  hipLaunchKernelGGL((head_mean_relu_csr_kernel<ST>), dim3((unsigned)r.grid_mean), dim3(256), 0, st, Ytmp, Y, (long long)B * N, P, F,
+                     ldy, y_f32);
+  magat_prof_end(pid, st);
+  return magat_check_launch();
+}
 
-  CsrParams p = {};
-  p.X = X; p.Z = Z; p.rowptr = rowptr; p.colidx = colidx; p.cscptr = cscptr; p.cscsrc = cscsrc; p.cscpos = cscpos;
-  p.att = att; p.bias = bias; p.Y = concat ? Y : static_cast<void*>(Ytmp); p.ldy = concat ? ldy : P * F;
-  p.y_f32 = concat ? y_f32 : 0;         // (the per-head rows of the mean form stay in the storage type)
-  p.B = B; p.N = N; p.K = K; p.P = P; p.mode = mode; p.concat = concat; p.nnz = nnz;
-  p.act_relu = gnn ? 0 : concat;        // GraphFilterBatch has no nonlinearity of its own
-  p.NC = L.NC; p.qoff = L.qoff; p.uoff = L.uoff; p.c1off = L.c1off; p.c2off = L.c2off;
-
-  if (K == 1 && (!att_opt || gnn)) {
-    MAGAT_CSR_DISPATCH(F, run_k1, ST)
-    if (rc != MAGAT_OK) return rc;
-  } else {
-    if (K > 1 && !have_csc) {
-      const int pid = magat_prof_begin(MAGAT_TAG_GSO_CSR, st);
-      int* csctmp = reinterpret_cast<int*>(ws + w.csctmp);
-      hipLaunchKernelGGL(csr_transpose_kernel, dim3(B), dim3(256), (size_t)(2 * N + 2) * sizeof(int), st, rowptr, colidx,
-                         cscptr, csctmp, N);
-      const long long cols = (long long)B * N;
-      hipLaunchKernelGGL(csr_sort_columns_kernel, dim3((unsigned)((cols + 3) / 4)), dim3(256), 0, st, rowptr, cscptr,
-                         csctmp, cscsrc, cscpos, N, cols);
-      magat_prof_end(pid, st);
-      if ((rc = magat_check_launch()) != MAGAT_OK) return rc;
-    }
-    if (!gnn) {
-      if (mode == MAGAT_MODE_KEYQUERY && !cosine && csr_tiled_ok<ST>(p, G, 1)) rc = run_tiled<ST>(p, G, true, st);
-      else { MAGAT_CSR_DISPATCH(G, run_scores, ST) }
-      if (rc != MAGAT_OK) return rc;
-    }
-    if (K == 1) {
-      MAGAT_CSR_DISPATCH(F, run_k1, ST)
-      if (rc != MAGAT_OK) return rc;
-    }
-    // hops k = K-2 .. 0; the first reads U_{K-1} straight out of Z
-    for (int k = K - 2, h = 0; k >= 0; --k, ++h) {
-      p.k = k;
-      p.last = k == 0;
-      if (h == 0) {
-        p.Told = Z;                          // row (b*N+i): + i*NC, head: + head*K*F
-        p.told_off = L.uoff + (K - 1) * F;
-        p.told_ld = L.NC;
-        p.told_head_stride = K * F;
-      } else {
-        p.Told = tbuf[(h - 1) & 1];
-        p.told_off = 0;
-        p.told_ld = P * F;
-        p.told_head_stride = F;
-      }
-      p.Tnew = tbuf[h & 1];
-      if (!cosine && csr_tiled_ok<ST>(p, F, 2)) rc = run_tiled<ST>(p, F, false, st);
-      else { MAGAT_CSR_DISPATCH(F, run_hop, ST) }
-      if (rc != MAGAT_OK) return rc;
-    }
-  }
-  if (!concat) {
-    const long long M = (long long)B * N;
-    long long blocks = (M * (F / 4) + 255) / 256;
-    if (blocks > 4096) blocks = 4096;
-    const int pid = magat_prof_begin(MAGAT_TAG_HEAD_MEAN, st);
-    hipLaunchKernelGGL((head_mean_relu_csr_kernel<ST>), dim3((unsigned)blocks), dim3(256), 0, st, Ytmp, Y, M, P, F, ldy,
-                       y_f32);
-    magat_prof_end(pid, st);
-    return magat_check_launch();
-  }
-  return MAGAT_OK;
+// the three *_workspace_bytes exports: the layout's total, 0 for a call without dimensions
+size_t ws_bytes(int B, int N, long long nnz, int G, int F, int K, int P, int mode, int concat, size_t esz, bool have_csc) {
+  if (!cr::dims_ok(B, N, nnz, K, P, G, F)) return 0;
+  const cr::RouteIn in = route_in(B, N, nnz, G, F, K, P, mode, concat, esz, have_csc, cr::PASS_INFER);
+  return cr::workspace(in, cr::fused_form(in)).total;
 }
 
 }  // namespace
@@ -1078,20 +1041,16 @@ int magat_cast_rows_if(const void* src, void* dst, int to_bf16, long long M, int
 
 extern "C" size_t magat_gat_csr_workspace_bytes(int B, int N, long long nnz, int G, int F, int K, int P, int mode,
                                                 int concat) {
-  if (B <= 0 || N <= 0 || nnz < 0 || G <= 0 || F <= 0 || K <= 0 || P <= 0) return 0;
-  return ws_layout(B, N, nnz, G, F, K, P, mode, concat).total;
+  return ws_bytes(B, N, nnz, G, F, K, P, mode, concat, sizeof(float), false);
 }
 extern "C" size_t magat_gat_csr_bf16_workspace_bytes(int B, int N, long long nnz, int G, int F, int K, int P, int mode,
                                                      int concat) {
-  if (B <= 0 || N <= 0 || nnz < 0 || G <= 0 || F <= 0 || K <= 0 || P <= 0) return 0;
-  return ws_layout(B, N, nnz, G, F, K, P, mode, concat, sizeof(u16)).total;
+  return ws_bytes(B, N, nnz, G, F, K, P, mode, concat, sizeof(u16), false);
 }
-
 // workspace of the *_csc_* entry points (the caller brings the column view: no transpose scratch)
 extern "C" size_t magat_gat_csc_workspace_bytes(int B, int N, long long nnz, int G, int F, int K, int P, int mode,
                                                 int concat, int bf16) {
-  if (B <= 0 || N <= 0 || nnz < 0 || G <= 0 || F <= 0 || K <= 0 || P <= 0) return 0;
-  return ws_layout(B, N, nnz, G, F, K, P, mode, concat, bf16 ? sizeof(u16) : sizeof(float), true).total;
+  return ws_bytes(B, N, nnz, G, F, K, P, mode, concat, bf16 ? sizeof(u16) : sizeof(float), true);
 }
 
 extern "C" int magat_gat_forward_csr_f32(const float* X, const int* rowptr, const int* colidx, long long nnz,
@@ -1157,57 +1116,24 @@ static int train_forward(const float* X, const int* rowptr, const int* colidx, l
   if (!X || !rowptr || !packed || !Ypre || !att || !Z || !cscptr || !cscsrc || !cscpos || !csctmp) return MAGAT_ERR_NULL;
   if (nnz > 0 && !colidx) return MAGAT_ERR_NULL;
   if (K > 2 && !T) return MAGAT_ERR_NULL;
-  if (B <= 0 || N <= 0 || nnz < 0 || K <= 0 || P <= 0) return MAGAT_ERR_BAD_SHAPE;
-  if (mode < MAGAT_MODE_KEYQUERY || mode > MAGAT_MODE_GAT_ORIGIN) return MAGAT_ERR_UNSUPPORTED;
-  if (G != F || !supported_width(G)) return MAGAT_ERR_UNSUPPORTED;
-  if (N > CSR_MAX_N) return MAGAT_ERR_UNSUPPORTED;
+  const cr::Route r = cr::route(route_in(B, N, nnz, G, F, K, P, mode, 1, sizeof(float), false, Xhat ? cr::PASS_TRAIN_COS : cr::PASS_TRAIN));
+  if (r.refusal != cr::REFUSE_NONE) return route_rc(r);
   const long long M = (long long)B * N;
-  // sizes the launches below cannot express (the maps GEMM takes its row count as an int; the hop grid is the largest), refused
-  // here and not behind the maps GEMM
-  if (M > 0x7fffffffLL || (long long)((B + MAGAT_NUM_XCD - 1) / MAGAT_NUM_XCD) * MAGAT_NUM_XCD * P * ((N + 3) / 4) > 0x7fffffffLL)
-    return MAGAT_ERR_BAD_SHAPE;
-  hipStream_t st = static_cast<hipStream_t>(stream);
   const PackLayout L = pack_layout(G, F, K, P, mode);
-  // float32 MFMA maps: Z is kept for the backward, and with caller-owned buffers there is no status word for a guarded
-  // split GEMM (the maps are 5 % of a training step either way)
   int rc = magat_gat_maps_gemm(X, packed, Z, (int)M, G, L.NC, L.NC, stream, 0, nullptr, 1);
   if (rc != MAGAT_OK) return rc;
-  if (Xhat) {      // cosine scores = KeyQuery scores of the normalised operands: q^ in place in Z, x^ in Xhat, the norms kept
+  if (r.prepare) {      // q^ in place in Z, x^ in Xhat, the norms kept
     magat_form_note(MAGAT_FORM_GAT_COS_TRAIN);
     rc = magat_gat_cos_prepare(X, Z, Xhat, M, G, L.qoff, L.NC, 0, stream, nullptr, norms);
     if (rc != MAGAT_OK) return rc;
     X = Xhat;      // (read below for the scores' x_i only: the taps come from Z)
   }
-  CsrParams p = {};
-  p.X = X; p.Z = Z; p.rowptr = rowptr; p.colidx = colidx; p.cscptr = cscptr; p.cscsrc = cscsrc; p.cscpos = cscpos;
-  p.att = att; p.bias = bias; p.Y = Ypre; p.ldy = P * F;
-  p.B = B; p.N = N; p.K = K; p.P = P; p.mode = mode; p.concat = 1; p.act_relu = 0; p.nnz = nnz;
-  p.NC = L.NC; p.qoff = L.qoff; p.uoff = L.uoff; p.c1off = L.c1off; p.c2off = L.c2off;
-  hipLaunchKernelGGL(csr_transpose_kernel, dim3(B), dim3(256), (size_t)(2 * N + 2) * sizeof(int), st, rowptr, colidx,
-                     cscptr, csctmp, N);
-  hipLaunchKernelGGL(csr_sort_columns_kernel, dim3((unsigned)((M + 3) / 4)), dim3(256), 0, st, rowptr, cscptr, csctmp,
-                     cscsrc, cscpos, N, M);
-  if ((rc = magat_check_launch()) != MAGAT_OK) return rc;
-  MAGAT_WIDTH_SWITCH(G, rc = run_scores<WW>(p, st));
-  if (rc != MAGAT_OK) return rc;
-  if (K == 1) {
-    MAGAT_WIDTH_SWITCH(F, rc = run_k1<WW>(p, st));
-    return rc;
-  }
-  for (int k = K - 2, h = 0; k >= 0; --k, ++h) {
-    p.k = k;
-    p.last = k == 0;
-    if (h == 0) {
-      p.Told = Z + L.uoff + (K - 1) * F; p.told_ld = L.NC; p.told_head_stride = K * F;
-    } else {
-      p.Told = T + (size_t)(h - 1) * M * P * F; p.told_ld = P * F; p.told_head_stride = F;
-    }
-    p.Tnew = T ? T + (size_t)h * M * P * F : nullptr;     // T_k for k = K-2-h (kept for the backward)
-    MAGAT_WIDTH_SWITCH(F, rc = run_hop<WW>(p, st));
-    if (rc != MAGAT_OK) return rc;
-  }
-  return MAGAT_OK;
+  CsrParams p = csr_params(X, Z, rowptr, colidx, cscptr, cscsrc, cscpos, att, bias, Ypre, P * F, nnz, B, N, G, F, K, P, mode);
+  p.concat = 1;
+  const HopBuffers hb = {{T, nullptr}, (size_t)M * P * F};
+  return csr_walk<float>(r, p, G, F, csctmp, hb, static_cast<hipStream_t>(stream));
 }
+
 
 extern "C" int magat_gat_train_forward_f32(const float* X, const int* rowptr, const int* colidx, long long nnz,
                                            const float* packed, const float* bias, float* Ypre, float* att, float* Z,

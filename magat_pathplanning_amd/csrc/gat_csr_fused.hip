@@ -25,6 +25,7 @@
 // One wave per SIMD (all 512 registers: q' of four heads is 128, the hop's accumulators of two heads 128), latency hidden by
 // a two-deep software pipeline (indices two slots ahead, rows one slot ahead).
 #include "magat_common.h"
+#include "gat_csr_route.h"
 
 typedef unsigned short u16;
 typedef unsigned int fu32x4 __attribute__((ext_vector_type(4)));
@@ -162,6 +163,7 @@ __global__ __launch_bounds__(1024) void csr_rank_kernel(const int* __restrict__ 
 #define FUSED_WAVES_N 8
 #endif
 constexpr int FUSED_WAVES = FUSED_WAVES_N, FUSED_THREADS = 64 * FUSED_WAVES;
+static_assert(FUSED_WAVES == magat_csr::kFusedWaves, "gat_csr_route.h sizes the grids by it");
 
 // which (instance, 32-row group) a wave works on in step s of its workgroup's persistent loop
 struct Item {
@@ -621,14 +623,6 @@ __global__ void csr_fused_att_out_kernel(const float* __restrict__ a, float* __r
   }
 }
 
-int device_cus() {
-  int dev = 0, cus = 0;
-  if (hipGetDevice(&dev) != hipSuccess ||
-      hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || cus <= 0)
-    cus = 256;
-  return cus;
-}
-
 }  // namespace
 
 #ifdef FUSED_STAMPS
@@ -636,22 +630,17 @@ static long long* g_fused_dbg = nullptr;
 extern "C" int magat_csr_fused_set_debug(long long* buf) { g_fused_dbg = buf; return MAGAT_OK; }
 #endif
 
-int magat_gat_csr_fused_supported(int G, int F, int K, int P, int mode, int concat) {
-  return magat_opt(MAGAT_OPT_CSR_FUSED) && mode == MAGAT_MODE_KEYQUERY && K == 2 && G == 128 && F == 128 && concat &&
-         (P == 1 || P == 2 || P == 4);
-}
-
 int magat_gat_csr_fused_pack(const float* Bt, void* frag_out, int P, hipStream_t st) {
   hipLaunchKernelGGL(csr_fused_pack_kernel, dim3(192), dim3(256), 0, st, Bt, static_cast<u16*>(frag_out), P);
   return magat_check_launch();
 }
 
-size_t magat_gat_csr_fused_order_bytes(int B, int N) { return (size_t)2 * B * N * sizeof(int); }
-
+// Whether this form serves a call, and its two grids, are decided by gat_csr_route.h (a workgroup per CU of the instance's XCD at
+// the most, the hop kernel's split into head pairs).  Checked here: what guards this file's own memory accesses.
 int magat_gat_csr_fused_forward(const uint16_t* X, const int* rowptr, const int* colidx, const int* cscptr, const int* cscsrc,
                                 const int* cscpos, long long nnz, const void* frags, const float* bias, void* Y, int ldy,
-                                int y_f32, float* att, float* att_opt, int* order, int B, int N, int P, hipStream_t st) {
-  if (!(P == 1 || P == 2 || P == 4)) return MAGAT_ERR_UNSUPPORTED;
+                                int y_f32, float* att, float* att_opt, int* order, int B, int N, int P, int grid_scores, int grid_hop,
+                                hipStream_t st) {
   if ((ldy & (y_f32 ? 3 : 7)) || (reinterpret_cast<uintptr_t>(Y) & 15) || (bias && (reinterpret_cast<uintptr_t>(bias) & 15)))
     return MAGAT_ERR_UNSUPPORTED;
   FusedParams p = {};
@@ -670,18 +659,14 @@ int magat_gat_csr_fused_forward(const uint16_t* X, const int* rowptr, const int*
     magat_prof_end(pid, st);
     if (magat_check_launch() != MAGAT_OK) return MAGAT_ERR_LAUNCH;
   }
-  const int per_xcd = device_cus() / MAGAT_NUM_XCD > 0 ? device_cus() / MAGAT_NUM_XCD : 1;
-  const int ng = (N + 31) / 32, nchunk = (ng + FUSED_WAVES - 1) / FUSED_WAVES;
-  const int items = ((B + MAGAT_NUM_XCD - 1) / MAGAT_NUM_XCD) * nchunk;
   {
-    const int wgx = items < per_xcd ? items : per_xcd;
     const size_t lds = (size_t)P * 32768;
     const void* fn = P == 4 ? reinterpret_cast<const void*>(&csr_fused_scores_kernel<4>)
                    : P == 2 ? reinterpret_cast<const void*>(&csr_fused_scores_kernel<2>)
                             : reinterpret_cast<const void*>(&csr_fused_scores_kernel<1>);
     if (magat_ensure_dyn_lds(fn, MAGAT_LDS_CSR_FUSED_A + (P == 4 ? 2 : P == 2 ? 1 : 0), lds) != MAGAT_OK) return MAGAT_ERR_LAUNCH;
     const int pid = magat_prof_begin(MAGAT_TAG_GAT_GRAPH, st);
-    const dim3 grid(MAGAT_NUM_XCD * wgx), block(FUSED_THREADS);
+    const dim3 grid(grid_scores), block(FUSED_THREADS);
     if (P == 4) hipLaunchKernelGGL((csr_fused_scores_kernel<4>), grid, block, lds, st, p);
     else if (P == 2) hipLaunchKernelGGL((csr_fused_scores_kernel<2>), grid, block, lds, st, p);
     else hipLaunchKernelGGL((csr_fused_scores_kernel<1>), grid, block, lds, st, p);
@@ -692,16 +677,13 @@ int magat_gat_csr_fused_forward(const uint16_t* X, const int* rowptr, const int*
 #ifdef FUSED_STAMPS
     if (p.dbg) p.dbg += 8 * FUSED_WAVES * 4096;      // (the hop kernel's stamps behind the score kernel's)
 #endif
-    const int HP = P >= 2 ? 2 : 1, ngrp = P / HP;
-    int per = per_xcd / ngrp;
-    if (per < 1) per = 1;
-    const int wgx = ngrp * (items < per ? items : per);
+    const int HP = P >= 2 ? 2 : 1;
     const size_t lds = (size_t)HP * 65536 + (size_t)FUSED_WAVES * 4096;      // weights + the row-store stage of every wave
     const void* fn = HP == 2 ? reinterpret_cast<const void*>(&csr_fused_hop_kernel<2>)
                              : reinterpret_cast<const void*>(&csr_fused_hop_kernel<1>);
     if (magat_ensure_dyn_lds(fn, MAGAT_LDS_CSR_FUSED_B + (HP == 2 ? 1 : 0), lds) != MAGAT_OK) return MAGAT_ERR_LAUNCH;
     const int pid = magat_prof_begin(MAGAT_TAG_GAT_GRAPH, st);
-    const dim3 grid(MAGAT_NUM_XCD * wgx), block(FUSED_THREADS);
+    const dim3 grid(grid_hop), block(FUSED_THREADS);
     if (HP == 2) hipLaunchKernelGGL((csr_fused_hop_kernel<2>), grid, block, lds, st, p);
     else hipLaunchKernelGGL((csr_fused_hop_kernel<1>), grid, block, lds, st, p);
     magat_prof_end(pid, st);

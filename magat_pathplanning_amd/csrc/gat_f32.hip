@@ -1380,6 +1380,8 @@ int run_head_mean(const GatCall& c, const gr::Route& r) {
   return magat_check_launch() != MAGAT_OK ? MAGAT_ERR_LAUNCH : MAGAT_OK;
 }
 
+}  // namespace
+
 // compute units of the CURRENT device (a cheap attribute query, no cached process-wide value: one process may drive several)
 int gat_device_cus() {
   int cus = 256, dev = 0;
@@ -1388,7 +1390,6 @@ int gat_device_cus() {
     cus = 256;
   return cus;
 }
-}  // namespace
 
 // Validate, ask gat_route.h which launches the call takes, run them.  tail / tail_done: magat_gat_forward_tail_f32 (below)
 static int gat_forward_impl(const float* X, const void* S, int s_is_f64, const float* packed, const float* bias, float* Y, int ldy,

@@ -2,6 +2,7 @@
 // forward kernels and lives with them in gat_csr_f32.hip).
 #include "magat_common.h"
 #include "gat_pack.h"
+#include "gat_csr_route.h"
 #include "gat_cos_parts.h"
 
 // =====================================================================================================
@@ -240,15 +241,14 @@ __global__ void gnn_bwd_seed_kernel(const float* __restrict__ dY, float* __restr
   }
 }
 
-// workgroups of a wave-per-row launch: whole XCD rounds of instances, `per_instance_factor` x 4-row tiles each
-long long rows_grid(int B, int N, int per_instance_factor) {
-  return (long long)((B + MAGAT_NUM_XCD - 1) / MAGAT_NUM_XCD) * MAGAT_NUM_XCD * per_instance_factor * ((N + 3) / 4);
-}
+using magat_csr::rows_grid;      // workgroups of a wave-per-row launch (gat_csr_route.h)
+using magat_csr::dims_ok;
+using magat_csr::kGridMax;
 
 template <int W, typename KFn>
 int launch_rows(KFn kern, const TrainParams& p, int per_instance_factor, hipStream_t st) {
   const long long grid = rows_grid(p.B, p.N, per_instance_factor);
-  if (grid > 0x7fffffffLL) return MAGAT_ERR_BAD_SHAPE;
+  if (grid > kGridMax) return MAGAT_ERR_BAD_SHAPE;
   hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(256), 0, st, p);
   return magat_check_launch();
 }
@@ -263,11 +263,11 @@ extern "C" int magat_gat_train_backward_f32(const float* dYpre, const float* X, 
   if (!dYpre || !X || !Z || !att || !rowptr || !cscptr || !cscsrc || !cscpos || !dZ || !dXd || !datt) return MAGAT_ERR_NULL;
   if (nnz > 0 && !colidx) return MAGAT_ERR_NULL;
   if (K > 2 && !T) return MAGAT_ERR_NULL;
-  if (B <= 0 || N <= 0 || nnz < 0 || K <= 0 || P <= 0) return MAGAT_ERR_BAD_SHAPE;
+  if (!dims_ok(B, N, nnz, K, P)) return MAGAT_ERR_BAD_SHAPE;
   if (mode < MAGAT_MODE_KEYQUERY || mode > MAGAT_MODE_GAT_ORIGIN) return MAGAT_ERR_UNSUPPORTED;
   if (G != F || !supported_width(G)) return MAGAT_ERR_UNSUPPORTED;
   // the largest grid of the call (the hops: P heads per instance), refused here and not behind the memsets and the seed launch
-  if (K > 1 && rows_grid(B, N, P) > 0x7fffffffLL) return MAGAT_ERR_BAD_SHAPE;
+  if (K > 1 && rows_grid(B, N, P) > kGridMax) return MAGAT_ERR_BAD_SHAPE;
   hipStream_t st = static_cast<hipStream_t>(stream);
   const PackLayout L = pack_layout(G, F, K, P, mode);
   TrainParams p = {};
@@ -305,10 +305,10 @@ extern "C" int magat_gat_train_backward_cos_f32(const float* dYpre, const float*
     return MAGAT_ERR_NULL;
   if (nnz > 0 && !colidx) return MAGAT_ERR_NULL;
   if (K > 2 && !T) return MAGAT_ERR_NULL;
-  if (B <= 0 || N <= 0 || nnz < 0 || K <= 0) return MAGAT_ERR_BAD_SHAPE;
-  if (!supported_width(G) || N > 8190) return MAGAT_ERR_UNSUPPORTED;      // (N: the limit of the forward that made the CSC view)
+  if (!dims_ok(B, N, nnz, K, 1)) return MAGAT_ERR_BAD_SHAPE;
+  if (!supported_width(G) || N > magat_csr::kCsrMaxN) return MAGAT_ERR_UNSUPPORTED;      // (N: the limit of the forward that made the CSC view)
   const long long M = (long long)B * N;
-  if (M > 0x7fffffffLL || (K > 1 && rows_grid(B, N, 1) > 0x7fffffffLL)) return MAGAT_ERR_BAD_SHAPE;
+  if (M > kGridMax || (K > 1 && rows_grid(B, N, 1) > kGridMax)) return MAGAT_ERR_BAD_SHAPE;
   int rc = magat_gat_train_backward_f32(dYpre, Xhat, Z, att, T, rowptr, colidx, cscptr, cscsrc, cscpos, nnz, dZ, dXd, datt, B, N,
                                         G, G, K, 1, MAGAT_MODE_KEYQUERY, stream);
   if (rc != MAGAT_OK || K == 1) return rc;      // (K = 1: no scores - dXd and the score columns of dZ are zero, and stay so)
@@ -328,10 +328,10 @@ extern "C" int magat_gnn_backward_csr_f32(const float* dY, const int* rowptr, co
                                           long long nnz, float* dZ, int B, int N, int F, int K, void* stream) {
   if (!dY || !rowptr || !dZ) return MAGAT_ERR_NULL;
   if (nnz > 0 && K > 1 && (!colidx || !vals)) return MAGAT_ERR_NULL;
-  if (B <= 0 || N <= 0 || nnz < 0 || K <= 0) return MAGAT_ERR_BAD_SHAPE;
+  if (!dims_ok(B, N, nnz, K, 1)) return MAGAT_ERR_BAD_SHAPE;
   if (!supported_width(F)) return MAGAT_ERR_UNSUPPORTED;
   const long long grid = rows_grid(B, N, 1);
-  if (K > 1 && grid > 0x7fffffffLL) return MAGAT_ERR_BAD_SHAPE;      // (before the seed launch)
+  if (K > 1 && grid > kGridMax) return MAGAT_ERR_BAD_SHAPE;      // (before the seed launch)
   hipStream_t st = static_cast<hipStream_t>(stream);
   const long long M = (long long)B * N;
   long long blocks = (M * (F / 4) + 255) / 256;

@@ -176,13 +176,13 @@ enum MagatLdsSlot {
 static_assert(MAGAT_LDS_END <= MAGAT_LDS_SLOTS, "LDS attribute slots");
 
 // (the packed graph-layer weights and their offsets: gat_pack.h)
-int magat_gat_csr_fused_supported(int G, int F, int K, int P, int mode, int concat);
 int magat_gat_csr_fused_pack(const float* Bt, void* frag_out, int P, hipStream_t st);
-size_t magat_gat_csr_fused_order_bytes(int B, int N);
+// (whether this form serves a call, and its two grids, are decided by gat_csr_route.h and handed over)
 int magat_gat_csr_fused_forward(const uint16_t* X, const int* rowptr, const int* colidx, const int* cscptr, const int* cscsrc,
                                 const int* cscpos, long long nnz, const void* frags, const float* bias, void* Y, int ldy,
                                 int y_f32, float* att /* workspace, [nnz][P] */, float* att_opt /* [P][nnz] or null */, int* order, int B, int N,
-                                int P, hipStream_t st);
+                                int P, int grid_scores, int grid_hop, hipStream_t st);
+int gat_device_cus();      // gat_f32.hip: compute units of the current device
 int magat_cast_rows_if(const void* src, void* dst, int to_bf16, long long M, int width, int ld_src, int ld_dst, void* stream,
                        const int32_t* run_if);      // gat_csr_f32.hip: magat_cast_rows, predicated on a device flag (null = always)
 // The one-launch forms of the dense graph layer.  WHICH of them serves a call, and in what form (size class, pack, head split, CU

@@ -419,80 +419,118 @@ def _gemm_nt(a, bt, dev):
     return y[:, :Nn]
 
 
+def _gat_train_forward(ctx, X, layer, P, mode, bias, rowptr, colidx, nnz, params, cos=False):
+    """The training forward of a graph-attention layer on the HIP kernels (magat_gat_train_forward_f32, or _cos_f32 for
+    GAT_Similarity) into buffers of this call; everything the backward needs is saved on ctx.  -> (Ypre, att)"""
+    lib = nat.lib()
+    B, N, G = X.shape
+    F, K = layer.F, layer.K
+    dev, M = X.device, B * N
+    f32 = dict(dtype=torch.float32, device=dev)
+    Xc = X.detach().contiguous().float()
+    with torch.cuda.device(dev):
+        stream = nat.current_stream(dev)
+        packed = _packed_weights(layer, dev, stream, G, F, K, P, mode)
+        NC = _packed_cols(layer.attentionMode, G, F, K, P)
+        Ypre = torch.empty(M, P * F, **f32)
+        att = torch.empty(P, max(nnz, 1), **f32)
+        Z = torch.empty(M, NC, **f32)
+        T = torch.empty(K - 2, M, P * F, **f32) if K > 2 else None
+        Xhat, norms = (torch.empty(M, G, **f32), torch.empty(2, M, **f32)) if cos else (None, None)
+        cscptr = torch.empty(B * (N + 1), dtype=torch.int32, device=dev)
+        csc = torch.empty(3, max(nnz, 1), dtype=torch.int32, device=dev)
+        b1 = None if bias is None else bias.detach().reshape(-1).contiguous().float()
+        head = (nat.ptr(Xc), nat.ptr(rowptr), nat.ptr(colidx), nnz, nat.ptr(packed), nat.ptr(b1), nat.ptr(Ypre), nat.ptr(att),
+                nat.ptr(Z), nat.ptr(T))
+        tail = (nat.ptr(cscptr), nat.ptr(csc[0]), nat.ptr(csc[1]), nat.ptr(csc[2]), B, N, G)
+        if cos:
+            nat.check(lib.magat_gat_train_forward_cos_f32(*head, nat.ptr(Xhat), nat.ptr(norms), *tail, K, stream),
+                      "magat_gat_train_forward_cos_f32")
+        else:
+            nat.check(lib.magat_gat_train_forward_f32(*head, *tail, F, K, P, mode, stream), "magat_gat_train_forward_f32")
+    ctx.layer, ctx.nnz, ctx.dims, ctx.cos, ctx.has_bias = layer, nnz, (B, N, G, F, K, P, mode, NC), cos, bias is not None
+    ctx.absent = [t is None for t in params]
+    none = torch.empty(0, device=dev)
+    ctx.save_for_backward(Xc, Z, att, rowptr, colidx, cscptr, csc, packed, *(none if t is None else t for t in (T, Xhat, norms) + tuple(params)))
+    return Ypre, att
+
+
+def _dense_backward(dZ, Bt, X, dev, dXd=None, want=(True, True)):
+    """The two dense products of a backward on the library's own float32 MFMA GEMM (deterministic tile order, no split-K
+    atomics): dX = dXd + dZ Bt, dBt = dZ^T X; `want`: which of the two (None for the other)."""
+    dX = dBt = None
+    if want[0]:
+        dX = _gemm_nt(dZ, Bt.t().contiguous(), dev)
+        if dXd is not None:
+            dX = dXd + dX
+    if want[1]:
+        dBt = _gemm_nt(dZ.t().contiguous(), X.t().contiguous(), dev)
+    return dX, dBt
+
+
+def _pack_grads(params, mode_name, dBt, dZ):
+    """Gradients of (weight, weight_bias, mixer, taps) - None: the mode has no such input - from those of the packed block Bt and
+    of its column bias (the column sums of dZ), through pack_torch."""
+    grads = [None] * len(params)
+    need = [i for i, t in enumerate(params) if t is not None and t.requires_grad]
+    if need:
+        with torch.enable_grad():
+            leaves = [None if t is None else t.detach().requires_grad_(True) for t in params]
+            Bt_t, cb_t = pack_torch(*leaves, mode_name)
+            outs, gouts = [Bt_t], [dBt]
+            if cb_t.requires_grad:          # KeyQuery and GAT_Similarity have a constant (zero) column bias
+                outs.append(cb_t)
+                gouts.append(dZ.sum(dim=0))
+            got = torch.autograd.grad(outs, [leaves[i] for i in need], gouts, allow_unused=True)
+        for i, g in zip(need, got):
+            grads[i] = g
+    return grads
+
+
+def _gat_train_backward(ctx, dYpre):
+    """The backward of _gat_train_forward: the graph part on the HIP kernels (magat_gat_train_backward_f32 / _cos_f32: with the
+    cosine scores, dZ's score columns come out as gradients wrt q = W x), the dense part and the parameters' gradients as above.
+    -> (dY, dX (B,N,G), [dweight, dweight_bias, dmixer, dtaps])"""
+    lib = nat.lib()
+    Xc, Z, att, rowptr, colidx, cscptr, csc, packed, T, Xhat, norms, *params = ctx.saved_tensors
+    params = [None if gone else t for t, gone in zip(params, ctx.absent)]
+    B, N, G, F, K, P, mode, NC = ctx.dims
+    dev, M = Xc.device, B * N
+    dY = dYpre.contiguous().float()
+    with torch.cuda.device(dev):
+        stream = nat.current_stream(dev)
+        dZ = torch.empty(M, NC, dtype=torch.float32, device=dev)
+        dXd = torch.empty(M, G, dtype=torch.float32, device=dev)
+        datt = torch.empty(P, max(ctx.nnz, 1), dtype=torch.float32, device=dev)
+        Tp = nat.ptr(T if T.numel() else None)
+        tail = (nat.ptr(rowptr), nat.ptr(colidx), nat.ptr(cscptr), nat.ptr(csc[0]), nat.ptr(csc[1]), ctx.nnz, nat.ptr(dZ),
+                nat.ptr(dXd), nat.ptr(datt), B, N, G)
+        if ctx.cos:
+            nat.check(lib.magat_gat_train_backward_cos_f32(nat.ptr(dY), nat.ptr(Xhat), nat.ptr(Z), nat.ptr(att), Tp, nat.ptr(norms),
+                                                           *tail, K, stream), "magat_gat_train_backward_cos_f32")
+        else:
+            nat.check(lib.magat_gat_train_backward_f32(nat.ptr(dY), nat.ptr(Xc), nat.ptr(Z), nat.ptr(att), Tp, *tail, F, K, P, mode,
+                                                       stream), "magat_gat_train_backward_f32")
+    dX, dBt = _dense_backward(dZ, packed[:NC * G].view(NC, G), Xc.view(M, G), dev, dXd)
+    return dY, dX.view(B, N, G), _pack_grads(params, ctx.layer.attentionMode, dBt, dZ)
+
+
 class _GatTrainFunction(torch.autograd.Function):
     """HIP forward + backward of the graph-attention layer for training (pre-activation, per-head output)."""
 
     @staticmethod
     def forward(ctx, X, weight, weight_bias, mixer, taps, bias, rowptr, colidx, nnz, layer):
-        lib = nat.lib()
-        B, N, G = X.shape
-        F, K, P = layer.F, layer.K, layer.P
-        mode = _MODES[layer.attentionMode]
-        dev = X.device
-        M = B * N
-        Xc = X.detach().contiguous().float()
-        with torch.cuda.device(dev):
-            stream = nat.current_stream(dev)
-            packed = _packed_weights(layer, dev, stream, G, F, K, P, mode)
-            NC = _packed_cols(layer.attentionMode, G, F, K, P)
-            Ypre = torch.empty(M, P * F, dtype=torch.float32, device=dev)
-            att = torch.empty(P, max(nnz, 1), dtype=torch.float32, device=dev)
-            Z = torch.empty(M, NC, dtype=torch.float32, device=dev)
-            T = torch.empty(max(K - 2, 0), M, P * F, dtype=torch.float32, device=dev) if K > 2 else None
-            cscptr = torch.empty(B * (N + 1), dtype=torch.int32, device=dev)
-            csc = torch.empty(3, max(nnz, 1), dtype=torch.int32, device=dev)
-            b1 = None if bias is None else bias.detach().reshape(-1).contiguous().float()
-            nat.check(lib.magat_gat_train_forward_f32(
-                nat.ptr(Xc), nat.ptr(rowptr), nat.ptr(colidx), nnz, nat.ptr(packed), nat.ptr(b1), nat.ptr(Ypre),
-                nat.ptr(att), nat.ptr(Z), nat.ptr(T), nat.ptr(cscptr), nat.ptr(csc[0]), nat.ptr(csc[1]),
-                nat.ptr(csc[2]), B, N, G, F, K, P, mode, stream), "magat_gat_train_forward_f32")
-        ctx.layer, ctx.nnz, ctx.dims = layer, nnz, (B, N, G, F, K, P, mode, NC)
-        ctx.has_bias = bias is not None
-        ctx.no_wb = weight_bias is None
-        ctx.save_for_backward(Xc, Z, att, T if T is not None else torch.empty(0, device=dev), rowptr, colidx, cscptr,
-                              csc, packed, weight, weight_bias if weight_bias is not None else torch.empty(0, device=dev),
-                              mixer, taps)
+        Ypre, att = _gat_train_forward(ctx, X, layer, layer.P, _MODES[layer.attentionMode], bias, rowptr, colidx, nnz,
+                                       (weight, weight_bias, mixer, taps))
         ctx.mark_non_differentiable(att)
         return Ypre, att           # att (P, nnz): the attention of every stored edge, row-major CSR order
 
     @staticmethod
     def backward(ctx, dYpre, _datt=None):
-        lib = nat.lib()
-        Xc, Z, att, T, rowptr, colidx, cscptr, csc, packed, weight, weight_bias, mixer, taps = ctx.saved_tensors
+        dY, dX, grads = _gat_train_backward(ctx, dYpre)
         B, N, G, F, K, P, mode, NC = ctx.dims
-        dev, M = Xc.device, B * N
-        dY = dYpre.contiguous().float()
-        with torch.cuda.device(dev):
-            stream = nat.current_stream(dev)
-            dZ = torch.empty(M, NC, dtype=torch.float32, device=dev)
-            dXd = torch.empty(M, G, dtype=torch.float32, device=dev)
-            datt = torch.empty(P, max(ctx.nnz, 1), dtype=torch.float32, device=dev)
-            nat.check(lib.magat_gat_train_backward_f32(
-                nat.ptr(dY), nat.ptr(Xc), nat.ptr(Z), nat.ptr(att), nat.ptr(T if T.numel() else None), nat.ptr(rowptr),
-                nat.ptr(colidx), nat.ptr(cscptr), nat.ptr(csc[0]), nat.ptr(csc[1]), ctx.nnz, nat.ptr(dZ), nat.ptr(dXd),
-                nat.ptr(datt), B, N, G, F, K, P, mode, stream), "magat_gat_train_backward_f32")
-        Bt = packed[:NC * G].view(NC, G)
-        X2 = Xc.view(M, G)
-        # the two dense products of the backward on the library's own float32 MFMA GEMM (deterministic tile order, no split-K
-        # atomics): dX = dXd + dZ Bt, dBt = dZ^T X
-        dX = (dXd + _gemm_nt(dZ, Bt.t().contiguous(), dev)).view(B, N, G)
-        dBt, dcb = _gemm_nt(dZ.t().contiguous(), X2.t().contiguous(), dev), dZ.sum(dim=0)
-        grads = [None, None, None, None]
-        params = [weight, None if ctx.no_wb else weight_bias, mixer, taps]
-        need = [i for i, t in enumerate(params) if t is not None and t.requires_grad]
-        if need:
-            with torch.enable_grad():
-                leaves = [None if t is None else t.detach().requires_grad_(True) for t in params]
-                Bt_t, cb_t = pack_torch(*leaves, ctx.layer.attentionMode)
-                outs, gouts = [Bt_t], [dBt]
-                if cb_t.requires_grad:          # KeyQuery has a constant (zero) column bias
-                    outs.append(cb_t)
-                    gouts.append(dcb)
-                got = torch.autograd.grad(outs, [leaves[i] for i in need], gouts, allow_unused=True)
-            for i, g in zip(need, got):
-                grads[i] = g
-        dbias = dY.view(M, P, F).sum(dim=(0, 1)).view(F, 1) if ctx.has_bias else None
-        return dX, grads[0], grads[1], grads[2], grads[3], dbias, None, None, None, None
+        dbias = dY.view(B * N, P, F).sum(dim=(0, 1)).view(F, 1) if ctx.has_bias else None
+        return (dX, *grads, dbias, None, None, None, None)
 
 
 _COS_TRAIN_WIDTHS = (16, 32, 64, 128, 256)
@@ -507,69 +545,34 @@ class _GatCosTrainFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, X, weight, taps, bias, rowptr, colidx, nnz, layer):
-        lib = nat.lib()
         B, N, G = X.shape
-        K = layer.K
         if G not in _COS_TRAIN_WIDTHS or N > _COS_TRAIN_MAX_N:
             raise nat.MagatNativeError("GAT_Similarity with hip_backward=True: %d features on graphs of %d agents are outside the "
                                        "training kernels (feature widths %s, N <= %d)" % (G, N, _COS_TRAIN_WIDTHS, _COS_TRAIN_MAX_N))
-        dev, M = X.device, B * N
-        Xc = X.detach().contiguous().float()
-        with torch.cuda.device(dev):
-            stream = nat.current_stream(dev)
-            packed = _packed_weights(layer, dev, stream, G, G, K, 1, nat.MODE_SIMILARITY)
-            NC = _packed_cols(layer.attentionMode, G, G, K, 1)
-            Ypre = torch.empty(M, G, dtype=torch.float32, device=dev)
-            att = torch.empty(1, max(nnz, 1), dtype=torch.float32, device=dev)
-            Z = torch.empty(M, NC, dtype=torch.float32, device=dev)
-            T = torch.empty(max(K - 2, 0), M, G, dtype=torch.float32, device=dev) if K > 2 else None
-            Xhat = torch.empty(M, G, dtype=torch.float32, device=dev)
-            norms = torch.empty(2, M, dtype=torch.float32, device=dev)
-            cscptr = torch.empty(B * (N + 1), dtype=torch.int32, device=dev)
-            csc = torch.empty(3, max(nnz, 1), dtype=torch.int32, device=dev)
-            b1 = None if bias is None else bias.detach().reshape(-1).contiguous().float()
-            nat.check(lib.magat_gat_train_forward_cos_f32(
-                nat.ptr(Xc), nat.ptr(rowptr), nat.ptr(colidx), nnz, nat.ptr(packed), nat.ptr(b1), nat.ptr(Ypre), nat.ptr(att),
-                nat.ptr(Z), nat.ptr(T), nat.ptr(Xhat), nat.ptr(norms), nat.ptr(cscptr), nat.ptr(csc[0]), nat.ptr(csc[1]),
-                nat.ptr(csc[2]), B, N, G, K, stream), "magat_gat_train_forward_cos_f32")
-        ctx.layer, ctx.nnz, ctx.dims = layer, nnz, (B, N, G, K, NC)
-        ctx.has_bias = bias is not None
-        ctx.save_for_backward(Xc, Xhat, norms, Z, att, T if T is not None else torch.empty(0, device=dev), rowptr, colidx,
-                              cscptr, csc, packed, weight, taps)
-        return Ypre
+        return _gat_train_forward(ctx, X, layer, 1, nat.MODE_SIMILARITY, bias, rowptr, colidx, nnz, (weight, None, None, taps),
+                                  cos=True)[0]
 
     @staticmethod
     def backward(ctx, dYpre):
-        lib = nat.lib()
-        Xc, Xhat, norms, Z, att, T, rowptr, colidx, cscptr, csc, packed, weight, taps = ctx.saved_tensors
-        B, N, G, K, NC = ctx.dims
-        dev, M = Xc.device, B * N
-        dY = dYpre.contiguous().float()
-        with torch.cuda.device(dev):
-            stream = nat.current_stream(dev)
-            dZ = torch.empty(M, NC, dtype=torch.float32, device=dev)
-            dXd = torch.empty(M, G, dtype=torch.float32, device=dev)
-            datt = torch.empty(1, max(ctx.nnz, 1), dtype=torch.float32, device=dev)
-            nat.check(lib.magat_gat_train_backward_cos_f32(
-                nat.ptr(dY), nat.ptr(Xhat), nat.ptr(Z), nat.ptr(att), nat.ptr(T if T.numel() else None), nat.ptr(norms),
-                nat.ptr(rowptr), nat.ptr(colidx), nat.ptr(cscptr), nat.ptr(csc[0]), nat.ptr(csc[1]), ctx.nnz, nat.ptr(dZ),
-                nat.ptr(dXd), nat.ptr(datt), B, N, G, K, stream), "magat_gat_train_backward_cos_f32")
-        Bt = packed[:NC * G].view(NC, G)
-        # the caller's two GEMMs, as for KeyQuery (dZ's score columns are gradients wrt q = W x now): dX = dXd + dZ Bt, dBt = dZ^T X
-        dX = (dXd + _gemm_nt(dZ, Bt.t().contiguous(), dev)).view(B, N, G)
-        dBt = _gemm_nt(dZ.t().contiguous(), Xc.view(M, G).t().contiguous(), dev)
-        grads = [None, None]
-        params = [weight, taps]
-        need = [i for i, t in enumerate(params) if t.requires_grad]
-        if need:
-            with torch.enable_grad():
-                leaves = [t.detach().requires_grad_(True) for t in params]
-                Bt_t, _ = pack_torch(leaves[0], None, None, leaves[1], ctx.layer.attentionMode)      # (the column bias is constant zero)
-                got = torch.autograd.grad([Bt_t], [leaves[i] for i in need], [dBt], allow_unused=True)
-            for i, g in zip(need, got):
-                grads[i] = g
-        dbias = dY.sum(dim=0).view(G, 1) if ctx.has_bias else None
-        return dX, grads[0], grads[1], dbias, None, None, None, None
+        dY, dX, grads = _gat_train_backward(ctx, dYpre)
+        dbias = dY.sum(dim=0).view(ctx.dims[2], 1) if ctx.has_bias else None
+        return dX, grads[0], grads[3], dbias, None, None, None, None
+
+
+def _intake(layer, x, rows=False, S3=None, rule=None):
+    """x (B,G,Nin) padded with zero agents to the N of the layer's GSO, and whether autograd wants this forward; with `rows` also
+    the rows (B,N,G) and the CSR arrays of the layer's GSO (S3, rule: of another GSO under another edge rule) for the training
+    kernels.  -> (x, needs_grad[, rows, rowptr, colidx, nnz])"""
+    B, Gin, Nin = x.shape
+    assert layer.S is not None, "addGSO must be called before forward"
+    if Nin < layer.N:
+        x = torch.cat((x, torch.zeros(B, Gin, layer.N - Nin, dtype=x.dtype, device=x.device)), dim=2)
+    needs_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in layer.parameters()))
+    if not rows:
+        return x, needs_grad
+    if S3 is None:
+        S3, rule = _gso3(layer.S, B, layer.N, x.device), layer.edge_rule
+    return (x, needs_grad, x.permute(0, 2, 1).contiguous()) + tuple(dense_gso_to_csr(S3, self_loops=rule))
 
 
 def _composite(layer, x, S):
@@ -728,20 +731,15 @@ class GraphFilterBatchAttentional(_DropsDeviceState, nn.Module):
         return np.mean(aij, axis=1)
 
     def forward(self, x):
-        B, Gin, Nin = x.shape
-        assert self.S is not None, "addGSO must be called before forward"
-        if Nin < self.N:
-            x = torch.cat((x, torch.zeros(B, Gin, self.N - Nin, dtype=x.dtype, device=x.device)), dim=2)
-        needs_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+        B, _, Nin = x.shape
+        x, needs_grad = _intake(self, x)
         if self.E != 1 or not _is_relu(self.nonlinearity):
             y = self._forward_general(x)
         elif needs_grad and x.is_cuda and not self.return_attention and self._hip_backward:
             # training on the GPU: HIP forward + backward of the graph layer (CSR kernels), ReLU / head merge in torch
             N = self.N
-            rowptr, colidx, nnz = dense_gso_to_csr(_gso3(self.S, B, N, x.device), self_loops=self.edge_rule)
-            w_, wb_, mx_, tp_ = self._pack_tensors()
-            Ypre, _ = _GatTrainFunction.apply(x.permute(0, 2, 1).contiguous(), w_, wb_, mx_, tp_, self.bias, rowptr,
-                                              colidx, nnz, self)
+            rows, rowptr, colidx, nnz = _intake(self, x, rows=True)[2:]
+            Ypre, _ = _GatTrainFunction.apply(rows, *self._pack_tensors(), self.bias, rowptr, colidx, nnz, self)
             Yh = Ypre.view(B, N, self.P, self.F)
             if self.concatenate:
                 y = torch.relu(Yh).reshape(B, N, self.P * self.F).permute(0, 2, 1)
@@ -781,8 +779,7 @@ class GraphFilterBatchAttentional(_DropsDeviceState, nn.Module):
             if rule:
                 Su = Su.float() + torch.eye(N, dtype=torch.float32, device=Su.device)
             Su, rule = Su.abs().sum(dim=1), 0
-        rowptr, colidx, nnz = dense_gso_to_csr(Su, self_loops=rule)
-        rows = x.permute(0, 2, 1).contiguous()
+        rows, rowptr, colidx, nnz = _intake(self, x, rows=True, S3=Su, rule=rule)[2:]
         if self._edge_views is None or len(self._edge_views) != E:
             self._edge_views = [_EdgeView(self, e) for e in range(E)]
         Ypre, atts = None, []
@@ -898,14 +895,10 @@ class GraphFilterBatchSimilarityAttentional(GraphFilterBatchAttentional):
 
     def _forward_hip_train(self, x):
         """Training on the GPU with hip_backward: HIP forward + backward of the layer (CSR kernels), ReLU in torch."""
-        B, Gin, Nin = x.shape
-        assert self.S is not None, "addGSO must be called before forward"
+        B, _, Nin = x.shape
+        rows, rowptr, colidx, nnz = _intake(self, x, rows=True)[2:]
         N = self.N
-        if Nin < N:
-            x = torch.cat((x, torch.zeros(B, Gin, N - Nin, dtype=x.dtype, device=x.device)), dim=2)
-        rowptr, colidx, nnz = dense_gso_to_csr(_gso3(self.S, B, N, x.device), self_loops=self.edge_rule)
-        Ypre = _GatCosTrainFunction.apply(x.permute(0, 2, 1).contiguous(), self.weight, self.filterWeight, self.bias, rowptr,
-                                          colidx, nnz, self)
+        Ypre = _GatCosTrainFunction.apply(rows, self.weight, self.filterWeight, self.bias, rowptr, colidx, nnz, self)
         y = torch.relu(Ypre.view(B, N, self.F)).permute(0, 2, 1)      # (one head: concatenation and mean are the same rows)
         self.aij = None
         return y[:, :, :Nin] if Nin < N else y
@@ -938,15 +931,13 @@ class _GnnTrainFunction(torch.autograd.Function):
             nat.check(nat.lib().magat_gnn_backward_csr_f32(nat.ptr(dY), nat.ptr(rowptr), nat.ptr(colidx), nat.ptr(vals),
                                                            ctx.nnz, nat.ptr(dZ), B, N, F, K, nat.current_stream(dev)),
                       "magat_gnn_backward_csr_f32")
-        dx = dw = db = None
-        if ctx.needs_input_grad[0]:
-            Bt = weight.detach()[:, 0].permute(1, 0, 2).reshape(K * F, G).float()        # row k*F+f = weight[f,0,k,:]
-            dx = _gemm_nt(dZ, Bt.t().contiguous(), dev).reshape(B, N, G).permute(0, 2, 1)
-        if ctx.needs_input_grad[1]:
-            dw = _gemm_nt(dZ.t().contiguous(), X.t().contiguous(), dev).reshape(K, F, G).permute(1, 0, 2) \
-                .reshape(F, 1, K, G).to(weight.dtype)
-        if ctx.has_bias and ctx.needs_input_grad[2]:
-            db = dY.sum(dim=0).view(F, 1)
+        Bt = weight.detach()[:, 0].permute(1, 0, 2).reshape(K * F, G).float() if ctx.needs_input_grad[0] else None   # row k*F+f = weight[f,0,k,:]
+        dx, dw = _dense_backward(dZ, Bt, X, dev, want=ctx.needs_input_grad[:2])
+        if dx is not None:
+            dx = dx.reshape(B, N, G).permute(0, 2, 1)
+        if dw is not None:
+            dw = dw.reshape(K, F, G).permute(1, 0, 2).reshape(F, 1, K, G).to(weight.dtype)
+        db = dY.sum(dim=0).view(F, 1) if ctx.has_bias and ctx.needs_input_grad[2] else None
         return dx, dw, db, None
 
 
@@ -986,12 +977,9 @@ class GraphFilterBatch(_DropsDeviceState, nn.Module):
         self.S = S
 
     def forward(self, x):
-        B, Gin, Nin = x.shape
-        assert self.S is not None, "addGSO must be called before forward"
+        Nin = x.shape[2]
+        x, needs_grad = _intake(self, x)
         N = self.N
-        if Nin < N:
-            x = torch.cat((x, torch.zeros(B, Gin, N - Nin, dtype=x.dtype, device=x.device)), dim=2)
-        needs_grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
         if needs_grad and not x.is_cuda:
             nat.require_device_or_composite(x, "GraphFilterBatch under autograd")     # CPU tensors: the torch composite
             Sf = self.S.to(x.device)[:, 0].to(x.dtype)      # (the checker runs this composite in float64 too)

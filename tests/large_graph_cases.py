@@ -134,7 +134,7 @@ def edge_mask(S, mode):
 
 
 def tiled_route(opt, mode, N, G, F, K, bf16, att):
-    """csr_tiled_ok of csrc/gat_csr_f32.hip, restated: (scores tiled, hops tiled) under option CSR_TILED = opt.  The tiled score
+    """tiled_ok and its callers in csrc/gat_csr_route.h, restated: (scores tiled, hops tiled) under option CSR_TILED = opt.  The tiled score
     kernel serves KeyQuery only (GAT_Similarity and the rank-1 modes keep the per-edge one, GraphFilterBatch has no scores); a
     kernel is tiled when its bit of the option is set, 8 <= N <= 1024 and a row of its width is a multiple of 128 bytes."""
     esz = 2 if bf16 else 4
@@ -329,9 +329,13 @@ def y_error(got, want):
 
 @functools.lru_cache(maxsize=None)
 def reference(cid):
+    """reference_of the case of this file called `cid`; computed once per process."""
+    return reference_of(CASES[cid])
+
+
+def reference_of(k):
     """Inputs (float32 values), the edge list of the layer's rule and the float64 yardstick of a case, the float32 composite's own
-    error against it and the gates that follow; computed once per process."""
-    k = CASES[cid]
+    error against it and the gates that follow.  (tests/gat_csr_route_cases.py brings cases of its own.)"""
     g = tg._gen(k.seed)
     with torch.random.fork_rng(devices=[]):      # (the layers draw their initial parameters from the global generator)
         torch.manual_seed(k.seed)

@@ -50,7 +50,7 @@ def test_forced_list_covers_widths_modes_heads_and_depths_pairwise():
 
 
 def test_routes_of_the_lists():
-    """csr_tiled_ok restated: with CSR_TILED = 0 no forced case reaches a tiled kernel; with CSR_TILED = 3 every case of the tiled
+    """tiled_ok (csrc/gat_csr_route.h) restated: with CSR_TILED = 0 no forced case reaches a tiled kernel; with CSR_TILED = 3 every case of the tiled
     list runs at least one and the list holds both kinds, the ends of the size range and a row format of each storage type."""
     for k in lg.FORCED.values():
         assert lg.tiled_route(0, k.mode, k.N, k.G, k.F, k.K, k.bf16, k.att) == (False, False), k.id
