@@ -226,11 +226,12 @@ int magat_gat_cos_prepare(const float* X, float* Z, float* Xhat, long long M, in
                           void* stream, const int32_t* run_if = nullptr,      // run_if: the launch is a no-op unless *run_if != 0
                           float* norms = nullptr);      // [2][M] or null: the unclamped |X[m]| and |Q[m]| (the training forward keeps them)
 
-// fp32 -> three bf16 planes (round-to-nearest-even each)
+// fp32 -> three bf16 planes (round-to-nearest-even each).  A NaN stays a NaN of its sign (quiet bit set): the rounding add would
+// carry a large payload over into the exponent and the sign - 0x7fffffff -> -0, 0xffffffff -> +0, 0x7f800001 -> +inf
 __device__ __forceinline__ unsigned short magat_bf16_rne(float v) {
-  unsigned u = __builtin_bit_cast(unsigned, v);
-  u += 0x7fffu + ((u >> 16) & 1u);
-  return (unsigned short)(u >> 16);
+  const unsigned u = __builtin_bit_cast(unsigned, v);
+  const unsigned r = u + 0x7fffu + ((u >> 16) & 1u);
+  return (unsigned short)(((u & 0x7fffffffu) > 0x7f800000u ? (u | 0x00400000u) : r) >> 16);
 }
 __device__ __forceinline__ float magat_bf16_f32(unsigned short h) { return __builtin_bit_cast(float, (unsigned)h << 16); }
 

@@ -533,6 +533,7 @@ def test_encoder_other_map_sizes(gpu_device, monkeypatch, hw, cnn, libopt):
     assert meta["n_feat"] == ref.shape[1]
     xd = x.to(gpu_device)
     ws = torch.empty(lib.magat_encoder_workspace_bytes(ctypes.byref(d), M), dtype=torch.uint8, device=gpu_device)
+    ws[:256].zero_()             # the range-guard status block: the caller zeroes it (include/magat_hip.h)
     scale = float(ref.abs().max())
     outs = []
     envs = [{}, {"MAGAT_L1_FUSED": "0"}, {"MAGAT_CONV_PCHAIN": "0"}]
@@ -545,6 +546,9 @@ def test_encoder_other_map_sizes(gpu_device, monkeypatch, hw, cnn, libopt):
         torch.cuda.synchronize()
         for k in env:
             libopt.reset(k)
+        st = (ctypes.c_int32 * 2)()
+        nat.check(lib.magat_encoder_read_status(nat.ptr(ws), st, nat.current_stream(gpu_device)), "magat_encoder_read_status")
+        assert list(st) == [0, 0], (env, list(st))      # the split kernels produced these numbers, not the guard's float32 re-run
         got = feat.double().cpu()
         assert float((got - ref).abs().max()) <= 2e-5 * max(scale, 1.0), (env, float((got - ref).abs().max()), scale)
         outs.append(got)
