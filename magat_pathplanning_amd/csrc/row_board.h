@@ -19,6 +19,23 @@ __device__ __forceinline__ u64 cells_up(u64 v) { return wave_shift<0x130>(v); } 
 __device__ __forceinline__ u64 cells_down(u64 v) { return wave_shift<0x138>(v); }      // wave_shr:1 - row r takes row r - 1
 __device__ __forceinline__ bool wave_any(bool p) { return __builtin_amdgcn_ballot_w64(p) != 0ull; }
 __device__ __forceinline__ bool has_bit(u64 w, int c) { return (w >> c) & 1ull; }
+// the butterfly over the 64 lanes: op(a, b) of an int from every lane, the same value in every lane afterwards
+template <typename Op>
+__device__ __forceinline__ int wave_all(int v, Op op) {
+  for (int off = 32; off >= 1; off >>= 1) v = op(v, __shfl_xor(v, off, 64));
+  return v;
+}
+__device__ __forceinline__ int wave_all_min(int v) { return wave_all(v, [](int a, int b) { return b < a ? b : a; }); }
+__device__ __forceinline__ int wave_all_max(int v) { return wave_all(v, [](int a, int b) { return b > a ? b : a; }); }
+__device__ __forceinline__ int wave_all_sum(int v) { return wave_all(v, [](int a, int b) { return a + b; }); }
+__device__ __forceinline__ int wave_all_or(int v) { return wave_all(v, [](int a, int b) { return a | b; }); }
+// the lexicographically smallest (a, b, c) of the lanes
+__device__ __forceinline__ void wave_all_min3(int& a, int& b, int& c) {
+  for (int off = 32; off >= 1; off >>= 1) {
+    const int oa = __shfl_xor(a, off, 64), ob = __shfl_xor(b, off, 64), oc = __shfl_xor(c, off, 64);
+    if (oa < a || (oa == a && (ob < b || (ob == b && oc < c)))) a = oa, b = ob, c = oc;
+  }
+}
 
 // ---- wide boards -------------------------------------------------------------------------------------------------------------
 // One workgroup of 64 * ceil(H / 64) threads, thread = map row, NW = 1, 2 or 4 words per row in registers (word k holds columns

@@ -19,25 +19,6 @@
 
 namespace {
 
-__device__ __forceinline__ int audit_wave_min(int v) {
-  for (int off = 32; off >= 1; off >>= 1) {
-    const int o = __shfl_xor(v, off, 64);
-    v = o < v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ int audit_wave_max(int v) {
-  for (int off = 32; off >= 1; off >>= 1) {
-    const int o = __shfl_xor(v, off, 64);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ int audit_wave_sum(int v) {
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // steps from (sr, sc) to another free cell (gr, gc), or -1 (wave-uniform)
 __device__ int audit_flood(u64 free, int sr, int sc, int gr, int gc, int lane) {
   u64 reach = lane == sr ? 1ull << sc : 0ull;
@@ -96,7 +77,7 @@ __global__ __launch_bounds__(64) void mapf_audit_kernel(const uint8_t* __restric
     if (lane == 0) audit_write(cs, status, fault, flowtime, makespan, 1, 0, -1, -1, -1, 0, 0);
     return;
   }
-  const int key1 = audit_wave_min(audit_stage1(rows, len, st, gl, N, T, H, W, lane, 64, is_free));
+  const int key1 = wave_all_min(audit_stage1(rows, len, st, gl, N, T, H, W, lane, 64, is_free));
   if (key1 != AUDIT_NONE) {
     if (lane == 0) {
       audit_write(cs, status, fault, flowtime, makespan, 2, 0, -1, -1, -1, 0, 0);
@@ -107,7 +88,7 @@ __global__ __launch_bounds__(64) void mapf_audit_kernel(const uint8_t* __restric
   int* at = workspace + a0 * 2;
   int t2 = -1;
   const int key2 = audit_stage2(rows, N, T, W, own[0], own[1], at, at + N, lane, 64, [](int key) {
-    key = audit_wave_min(key);
+    key = wave_all_min(key);
     __syncthreads();
     return key;
   }, &t2);
@@ -117,8 +98,8 @@ __global__ __launch_bounds__(64) void mapf_audit_kernel(const uint8_t* __restric
     flow += lb - 1;
     last = lb - 1 > last ? lb - 1 : last;
   }
-  flow = audit_wave_sum(flow);
-  last = audit_wave_max(last);
+  flow = wave_all_sum(flow);
+  last = wave_all_max(last);
   if (lane == 0) {
     if (key2 == AUDIT_NONE) audit_write(cs, status, fault, flowtime, makespan, 0, 0, -1, -1, -1, flow, last);
     else audit_write(cs, status, fault, flowtime, makespan, 2, 7 + (key2 & 1), t2, key2 >> 13, key2 >> 1 & 4095, 0, 0);

@@ -23,25 +23,6 @@ namespace {
 
 __host__ __device__ inline long long waudit_case_ints(int H, int W, int N) { return 2LL * H * W + 2LL * N; }
 
-__device__ __forceinline__ int waudit_wave_min(int v) {
-  for (int off = 32; off >= 1; off >>= 1) {
-    const int o = __shfl_xor(v, off, 64);
-    v = o < v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ int waudit_wave_max(int v) {
-  for (int off = 32; off >= 1; off >>= 1) {
-    const int o = __shfl_xor(v, off, 64);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ int waudit_wave_sum(int v) {
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-
 // steps from (sr, sc) to a free cell (gr, gc), or -1 (the same for every thread); one round of the mail per step
 template <int NW>
 __device__ int waudit_flood(wide_seat& s, const wboard<NW>& free, int sr, int sc, int gr, int gc, int tid) {
@@ -119,7 +100,7 @@ __global__ __launch_bounds__(WIDE_SIDE) void wmapf_audit_kernel(const uint8_t* _
     return;
   }
   const auto group_min = [&](int key) {
-    wide_post(s, 0, waudit_wave_min(key));
+    wide_post(s, 0, wave_all_min(key));
     return wide_min(s, wide_sync(s), 0);
   };
   const int key1 = group_min(audit_stage1(rows, len, st, gl, N, T, H, W, tid, nt, is_free));
@@ -138,8 +119,8 @@ __global__ __launch_bounds__(WIDE_SIDE) void wmapf_audit_kernel(const uint8_t* _
     flow += lb - 1;
     last = lb - 1 > last ? lb - 1 : last;
   }
-  wide_post(s, 0, waudit_wave_sum(flow));
-  wide_post(s, 1, waudit_wave_max(last));
+  wide_post(s, 0, wave_all_sum(flow));
+  wide_post(s, 1, wave_all_max(last));
   const int p = wide_sync(s);
   if (tid == 0) {
     if (key2 == AUDIT_NONE)

@@ -1,27 +1,13 @@
-// What conflict-based search (sim_mapf_cbs.hip) and its bounded-suboptimal form (sim_mapf_ecbs.hip) share: the reductions over the
-// wavefront, the constraint bits of an agent's chain on the hard boards, and a node's path laid into a row of the schedule.
-// One wavefront per case, lane = map row.  Every store is a per-lane (vector) store from plain C++.
+// What the tree walk (sim_mapf_tree.h) takes from below: the constraint bits of an agent's chain and a node's path laid into a row
+// of the schedule, for any form - and cbs_wave, what the two one-wavefront forms (sim_mapf_cbs.hip, sim_mapf_ecbs.hip: lane = map row,
+// one 64-bit word per row) bring alike: the butterfly reductions, the free board, the screening and a bit of the hard boards.
+// Every store is a per-lane (vector) store from plain C++.
 #pragma once
 #include <cstdint>
 
 #include "magat_common.h"
-#include "row_board.h"
+#include "row_board.h"           // wave_any, wave_all_min / _max / _sum / _min3
 #include "sim_mapf_parts.h"      // MAPF_BOARDS, MAPF_SIDE
-
-__device__ __forceinline__ int cbs_wave_min(int v) {
-  for (int off = 32; off >= 1; off >>= 1) {
-    const int o = __shfl_xor(v, off, 64);
-    v = o < v ? o : v;
-  }
-  return v;
-}
-__device__ __forceinline__ int cbs_wave_max(int v) {
-  for (int off = 32; off >= 1; off >>= 1) {
-    const int o = __shfl_xor(v, off, 64);
-    v = o > v ? o : v;
-  }
-  return v;
-}
 
 // one constraint bit, by the lane of its row
 template <bool SET>
@@ -42,9 +28,9 @@ __device__ __forceinline__ void cbs_for_chain(const Node* nodes, int i, int x, M
     i = __builtin_amdgcn_readfirstlane(nodes[i].parent);
   }
 }
-template <bool SET, typename Node>
-__device__ void cbs_mark_chain(u64* boards, const Node* nodes, int i, int x, int lane) {
-  cbs_for_chain(nodes, i, x, [&](int board, int t, int r, int c) { cbs_mark<SET>(boards, board, t, r, c, lane); });
+template <bool SET, typename Form, typename Node>
+__device__ __forceinline__ void cbs_mark_chain(Form& f, const Node* nodes, int i, int x) {
+  cbs_for_chain(nodes, i, x, [&](int board, int t, int r, int c) { f.template mark<SET>(board, t, r, c); });
 }
 
 // a path of `len` 16-bit cells, padded with its last one, into a row of the schedule; the nt threads of the workgroup over t
@@ -55,3 +41,51 @@ __device__ __forceinline__ void cbs_place(int* p, const uint16_t* src, int len, 
     p[2 * t + 1] = cell & 255;
   }
 }
+
+struct cbs_wave {
+  static constexpr int nt = 64;
+  int tid;
+  u64* hard;      // [t][V, A_up, A_left, A_down, A_right][row]: the constraints of the agent that is searched
+  u64 free;
+  __device__ __forceinline__ int group_min(int v) {
+    v = wave_all_min(v);
+    __syncthreads();
+    return v;
+  }
+  __device__ __forceinline__ int group_max(int v) {
+    v = wave_all_max(v);
+    __syncthreads();
+    return v;
+  }
+  __device__ __forceinline__ int group_sum(int v) {
+    v = wave_all_sum(v);
+    __syncthreads();
+    return v;
+  }
+  __device__ __forceinline__ void group_min3(int& a, int& b, int& c) { wave_all_min3(a, b, c); }
+  __device__ __forceinline__ void load_free(const uint8_t* mp, int H, int W) {
+    free = 0ull;
+    for (int r = 0; r < H; ++r) {
+      const u64 word = __builtin_amdgcn_ballot_w64(tid < W && mp[r * W + (tid < W ? tid : 0)] == 0);
+      if (tid == r) free = word;
+    }
+  }
+  __device__ __forceinline__ bool screen(const int* st, const int* gl, int N, int H, int W) const {
+    u64 starts = 0ull, goals = 0ull;
+    bool ok = true;
+    for (int a = 0; a < N && ok; ++a) {
+      const int sr = __builtin_amdgcn_readfirstlane(st[2 * a]), sc = __builtin_amdgcn_readfirstlane(st[2 * a + 1]);
+      const int gr = __builtin_amdgcn_readfirstlane(gl[2 * a]), gc = __builtin_amdgcn_readfirstlane(gl[2 * a + 1]);
+      const bool inside = sr >= 0 && sr < H && sc >= 0 && sc < W && gr >= 0 && gr < H && gc >= 0 && gc < W;
+      const u64 sbit = inside ? 1ull << sc : 0ull, gbit = inside ? 1ull << gc : 0ull;
+      ok = wave_any(tid == sr && (free & ~starts & sbit)) && wave_any(tid == gr && (free & ~goals & gbit));
+      if (tid == sr) starts |= sbit;
+      if (tid == gr) goals |= gbit;
+    }
+    return ok;
+  }
+  template <bool SET>
+  __device__ __forceinline__ void mark(int board, int t, int r, int c) const {
+    cbs_mark<SET>(hard, board, t, r, c, tid);
+  }
+};

@@ -3,26 +3,27 @@
 // in tests/ecbs_restatement.py).  A solved case promises 1000 * flowtime <= w_milli * lower_bound <= w_milli * optimum.
 //   magat_sim_mapf_ecbs_workspace_bytes   per case: hard and soft boards, the planes, the root's paths, the node pool, five int rows
 //   magat_sim_mapf_ecbs                   one wavefront per case runs the whole tree; one launch, no host round trip
-// The layout of mapf_cbs_kernel (sim_mapf_cbs.hip): lane = map row, one 64-bit word per row.  Per case:
+// The tree is sim_mapf_tree.h's walk, under the focal rule (FOCAL = true).  This file brings its form.  The layout of
+// mapf_cbs_kernel (sim_mapf_cbs.hip): lane = map row, one 64-bit word per row.  Per case:
 //   hard boards    workspace [t][V, A_up, A_left, A_down, A_right][row]: the constraints of the agent that is searched, as in CBS.
 //   soft boards    a second set: the planner's reservation of every OTHER agent of the schedule the search runs against, set
-//                  before a search and cleared after it by lanes over t (a lane owns the words of its t).
+//                  before a search and cleared after it by lanes over t (a lane owns the words of its t).  None at K = 1.
 //   planes         workspace [k][t][row], K = levels of them: plane K - 1 is the planner's R on the hard boards, plane k below it
 //                  the cells reached with at most k steps that break a soft board.  A lane reads back only the rows it wrote.
-//   node pool      workspace: 32 bytes per node (parent, cost, lb, hc, agent | board | open | length, t | cell, t*) and its agent's
-//                  new path, T cells of 16 bits; the root's N paths, lengths and t* beside it.
-//   schedule       assembled into `paths` / `lengths` themselves, as in CBS; `src` remembers which node gave an agent its path.
+//   focal search   ecbs_search / ecbs_backtrace below: t*, and the arrival (plane ka, step ta) that the trace starts from.
+//   node pool      workspace: 32 bytes per node (sim_mapf_ecbs_parts.h) and its agent's new path, T cells of 16 bits; the root's N
+//                  paths, lengths and t*, and `src`, beside it.
 //   LDS            the two cell-owner grids of the conflict scan and the conflict count (32 KB) and the path just traced (1 KB).
-//   open list      two linear scans by the wave: the smallest lb, then the smallest (hc, cost, index) inside the focal bound.
 // Integer and bit arithmetic only.  Every store is a per-lane (vector) store or an LDS atomic from plain C++.
 #include <cstdint>
 
 #include "magat_common.h"
 #include "row_board.h"
-#include "sim_mapf_audit_parts.h"      // AUDIT_MAX_N, AUDIT_NONE, audit_stage2
-#include "sim_mapf_cbs_parts.h"        // cbs_wave_min / _max, cbs_mark, cbs_mark_chain, cbs_place
-#include "sim_mapf_ecbs_parts.h"       // ECBS_*, ecbs_node, ecbs_wave_sum, ecbs_count
+#include "sim_mapf_audit_parts.h"      // AUDIT_MAX_N, audit_stage2 - the walk's conflict scan
+#include "sim_mapf_cbs_parts.h"        // cbs_wave
+#include "sim_mapf_ecbs_parts.h"       // ECBS_*, ecbs_node
 #include "sim_mapf_parts.h"            // MAPF_*, board_row
+#include "sim_mapf_tree.h"             // mapf_tree_search, tree_entry_check
 
 namespace {
 
@@ -202,6 +203,27 @@ __device__ void ecbs_backtrace(const u64* hard, const u64* soft, const u64* P, i
 }
 
 template <int K>
+struct ecbs_form : cbs_wave {
+  static constexpr bool FOCAL = true, BORROWS_GRIDS = false;
+  u64 *soft, *P;
+  int *own0, *own1;
+  int T, W, w_milli, ka, ta;
+  template <bool SET>
+  __device__ __forceinline__ void reserve(const int* p) const {
+    if constexpr (K > 1) ecbs_reserve<SET>(soft, p, T, tid);
+  }
+  template <bool CHILD>
+  __device__ __forceinline__ int search(int sr, int sc, int gr, int gc) {
+    ka = 0, ta = 0;
+    return ecbs_search<K>(hard, soft, P, free, sr, sc, gr, gc, T, w_milli, tid, &ka, &ta);
+  }
+  template <bool CHILD>
+  __device__ __forceinline__ void trace(int* cells, int gr, int gc) const {
+    ecbs_backtrace<K>(hard, soft, P, cells, gr, gc, ka, ta, T, W, tid);
+  }
+};
+
+template <int K>
 __global__ __launch_bounds__(64) void mapf_ecbs_kernel(const uint8_t* __restrict__ map, long long map_stride, int H, int W,
                                                        const int* __restrict__ start, const int* __restrict__ goal, int* paths,
                                                        int* lengths, int* __restrict__ makespan, uint8_t* __restrict__ solved,
@@ -209,245 +231,21 @@ __global__ __launch_bounds__(64) void mapf_ecbs_kernel(const uint8_t* __restrict
                                                        int* __restrict__ lower_bound, int* __restrict__ nodes_out,
                                                        int* __restrict__ expanded_out, int* __restrict__ horizon_hit, u64* workspace,
                                                        int N, int T, int max_nodes, int w_milli) {
-  __shared__ int own[2 * ECBS_GRID];              // the owner grids of the conflict scan and the conflict count
-  __shared__ int cells[MAPF_MAX_T];               // the path just traced
+  __shared__ int own[2 * ECBS_GRID];
+  __shared__ int cells[MAPF_MAX_T];
   const int cs = blockIdx.x, lane = threadIdx.x;
   const ecbs_layout lay = ecbs_case_layout(N, T, max_nodes, K);
   u64* hard = workspace + (long long)cs * lay.words;
-  u64* soft = hard + lay.soft;
-  u64* P = hard + lay.planes;
-  uint16_t* root = reinterpret_cast<uint16_t*>(hard + lay.root);
-  uint16_t* npath = reinterpret_cast<uint16_t*>(hard + lay.npath);
-  ecbs_node* nodes = reinterpret_cast<ecbs_node*>(hard + lay.nodes);
-  int* rlen = reinterpret_cast<int*>(hard + lay.ints);      // the root's lengths
-  int* rts = rlen + N;                                       // the root's t*
-  int* src = rts + N;                                        // the node an agent's row of the schedule came from; 0: the root
-  int* at = src + N;
+  int* ints = reinterpret_cast<int*>(hard + lay.ints);      // rlen, rts, src, the two cell rows: N ints each
   const long long a0 = (long long)cs * N;
-  int* len = lengths + a0;
-  int* rows = paths + a0 * T * 2;
-  const int *st = start + a0 * 2, *gl = goal + a0 * 2;
+  const tree_case<ecbs_node> k{start + a0 * 2, goal + a0 * 2, paths + a0 * T * 2, lengths + a0,
+                               reinterpret_cast<uint16_t*>(hard + lay.root), reinterpret_cast<uint16_t*>(hard + lay.npath),
+                               reinterpret_cast<ecbs_node*>(hard + lay.nodes), ints, ints + N, ints + 2 * N, ints + 3 * N, cells,
+                               N, T, H, W, max_nodes, w_milli};
   for (long long i = lane; i < lay.planes; i += 64) hard[i] = 0ull;      // both sets of boards
-  for (int i = lane; i < 2 * ECBS_GRID; i += 64) own[i] = AUDIT_NONE;
-  const uint8_t* mp = map + cs * map_stride;
-  u64 free = 0ull;
-  for (int r = 0; r < H; ++r) {
-    const u64 word = __builtin_amdgcn_ballot_w64(lane < W && mp[r * W + (lane < W ? lane : 0)] == 0);
-    if (lane == r) free = word;
-  }
-  int state = -1, count = 0, expanded = 0, hit = 0;      // state: the status once it is known
-  // screening: every start and goal on a free cell of its own, before any cell indexes anything
-  u64 starts = 0ull, goals = 0ull;
-  for (int a = 0; a < N && state < 0; ++a) {
-    const int sr = __builtin_amdgcn_readfirstlane(st[2 * a]), sc = __builtin_amdgcn_readfirstlane(st[2 * a + 1]);
-    const int gr = __builtin_amdgcn_readfirstlane(gl[2 * a]), gc = __builtin_amdgcn_readfirstlane(gl[2 * a + 1]);
-    const bool inside = sr >= 0 && sr < H && sc >= 0 && sc < W && gr >= 0 && gr < H && gc >= 0 && gc < W;
-    const u64 sbit = inside ? 1ull << sc : 0ull, gbit = inside ? 1ull << gc : 0ull;
-    const bool ok = wave_any(lane == sr && (free & ~starts & sbit)) && wave_any(lane == gr && (free & ~goals & gbit));
-    if (!ok) state = 3;
-    if (lane == sr) starts |= sbit;
-    if (lane == gr) goals |= gbit;
-  }
-  __syncthreads();      // the cleared boards
-  // the root: the agents in index order, each against the soft boards of those before it
-  int cost = 0, lb = 0;
-  for (int a = 0; a < N && state < 0; ++a) {
-    const int sr = __builtin_amdgcn_readfirstlane(st[2 * a]), sc = __builtin_amdgcn_readfirstlane(st[2 * a + 1]);
-    const int gr = __builtin_amdgcn_readfirstlane(gl[2 * a]), gc = __builtin_amdgcn_readfirstlane(gl[2 * a + 1]);
-    int ka = 0, ta = 0;
-    const int tstar = ecbs_search<K>(hard, soft, P, free, sr, sc, gr, gc, T, w_milli, lane, &ka, &ta);
-    if (tstar < 0) {
-      state = 2, hit = 1;
-      break;
-    }
-    __syncthreads();
-    ecbs_backtrace<K>(hard, soft, P, cells, gr, gc, ka, ta, T, W, lane);
-    __syncthreads();
-    for (int t = lane; t <= ta; t += 64) root[(long long)a * T + t] = (uint16_t)cells[t];
-    if (lane == 0) rlen[a] = len[a] = ta + 1, rts[a] = tstar;
-    cost += ta, lb += tstar;
-    __syncthreads();      // the path is read by other lanes; `cells` is traced again
-    cbs_place(rows + (long long)a * T * 2, root + (long long)a * T, ta + 1, T, lane);
-    __syncthreads();
-    if constexpr (K > 1) {
-      ecbs_reserve<true>(soft, rows + (long long)a * T * 2, T, lane);
-      __syncthreads();
-    }
-  }
-  if (state < 0) {
-    if constexpr (K > 1) {
-      for (int a = 0; a < N; ++a) ecbs_reserve<false>(soft, rows + (long long)a * T * 2, T, lane);
-    }
-    int span = 0;
-    for (int base = 0; base < N; base += 64) {
-      const int b = base + lane, l = b < N ? len[b] : 1;
-      span = l > span ? l : span;
-    }
-    span = cbs_wave_max(span);
-    const int hc = ecbs_count(rows, N, T, W, span, own, own + ECBS_GRID, at, at + N, lane, 64, ecbs_wave_sum);
-    if (lane == 0) nodes[0] = ecbs_node{-1, cost, lb, hc, ECBS_OPEN, 0, 0, 0};
-    count = 1;
-  }
-  int best_cost = 0, lbmin = -1;
-  while (state < 0) {
-    __syncthreads();      // the nodes, their paths, the cleared boards
-    // the smallest lb of the open list, then the smallest (hc, cost, index) among the open nodes inside w * that
-    int lo = AUDIT_NONE;
-    for (int i = lane; i < count; i += 64) {
-      const ecbs_node nd = nodes[i];
-      if ((nd.who & ECBS_OPEN) && nd.lb < lo) lo = nd.lb;
-    }
-    lo = cbs_wave_min(lo);
-    if (lo == AUDIT_NONE) {
-      state = 2;
-      break;
-    }
-    lbmin = lo;
-    int bh = AUDIT_NONE, bc = AUDIT_NONE, bi = AUDIT_NONE;
-    for (int i = lane; i < count; i += 64) {
-      const ecbs_node nd = nodes[i];
-      if (!(nd.who & ECBS_OPEN) || 1000LL * nd.cost > (long long)w_milli * lo) continue;
-      if (nd.hc < bh || (nd.hc == bh && nd.cost < bc)) bh = nd.hc, bc = nd.cost, bi = i;
-    }
-    for (int off = 32; off >= 1; off >>= 1) {
-      const int oh = __shfl_xor(bh, off, 64), oc = __shfl_xor(bc, off, 64), oi = __shfl_xor(bi, off, 64);
-      if (oh < bh || (oh == bh && (oc < bc || (oc == bc && oi < bi)))) bh = oh, bc = oc, bi = oi;
-    }
-    if (bi == AUDIT_NONE) {      // (the node that gives the smallest lb is inside the bound: not reached)
-      state = 2;
-      break;
-    }
-    best_cost = bc;
-    const int blb = __builtin_amdgcn_readfirstlane(nodes[bi].lb);
-    __syncthreads();      // everybody has read the node before it is closed
-    if (lane == 0) nodes[bi].who &= ~ECBS_OPEN;
-    // its schedule: the first node of the chain that names an agent holds its path, the root the others'
-    u64 named = 0ull;      // agents 64 * lane .. 64 * lane + 63
-    for (int i = bi; i > 0; i = __builtin_amdgcn_readfirstlane(nodes[i].parent)) {
-      const int who = __builtin_amdgcn_readfirstlane(nodes[i].who), x = who & 4095;
-      if (wave_any(lane == (x >> 6) && has_bit(named, x & 63))) continue;
-      if (lane == (x >> 6)) named |= 1ull << (x & 63);
-      const int lx = (who >> 16 & 255) + 1;
-      cbs_place(rows + (long long)x * T * 2, npath + (long long)i * T, lx, T, lane);
-      if (lane == 0) len[x] = lx, src[x] = i;
-    }
-    for (int a = 0; a < N; ++a) {
-      if (wave_any(lane == (a >> 6) && has_bit(named, a & 63))) continue;
-      const int la = __builtin_amdgcn_readfirstlane(rlen[a]);
-      cbs_place(rows + (long long)a * T * 2, root + (long long)a * T, la, T, lane);
-      if (lane == 0) len[a] = la, src[a] = 0;
-    }
-    __syncthreads();
-    int t2 = -1;
-    const int key2 = audit_stage2(rows, N, T, W, own, own + ECBS_GRID, at, at + N, lane, 64, [](int key) {
-      key = cbs_wave_min(key);
-      __syncthreads();
-      return key;
-    }, &t2);
-    if (key2 == AUDIT_NONE) {
-      state = 0;
-      break;
-    }
-    if (count + 2 > max_nodes) {
-      state = 1;
-      break;
-    }
-    ++expanded;
-    __syncthreads();      // the scan's reads of the grids lie behind
-    for (int i = lane; i < H * W; i += 64) own[i] = own[ECBS_GRID + i] = AUDIT_NONE;
-    const int kind = key2 & 1;
-    for (int k = 0; k < 2; ++k) {
-      const int x = k ? key2 >> 1 & 4095 : key2 >> 13, child = count + k;
-      const int lx = __builtin_amdgcn_readfirstlane(len[x]), from = __builtin_amdgcn_readfirstlane(src[x]);
-      const int tx = from ? __builtin_amdgcn_readfirstlane(nodes[from].tstar) : __builtin_amdgcn_readfirstlane(rts[x]);
-      int* px = rows + (long long)x * T * 2;
-      const int th = t2 < lx ? t2 : lx - 1;
-      int cr = __builtin_amdgcn_readfirstlane(px[2 * th]), cc = __builtin_amdgcn_readfirstlane(px[2 * th + 1]), board = 0;
-      if (kind) {      // its own step at t2: from (fr, fc) in direction d - closed by bit (fr, fc) of A_opp(d)[t2]
-        const int fr = __builtin_amdgcn_readfirstlane(px[2 * t2 - 2]), fc = __builtin_amdgcn_readfirstlane(px[2 * t2 - 1]);
-        const int dr = cr - fr, dc = cc - fc, d = dr == -1 ? 0 : dc == -1 ? 1 : dr == 1 ? 2 : 3;
-        board = 1 + ((d + 2) & 3), cr = fr, cc = fc;
-      }
-      cbs_mark<true>(hard, board, t2, cr, cc, lane);
-      cbs_mark_chain<true>(hard, nodes, bi, x, lane);
-      if constexpr (K > 1) {
-        for (int o = 0; o < N; ++o)
-          if (o != x) ecbs_reserve<true>(soft, rows + (long long)o * T * 2, T, lane);
-      }
-      __syncthreads();
-      const int sr = __builtin_amdgcn_readfirstlane(st[2 * x]), sc = __builtin_amdgcn_readfirstlane(st[2 * x + 1]);
-      const int gr = __builtin_amdgcn_readfirstlane(gl[2 * x]), gc = __builtin_amdgcn_readfirstlane(gl[2 * x + 1]);
-      int ka = 0, ta = 0;
-      const int tstar = ecbs_search<K>(hard, soft, P, free, sr, sc, gr, gc, T, w_milli, lane, &ka, &ta);
-      __syncthreads();
-      if (tstar >= 0) {
-        ecbs_backtrace<K>(hard, soft, P, cells, gr, gc, ka, ta, T, W, lane);
-        __syncthreads();
-        for (int t = lane; t <= ta; t += 64) npath[(long long)child * T + t] = (uint16_t)cells[t];
-      } else {
-        hit = 1;
-      }
-      __syncthreads();      // every load of the boards lies behind; the child's path is read by other lanes
-      cbs_mark<false>(hard, board, t2, cr, cc, lane);
-      cbs_mark_chain<false>(hard, nodes, bi, x, lane);
-      if constexpr (K > 1) {
-        for (int o = 0; o < N; ++o)
-          if (o != x) ecbs_reserve<false>(soft, rows + (long long)o * T * 2, T, lane);
-      }
-      int hc = 0;
-      if (tstar >= 0) {      // the child's own schedule: the agent's row replaced, counted, put back
-        cbs_place(px, npath + (long long)child * T, ta + 1, T, lane);
-        if (lane == 0) len[x] = ta + 1;
-        __syncthreads();
-        int span = 0;
-        for (int base = 0; base < N; base += 64) {
-          const int b = base + lane, l = b < N ? len[b] : 1;
-          span = l > span ? l : span;
-        }
-        span = cbs_wave_max(span);
-        hc = ecbs_count(rows, N, T, W, span, own, own + ECBS_GRID, at, at + N, lane, 64, ecbs_wave_sum);
-        cbs_place(px, from ? npath + (long long)from * T : root + (long long)x * T, lx, T, lane);
-        if (lane == 0) len[x] = lx;
-      }
-      if (lane == 0)
-        nodes[child] = ecbs_node{bi, tstar >= 0 ? bc - (lx - 1) + ta : -1, tstar >= 0 ? blb - tx + tstar : -1, hc,
-                                 x | board << 12 | (tstar >= 0 ? ECBS_OPEN | ta << 16 : 0), t2 | cr << 16 | cc << 24,
-                                 tstar >= 0 ? tstar : 0, 0};
-      __syncthreads();
-    }
-    count += 2;
-  }
-  // the answer stands in paths / lengths already; every other case gets the start cells
-  int longest = 0;
-  if (state == 0) {
-    __syncthreads();
-    for (int base = 0; base < N; base += 64) {
-      const int b = base + lane, l = b < N ? len[b] : 1;
-      longest = l - 1 > longest ? l - 1 : longest;
-    }
-    longest = cbs_wave_max(longest);
-  } else {
-    __syncthreads();      // the conflict scan has read the rows
-    for (int a = 0; a < N; ++a) {
-      const int sr = st[2 * a], sc = st[2 * a + 1];
-      int* p = rows + (long long)a * T * 2;
-      for (int t = lane; t < T; t += 64) {
-        p[2 * t] = sr;
-        p[2 * t + 1] = sc;
-      }
-      if (lane == 0) len[a] = 1;
-    }
-  }
-  if (lane == 0) {
-    makespan[cs] = longest;
-    solved[cs] = state == 0 ? 1 : 0;
-    status[cs] = state;
-    flowtime[cs] = state == 0 ? best_cost : -1;
-    lower_bound[cs] = state <= 1 ? lbmin : -1;
-    nodes_out[cs] = count;
-    expanded_out[cs] = expanded;
-    horizon_hit[cs] = hit;
-  }
+  ecbs_form<K> f{{lane, hard, 0ull}, hard + lay.soft, hard + lay.planes, own, own + ECBS_GRID, T, W, w_milli, 0, 0};
+  f.load_free(map + cs * map_stride, H, W);
+  mapf_tree_search(f, k, tree_out{makespan, solved, status, flowtime, lower_bound, nodes_out, expanded_out, horizon_hit}, cs);
 }
 
 }  // namespace
@@ -464,15 +262,11 @@ extern "C" int magat_sim_mapf_ecbs(const uint8_t* map, int map_batched, int H, i
                                    int32_t* flowtime, int32_t* lower_bound, int32_t* nodes, int32_t* expanded, int32_t* horizon_hit,
                                    void* workspace, size_t workspace_bytes, int C, int N, int T, int max_nodes, int w_milli, int levels,
                                    void* stream) {
-  if (!map || !start || !goal || !paths || !lengths || !makespan || !solved || !status || !flowtime || !lower_bound || !nodes ||
-      !expanded || !horizon_hit || !workspace)
-    return MAGAT_ERR_NULL;
-  if (H <= 0 || W <= 0 || C <= 0 || N <= 0 || T <= 0 || max_nodes <= 0 || levels <= 0 || w_milli < 1000) return MAGAT_ERR_BAD_SHAPE;
-  if (H > MAPF_SIDE || W > MAPF_SIDE || T > MAPF_MAX_T || N > AUDIT_MAX_N || max_nodes > ECBS_MAX_NODES || levels > ECBS_MAX_LEVELS ||
-      w_milli > ECBS_MAX_W_MILLI)
-    return MAGAT_ERR_UNSUPPORTED;
-  if (workspace_bytes < magat_sim_mapf_ecbs_workspace_bytes(C, N, T, max_nodes, levels)) return MAGAT_ERR_UNSUPPORTED;
-  if (reinterpret_cast<uintptr_t>(workspace) % sizeof(u64)) return MAGAT_ERR_WORKSPACE;
+  const int rc = tree_entry_check({map, start, goal, paths, lengths, makespan, solved, status, flowtime, lower_bound, nodes, expanded, horizon_hit},
+                                  H, W, C, N, T, max_nodes, levels > 0 && w_milli >= 1000, levels <= ECBS_MAX_LEVELS && w_milli <= ECBS_MAX_W_MILLI,
+                                  MAPF_SIDE, MAPF_MAX_T, ECBS_MAX_NODES, workspace, workspace_bytes,
+                                  magat_sim_mapf_ecbs_workspace_bytes(C, N, T, max_nodes, levels));
+  if (rc != MAGAT_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   magat_form_note(MAGAT_FORM_SIM_MAPF_ECBS);
   const int pid = magat_prof_begin(MAGAT_TAG_SIM_MAPF_ECBS, st);

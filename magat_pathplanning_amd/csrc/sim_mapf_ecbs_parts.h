@@ -1,7 +1,7 @@
-// What the two forms of ECBS (sim_mapf_ecbs.hip, sim_mapf_ecbs_wide.hip) share: the limits, the node of the tree and the conflict
-// count hc of a schedule.  The rule is in include/magat_hip.h and DESIGN 4.11, restated cell by cell in tests/ecbs_restatement.py.
-// The forms differ in how a map is held (one wave with a word per row, or a workgroup with up to four) and so bring group_sum(n):
-// the sum over the workgroup, the same value for every thread.
+// What the two forms of ECBS (sim_mapf_ecbs.hip, sim_mapf_ecbs_wide.hip) share below the tree walk (sim_mapf_tree.h): the limits, the
+// node of the tree and the conflict count hc of a schedule.  The rule is in include/magat_hip.h and DESIGN 4.11, restated cell by cell
+// in tests/ecbs_restatement.py.  The forms differ in how a map is held (one wave with a word per row, or a workgroup with up to four)
+// and so bring group_sum(n): the sum over the workgroup (row_board.h: wave_all_sum, then the mail), the same value for every thread.
 // Every store is a per-lane (vector) store or an atomic from plain C++.
 #pragma once
 #include <cstdint>
@@ -12,23 +12,17 @@
 constexpr int ECBS_MAX_NODES = 4096;
 constexpr int ECBS_MAX_LEVELS = 4;
 constexpr int ECBS_MAX_W_MILLI = 1 << 20;
-constexpr int ECBS_OPEN = 1 << 15;
 
 struct ecbs_node {
   int parent;
   int cost;      // the flowtime of the node's schedule; -1: the child found no arrival
   int lb;        // the sum of the agents' t*
   int hc;        // the conflicts of the node's schedule
-  int who;       // agent | board << 12 | open << 15 | (narrow form only, lengths up to 256: (length - 1) << 16)
+  int who;       // agent | board << 12 | open << 15
   int what;      // the constraint: t | row << 16 | col << 24
   int tstar;     // the re-planned agent's bound
-  int len1;      // the wide form, lengths up to 1024: length - 1; the narrow form: 0
+  int len1;      // the length of its new path - 1 (up to 1023 in the wide form: a word of its own in both)
 };
-
-__device__ __forceinline__ int ecbs_wave_sum(int v) {
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
 
 // hc of the schedule in `rows`, over t < span: own_t[cell] is the smallest agent on a cell at t (audit_stage2's grids, all
 // AUDIT_NONE going in and coming out).  Counted: the agents a with own_t[cell_a(t)] < a, and for t >= 1 the agents a that moved,

@@ -3,19 +3,20 @@
 //   magat_sim_mapf_ecbs_wide_workspace_bytes   per case: hard and soft boards, the planes, the root's paths, the node pool, five int
 //                                              rows and the two cell-owner grids
 //   magat_sim_mapf_ecbs_wide                   one workgroup per case runs the whole tree; one launch, no host round trip
-// The layout of wmapf_plan_kernel (sim_mapf_wide.hip): `rows` = 64 ceil(H / 64) threads, thread = map row, NW = 1, 2 or 4 64-bit
-// words per row in registers, votes and minima across the wavefronts through the LDS mail (row_board.h).  Per case, in the workspace:
+// The tree is sim_mapf_tree.h's walk, the one the narrow form runs, under the focal rule.  This file brings its form.  The layout of
+// wmapf_plan_kernel (sim_mapf_wide.hip): `rows` = 64 ceil(H / 64) threads, thread = map row, NW = 1, 2 or 4 64-bit words per row in
+// registers, votes and minima across the wavefronts through the LDS mail (row_board.h).  Per case, in the workspace:
 //   hard boards    [t][V, A_up, A_left, A_down, A_right][row][NW]: the constraints of the agent that is searched.
 //   soft boards    a second set: the planner's reservation of every OTHER agent of the schedule the search runs against, set before
-//                  a search and cleared after it by threads over t (a thread owns the words of its t).
+//                  a search and cleared after it by threads over t (a thread owns the words of its t).  None at K = 1.
 //   planes         [k][t][row][NW], K = levels of them, as in the narrow form.  A thread reads back its own row, and in the
 //                  backtrace the rows next to the cell it stands on, behind a barrier.
-//   node pool      32 bytes per node - the narrow form's, but the length (10 bits here) has its own word - and its agent's new path,
-//                  T cells of 16 bits; the root's N paths, lengths and t* beside it.
+//   node pool      32 bytes per node (sim_mapf_ecbs_parts.h) and its agent's new path, T cells of 16 bits; the root's N paths, lengths
+//                  and t*, and `src`, beside it.
 //   grids          the two cell-owner grids of the conflict scan and the conflict count, 2 * H * W ints (512 KB at 256 x 256: not
-//                  LDS), set to "nobody" here, global atomicMin; the cell of every agent at two steps in the int rows.
+//                  LDS), global atomicMin; the cell of every agent at two steps in the int rows.
 //   LDS            seven copies of the mail - a step of the flood sends the boundary rows of up to seven boards in one round - and
-//                  the path just traced (4 KB).
+//                  the path just traced (4 KB).  The walk's reductions go through copy 0.
 // The flood takes ONE barrier per step: the boundary rows of every plane's hard- and clean-masked fronts and the votes (the goal is
 // in plane k; plane K - 1 is not empty) travel together.  The backtrace takes one per step too: every candidate of both planes and
 // the soft-V test are one posted word.  All control flow around a barrier is uniform over the workgroup: every condition on it
@@ -25,9 +26,10 @@
 
 #include "magat_common.h"
 #include "row_board.h"
-#include "sim_mapf_audit_parts.h"      // AUDIT_MAX_N, AUDIT_NONE, audit_stage2
-#include "sim_mapf_cbs_parts.h"        // cbs_wave_min / _max, cbs_for_chain, cbs_place
-#include "sim_mapf_ecbs_parts.h"       // ECBS_*, ecbs_node, ecbs_wave_sum, ecbs_count
+#include "sim_mapf_audit_parts.h"      // AUDIT_MAX_N, audit_stage2 - the walk's conflict scan
+#include "sim_mapf_cbs_parts.h"        // (the walk's cbs_mark_chain, cbs_place)
+#include "sim_mapf_ecbs_parts.h"       // ECBS_*, ecbs_node
+#include "sim_mapf_tree.h"             // mapf_tree_search, tree_entry_check
 #include "sim_mapf_wide_parts.h"       // WMAPF_MAX_T, wide_rows / wide_words, wide_layers
 
 namespace {
@@ -65,11 +67,6 @@ template <int NW>
 using wecbs_set = wide_layers<NW, WECBS_BOARDS>;
 template <int NW>
 using wecbs_plane = wide_layers<NW, 1>;
-
-__device__ __forceinline__ int wecbs_wave_or(int v) {
-  for (int off = 32; off >= 1; off >>= 1) v |= __shfl_xor(v, off, 64);
-  return v;
-}
 
 // one constraint bit, by the thread of its row
 template <bool SET, int NW>
@@ -123,7 +120,7 @@ __device__ int wecbs_search(const wecbs_set<NW>& hard, const wecbs_set<NW>& soft
   int hit = -1;      // threads over t, ascending: a thread's last hit is its largest
   for (int t = tid; t < T; t += nt)
     if (has_bit(hard.at(t, 0, gr)[gc >> 6], gc & 63)) hit = t;
-  wide_post(s, 0, cbs_wave_max(hit));
+  wide_post(s, 0, wave_all_max(hit));
   const int last = wide_max(s, wide_sync(s), 0);
   if (last >= T - 1) return -1;      // the goal is held for ever
   wboard<NW> cur[K];
@@ -170,7 +167,7 @@ __device__ int wecbs_search(const wecbs_set<NW>& hard, const wecbs_set<NW>& soft
           wide_post_rows(sk, cur[k] & ~c[3], cur[k] & ~c[1]);
         }
       }
-      wide_post(s, 0, wecbs_wave_or(mine));
+      wide_post(s, 0, wave_all_or(mine));
       const int p = wide_sync(s);
       const int votes = wide_or(s, p, 0);
       if (tstar < 0) {
@@ -266,7 +263,7 @@ __device__ void wecbs_backtrace(const wecbs_set<NW>& hard, const wecbs_set<NW>& 
         if constexpr (K > 1) mine |= (int)(tid == r && wb_has(soft.load(t, 0, tid), c)) << 10;
       }
     }
-    wide_post(s, 0, wecbs_wave_or(mine));
+    wide_post(s, 0, wave_all_or(mine));
     const int votes = wide_or(s, wide_sync(s), 0);
     int mv = -1;
     if (k == K - 1) {
@@ -287,6 +284,93 @@ __device__ void wecbs_backtrace(const wecbs_set<NW>& hard, const wecbs_set<NW>& 
 }
 
 template <int NW, int K>
+struct wecbs_form {
+  static constexpr bool FOCAL = true, BORROWS_GRIDS = false;
+  int tid, nt;      // nt = rows
+  wide_seat s;
+  wecbs_set<NW> hard, soft;
+  u64* planes;
+  long long plane_words;
+  int *own0, *own1;
+  wboard<NW> free;
+  int T, W, w_milli, ka, ta;
+  __device__ __forceinline__ int group_min(int v) {
+    wide_post(s, 0, wave_all_min(v));
+    return wide_min(s, wide_sync(s), 0);
+  }
+  __device__ __forceinline__ int group_max(int v) {
+    wide_post(s, 0, wave_all_max(v));
+    return wide_max(s, wide_sync(s), 0);
+  }
+  __device__ __forceinline__ int group_sum(int v) {
+    wide_post(s, 0, wave_all_sum(v));
+    return wide_sum(s, wide_sync(s), 0);
+  }
+  __device__ __forceinline__ void group_min3(int& a, int& b, int& c) {      // the butterfly, then the waves' three ints through the mail
+    wave_all_min3(a, b, c);
+    wide_post(s, 0, a);
+    wide_post(s, 1, b);
+    wide_post(s, 2, c);
+    const int p = wide_sync(s);
+    for (int w = 0; w < s.nwaves; ++w) {
+      const int oa = s.mail->num[p][w][0], ob = s.mail->num[p][w][1], oc = s.mail->num[p][w][2];
+      if (oa < a || (oa == a && (ob < b || (ob == b && oc < c)))) a = oa, b = ob, c = oc;
+    }
+  }
+  // free cells: the rows of this wave, each read by the lanes over its columns, one ballot per word; rows >= H and bits >= W
+  // stay zero
+  __device__ __forceinline__ void load_free(const uint8_t* mp, int H, int W) {
+    free = wb_zero<NW>();
+    for (int r = 64 * s.wave; r < H && r < 64 * s.wave + 64; ++r) {
+#pragma unroll
+      for (int k = 0; k < NW; ++k) {
+        const int col = 64 * k + s.lane;
+        const u64 word = __builtin_amdgcn_ballot_w64(col < W && mp[r * W + (col < W ? col : 0)] == 0);
+        if (tid == r) free.w[k] = word;
+      }
+    }
+  }
+  __device__ __forceinline__ bool screen(const int* st, const int* gl, int N, int H, int W) {      // one round per agent
+    wboard<NW> starts = wb_zero<NW>(), goals = wb_zero<NW>();
+    bool ok = true;
+    for (int a = 0; a < N && ok; ++a) {
+      const int sr = __builtin_amdgcn_readfirstlane(st[2 * a]), sc = __builtin_amdgcn_readfirstlane(st[2 * a + 1]);
+      const int gr = __builtin_amdgcn_readfirstlane(gl[2 * a]), gc = __builtin_amdgcn_readfirstlane(gl[2 * a + 1]);
+      const bool inside = sr >= 0 && sr < H && sc >= 0 && sc < W && gr >= 0 && gr < H && gc >= 0 && gc < W;
+      const int scc = inside ? sc : 0, gcc = inside ? gc : 0;
+      const bool s_ok = inside && tid == sr && wb_has(free & ~starts, scc), g_ok = inside && tid == gr && wb_has(free & ~goals, gcc);
+      wide_post(s, 0, (int)wave_any(s_ok) | (int)wave_any(g_ok) << 1);
+      ok = wide_or(s, wide_sync(s), 0) == 3;
+      if (inside && tid == sr) starts = starts | wb_bit<NW>(scc);
+      if (inside && tid == gr) goals = goals | wb_bit<NW>(gcc);
+    }
+    return ok;
+  }
+  template <bool SET>
+  __device__ __forceinline__ void mark(int board, int t, int r, int c) const {
+    wecbs_mark<SET>(hard, board, t, r, c, tid);
+  }
+  template <bool SET>
+  __device__ __forceinline__ void reserve(const int* p) const {
+    if constexpr (K > 1) wecbs_reserve<SET>(soft, p, T, tid, nt);
+  }
+  template <bool CHILD>
+  __device__ __forceinline__ int search(int sr, int sc, int gr, int gc) {
+    // (the seat and the arrival go in as locals of their own: the inliner weighs the call by what it can keep in registers, as it
+    // did when they were the kernel's locals, and a member of the form counts for that only as long as every other member does)
+    wide_seat seat = s;
+    int k_arrival = 0, t_arrival = 0;
+    const int tstar = wecbs_search<NW, K>(hard, soft, planes, plane_words, seat, free, sr, sc, gr, gc, T, w_milli, tid, nt, &k_arrival, &t_arrival);
+    s = seat, ka = k_arrival, ta = t_arrival;
+    return tstar;
+  }
+  template <bool CHILD>
+  __device__ __forceinline__ void trace(int* cells, int gr, int gc) {
+    wecbs_backtrace<NW, K>(hard, soft, planes, plane_words, s, cells, gr, gc, ka, ta, W, tid, nt);
+  }
+};
+
+template <int NW, int K>
 __global__ __launch_bounds__(WIDE_SIDE) void wmapf_ecbs_kernel(const uint8_t* __restrict__ map, long long map_stride, int H, int W,
                                                                const int* __restrict__ start, const int* __restrict__ goal, int* paths,
                                                                int* lengths, int* __restrict__ makespan, uint8_t* __restrict__ solved,
@@ -295,264 +379,22 @@ __global__ __launch_bounds__(WIDE_SIDE) void wmapf_ecbs_kernel(const uint8_t* __
                                                                int* __restrict__ expanded_out, int* __restrict__ horizon_hit,
                                                                u64* workspace, int N, int T, int max_nodes, int w_milli) {
   __shared__ wide_mail mails[WECBS_MAILS];
-  __shared__ int cells[WMAPF_MAX_T];              // the path just traced
-  const int cs = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;      // nt = rows
-  wide_seat s{mails, tid & 63, tid >> 6, nt >> 6, 0};
+  __shared__ int cells[WMAPF_MAX_T];
+  const int cs = blockIdx.x, tid = threadIdx.x, nt = blockDim.x;
   const wecbs_layout lay = wecbs_case_layout(H, W, N, T, max_nodes, K);
   u64* mine = workspace + (long long)cs * lay.words;
-  const wecbs_set<NW> hard{mine, nt}, soft{mine + lay.soft, nt};
-  u64* planes = mine + lay.planes;
-  const long long plane_words = (long long)T * nt * NW;
-  uint16_t* root = reinterpret_cast<uint16_t*>(mine + lay.root);
-  uint16_t* npath = reinterpret_cast<uint16_t*>(mine + lay.npath);
-  ecbs_node* nodes = reinterpret_cast<ecbs_node*>(mine + lay.nodes);
-  int* rlen = reinterpret_cast<int*>(mine + lay.ints);      // the root's lengths
-  int* rts = rlen + N;                                       // the root's t*
-  int* src = rts + N;                                        // the node an agent's row of the schedule came from; 0: the root
-  int* at = src + N;
+  int* ints = reinterpret_cast<int*>(mine + lay.ints);      // rlen, rts, src, the two cell rows: N ints each
   int* own = reinterpret_cast<int*>(mine + lay.grids);
-  const int grid = H * W;
   const long long a0 = (long long)cs * N;
-  int* len = lengths + a0;
-  int* rows = paths + a0 * T * 2;
-  const int *st = start + a0 * 2, *gl = goal + a0 * 2;
+  const tree_case<ecbs_node> k{start + a0 * 2, goal + a0 * 2, paths + a0 * T * 2, lengths + a0,
+                               reinterpret_cast<uint16_t*>(mine + lay.root), reinterpret_cast<uint16_t*>(mine + lay.npath),
+                               reinterpret_cast<ecbs_node*>(mine + lay.nodes), ints, ints + N, ints + 2 * N, ints + 3 * N, cells,
+                               N, T, H, W, max_nodes, w_milli};
   for (long long i = tid; i < lay.planes; i += nt) mine[i] = 0ull;      // both sets of boards
-  for (int i = tid; i < 2 * grid; i += nt) own[i] = AUDIT_NONE;
-  // free cells: the rows of this wave, each read by the lanes over its columns, one ballot per word; rows >= H and bits >= W
-  // stay zero
-  const uint8_t* mp = map + cs * map_stride;
-  wboard<NW> free = wb_zero<NW>();
-  for (int r = 64 * s.wave; r < H && r < 64 * s.wave + 64; ++r) {
-#pragma unroll
-    for (int k = 0; k < NW; ++k) {
-      const int col = 64 * k + s.lane;
-      const u64 word = __builtin_amdgcn_ballot_w64(col < W && mp[r * W + (col < W ? col : 0)] == 0);
-      if (tid == r) free.w[k] = word;
-    }
-  }
-  const auto group_sum = [&](int n) {
-    wide_post(s, 0, ecbs_wave_sum(n));
-    return wide_sum(s, wide_sync(s), 0);
-  };
-  const auto group_min = [&](int key) {
-    wide_post(s, 0, cbs_wave_min(key));
-    return wide_min(s, wide_sync(s), 0);
-  };
-  const auto longest_length = [&]() {      // max over the agents of len, at least 1
-    int span = 1;
-    for (int b = tid; b < N; b += nt) span = len[b] > span ? len[b] : span;
-    wide_post(s, 0, cbs_wave_max(span));
-    return wide_max(s, wide_sync(s), 0);
-  };
-  int state = -1, count = 0, expanded = 0, hit = 0;      // state: the status once it is known
-  // screening: every start and goal on a free cell of its own, before any cell indexes anything; one round per agent
-  wboard<NW> starts = wb_zero<NW>(), goals = wb_zero<NW>();
-  for (int a = 0; a < N && state < 0; ++a) {
-    const int sr = __builtin_amdgcn_readfirstlane(st[2 * a]), sc = __builtin_amdgcn_readfirstlane(st[2 * a + 1]);
-    const int gr = __builtin_amdgcn_readfirstlane(gl[2 * a]), gc = __builtin_amdgcn_readfirstlane(gl[2 * a + 1]);
-    const bool inside = sr >= 0 && sr < H && sc >= 0 && sc < W && gr >= 0 && gr < H && gc >= 0 && gc < W;
-    const int scc = inside ? sc : 0, gcc = inside ? gc : 0;
-    const bool s_ok = inside && tid == sr && wb_has(free & ~starts, scc), g_ok = inside && tid == gr && wb_has(free & ~goals, gcc);
-    wide_post(s, 0, (int)wave_any(s_ok) | (int)wave_any(g_ok) << 1);
-    if (wide_or(s, wide_sync(s), 0) != 3) state = 3;
-    if (inside && tid == sr) starts = starts | wb_bit<NW>(scc);
-    if (inside && tid == gr) goals = goals | wb_bit<NW>(gcc);
-  }
-  __syncthreads();      // the cleared boards and grids
-  // the root: the agents in index order, each against the soft boards of those before it
-  int cost = 0, lb = 0;
-  for (int a = 0; a < N && state < 0; ++a) {
-    const int sr = __builtin_amdgcn_readfirstlane(st[2 * a]), sc = __builtin_amdgcn_readfirstlane(st[2 * a + 1]);
-    const int gr = __builtin_amdgcn_readfirstlane(gl[2 * a]), gc = __builtin_amdgcn_readfirstlane(gl[2 * a + 1]);
-    int ka = 0, ta = 0;
-    const int tstar = wecbs_search<NW, K>(hard, soft, planes, plane_words, s, free, sr, sc, gr, gc, T, w_milli, tid, nt, &ka, &ta);
-    if (tstar < 0) {
-      state = 2, hit = 1;
-      break;
-    }
-    __syncthreads();      // the planes are read across rows
-    wecbs_backtrace<NW, K>(hard, soft, planes, plane_words, s, cells, gr, gc, ka, ta, W, tid, nt);
-    __syncthreads();
-    for (int t = tid; t <= ta; t += nt) root[(long long)a * T + t] = (uint16_t)cells[t];
-    if (tid == 0) rlen[a] = len[a] = ta + 1, rts[a] = tstar;
-    cost += ta, lb += tstar;
-    __syncthreads();      // the path is read by other threads; `cells` is traced again
-    cbs_place(rows + (long long)a * T * 2, root + (long long)a * T, ta + 1, T, tid, nt);
-    __syncthreads();
-    if constexpr (K > 1) {
-      wecbs_reserve<true>(soft, rows + (long long)a * T * 2, T, tid, nt);
-      __syncthreads();
-    }
-  }
-  if (state < 0) {
-    if constexpr (K > 1) {
-      for (int a = 0; a < N; ++a) wecbs_reserve<false>(soft, rows + (long long)a * T * 2, T, tid, nt);
-    }
-    const int span = longest_length();
-    const int hc = ecbs_count(rows, N, T, W, span, own, own + grid, at, at + N, tid, nt, group_sum);
-    if (tid == 0) nodes[0] = ecbs_node{-1, cost, lb, hc, ECBS_OPEN, 0, 0, 0};
-    count = 1;
-  }
-  int best_cost = 0, lbmin = -1;
-  while (state < 0) {
-    __syncthreads();      // the nodes, their paths, the cleared boards
-    // the smallest lb of the open list, then the smallest (hc, cost, index) among the open nodes inside w * that
-    int lo = AUDIT_NONE;
-    for (int i = tid; i < count; i += nt) {
-      const ecbs_node nd = nodes[i];
-      if ((nd.who & ECBS_OPEN) && nd.lb < lo) lo = nd.lb;
-    }
-    lo = group_min(lo);
-    if (lo == AUDIT_NONE) {
-      state = 2;
-      break;
-    }
-    lbmin = lo;
-    int bh = AUDIT_NONE, bc = AUDIT_NONE, bi = AUDIT_NONE;
-    for (int i = tid; i < count; i += nt) {
-      const ecbs_node nd = nodes[i];
-      if (!(nd.who & ECBS_OPEN) || 1000LL * nd.cost > (long long)w_milli * lo) continue;
-      if (nd.hc < bh || (nd.hc == bh && nd.cost < bc)) bh = nd.hc, bc = nd.cost, bi = i;
-    }
-    for (int off = 32; off >= 1; off >>= 1) {
-      const int oh = __shfl_xor(bh, off, 64), oc = __shfl_xor(bc, off, 64), oi = __shfl_xor(bi, off, 64);
-      if (oh < bh || (oh == bh && (oc < bc || (oc == bc && oi < bi)))) bh = oh, bc = oc, bi = oi;
-    }
-    wide_post(s, 0, bh);
-    wide_post(s, 1, bc);
-    wide_post(s, 2, bi);
-    {
-      const int p = wide_sync(s);
-      for (int w = 0; w < s.nwaves; ++w) {
-        const int oh = mails[0].num[p][w][0], oc = mails[0].num[p][w][1], oi = mails[0].num[p][w][2];
-        if (oh < bh || (oh == bh && (oc < bc || (oc == bc && oi < bi)))) bh = oh, bc = oc, bi = oi;
-      }
-    }
-    if (bi == AUDIT_NONE) {      // (the node that gives the smallest lb is inside the bound: not reached)
-      state = 2;
-      break;
-    }
-    best_cost = bc;
-    const int blb = __builtin_amdgcn_readfirstlane(nodes[bi].lb);
-    __syncthreads();      // everybody has read the node before it is closed
-    if (tid == 0) nodes[bi].who &= ~ECBS_OPEN;
-    __syncthreads();
-    // its schedule: the first node of the chain that names an agent holds its path, the root the others'.  Every wave keeps the
-    // set of the named agents for itself: lane l holds the agents 64 l .. 64 l + 63
-    u64 named = 0ull;
-    for (int i = bi; i > 0; i = __builtin_amdgcn_readfirstlane(nodes[i].parent)) {
-      const int x = __builtin_amdgcn_readfirstlane(nodes[i].who) & 4095;
-      if (wave_any(s.lane == (x >> 6) && has_bit(named, x & 63))) continue;
-      if (s.lane == (x >> 6)) named |= 1ull << (x & 63);
-      const int lx = __builtin_amdgcn_readfirstlane(nodes[i].len1) + 1;
-      cbs_place(rows + (long long)x * T * 2, npath + (long long)i * T, lx, T, tid, nt);
-      if (tid == 0) len[x] = lx, src[x] = i;
-    }
-    for (int a = 0; a < N; ++a) {
-      if (wave_any(s.lane == (a >> 6) && has_bit(named, a & 63))) continue;
-      const int la = __builtin_amdgcn_readfirstlane(rlen[a]);
-      cbs_place(rows + (long long)a * T * 2, root + (long long)a * T, la, T, tid, nt);
-      if (tid == 0) len[a] = la, src[a] = 0;
-    }
-    __syncthreads();
-    int t2 = -1;
-    const int key2 = audit_stage2(rows, N, T, W, own, own + grid, at, at + N, tid, nt, group_min, &t2);
-    if (key2 == AUDIT_NONE) {
-      state = 0;
-      break;
-    }
-    if (count + 2 > max_nodes) {
-      state = 1;
-      break;
-    }
-    ++expanded;
-    __syncthreads();      // the scan's reads of the grids lie behind
-    for (int i = tid; i < 2 * grid; i += nt) own[i] = AUDIT_NONE;
-    const int kind = key2 & 1;
-    for (int k = 0; k < 2; ++k) {
-      const int x = k ? key2 >> 1 & 4095 : key2 >> 13, child = count + k;
-      const int lx = __builtin_amdgcn_readfirstlane(len[x]), from = __builtin_amdgcn_readfirstlane(src[x]);
-      const int tx = from ? __builtin_amdgcn_readfirstlane(nodes[from].tstar) : __builtin_amdgcn_readfirstlane(rts[x]);
-      int* px = rows + (long long)x * T * 2;
-      const int th = t2 < lx ? t2 : lx - 1;
-      int cr = __builtin_amdgcn_readfirstlane(px[2 * th]), cc = __builtin_amdgcn_readfirstlane(px[2 * th + 1]), board = 0;
-      if (kind) {      // its own step at t2: from (fr, fc) in direction d - closed by bit (fr, fc) of A_opp(d)[t2]
-        const int fr = __builtin_amdgcn_readfirstlane(px[2 * t2 - 2]), fc = __builtin_amdgcn_readfirstlane(px[2 * t2 - 1]);
-        const int dr = cr - fr, dc = cc - fc, d = dr == -1 ? 0 : dc == -1 ? 1 : dr == 1 ? 2 : 3;
-        board = 1 + ((d + 2) & 3), cr = fr, cc = fc;
-      }
-      wecbs_mark<true>(hard, board, t2, cr, cc, tid);
-      cbs_for_chain(nodes, bi, x, [&](int b, int t, int r, int c) { wecbs_mark<true>(hard, b, t, r, c, tid); });
-      if constexpr (K > 1) {
-        for (int o = 0; o < N; ++o)
-          if (o != x) wecbs_reserve<true>(soft, rows + (long long)o * T * 2, T, tid, nt);
-      }
-      __syncthreads();
-      const int sr = __builtin_amdgcn_readfirstlane(st[2 * x]), sc = __builtin_amdgcn_readfirstlane(st[2 * x + 1]);
-      const int gr = __builtin_amdgcn_readfirstlane(gl[2 * x]), gc = __builtin_amdgcn_readfirstlane(gl[2 * x + 1]);
-      int ka = 0, ta = 0;
-      const int tstar = wecbs_search<NW, K>(hard, soft, planes, plane_words, s, free, sr, sc, gr, gc, T, w_milli, tid, nt, &ka, &ta);
-      __syncthreads();
-      if (tstar >= 0) {
-        wecbs_backtrace<NW, K>(hard, soft, planes, plane_words, s, cells, gr, gc, ka, ta, W, tid, nt);
-        __syncthreads();
-        for (int t = tid; t <= ta; t += nt) npath[(long long)child * T + t] = (uint16_t)cells[t];
-      } else {
-        hit = 1;
-      }
-      __syncthreads();      // every load of the boards lies behind; the child's path is read by other threads
-      wecbs_mark<false>(hard, board, t2, cr, cc, tid);
-      cbs_for_chain(nodes, bi, x, [&](int b, int t, int r, int c) { wecbs_mark<false>(hard, b, t, r, c, tid); });
-      if constexpr (K > 1) {
-        for (int o = 0; o < N; ++o)
-          if (o != x) wecbs_reserve<false>(soft, rows + (long long)o * T * 2, T, tid, nt);
-      }
-      int hc = 0;
-      if (tstar >= 0) {      // the child's own schedule: the agent's row replaced, counted, put back
-        __syncthreads();     // the reservations were read from the row
-        cbs_place(px, npath + (long long)child * T, ta + 1, T, tid, nt);
-        if (tid == 0) len[x] = ta + 1;
-        __syncthreads();
-        const int span = longest_length();
-        hc = ecbs_count(rows, N, T, W, span, own, own + grid, at, at + N, tid, nt, group_sum);
-        cbs_place(px, from ? npath + (long long)from * T : root + (long long)x * T, lx, T, tid, nt);
-        if (tid == 0) len[x] = lx;
-      }
-      if (tid == 0)
-        nodes[child] = ecbs_node{bi, tstar >= 0 ? bc - (lx - 1) + ta : -1, tstar >= 0 ? blb - tx + tstar : -1, hc,
-                                 x | board << 12 | (tstar >= 0 ? ECBS_OPEN : 0), t2 | cr << 16 | cc << 24,
-                                 tstar >= 0 ? tstar : 0, tstar >= 0 ? ta : 0};
-      __syncthreads();
-    }
-    count += 2;
-  }
-  // the answer stands in paths / lengths already; every other case gets the start cells
-  int longest = 0;
-  if (state == 0) {
-    __syncthreads();
-    longest = longest_length() - 1;
-  } else {
-    __syncthreads();      // the conflict scan has read the rows
-    for (int a = 0; a < N; ++a) {
-      const int sr = st[2 * a], sc = st[2 * a + 1];
-      int* p = rows + (long long)a * T * 2;
-      for (int t = tid; t < T; t += nt) {
-        p[2 * t] = sr;
-        p[2 * t + 1] = sc;
-      }
-      if (tid == 0) len[a] = 1;
-    }
-  }
-  if (tid == 0) {
-    makespan[cs] = longest;
-    solved[cs] = state == 0 ? 1 : 0;
-    status[cs] = state;
-    flowtime[cs] = state == 0 ? best_cost : -1;
-    lower_bound[cs] = state <= 1 ? lbmin : -1;
-    nodes_out[cs] = count;
-    expanded_out[cs] = expanded;
-    horizon_hit[cs] = hit;
-  }
+  wecbs_form<NW, K> f{tid, nt, wide_seat{mails, tid & 63, tid >> 6, nt >> 6, 0}, wecbs_set<NW>{mine, nt}, wecbs_set<NW>{mine + lay.soft, nt},
+                      mine + lay.planes, (long long)T * nt * NW, own, own + H * W, wb_zero<NW>(), T, W, w_milli, 0, 0};
+  f.load_free(map + cs * map_stride, H, W);
+  mapf_tree_search(f, k, tree_out{makespan, solved, status, flowtime, lower_bound, nodes_out, expanded_out, horizon_hit}, cs);
 }
 
 }  // namespace
@@ -569,15 +411,11 @@ extern "C" int magat_sim_mapf_ecbs_wide(const uint8_t* map, int map_batched, int
                                         int32_t* flowtime, int32_t* lower_bound, int32_t* nodes, int32_t* expanded, int32_t* horizon_hit,
                                         void* workspace, size_t workspace_bytes, int C, int N, int T, int max_nodes, int w_milli,
                                         int levels, void* stream) {
-  if (!map || !start || !goal || !paths || !lengths || !makespan || !solved || !status || !flowtime || !lower_bound || !nodes ||
-      !expanded || !horizon_hit || !workspace)
-    return MAGAT_ERR_NULL;
-  if (H <= 0 || W <= 0 || C <= 0 || N <= 0 || T <= 0 || max_nodes <= 0 || levels <= 0 || w_milli < 1000) return MAGAT_ERR_BAD_SHAPE;
-  if (H > WIDE_SIDE || W > WIDE_SIDE || T > WMAPF_MAX_T || N > AUDIT_MAX_N || max_nodes > ECBS_MAX_NODES || levels > ECBS_MAX_LEVELS ||
-      w_milli > ECBS_MAX_W_MILLI)
-    return MAGAT_ERR_UNSUPPORTED;
-  if (workspace_bytes < magat_sim_mapf_ecbs_wide_workspace_bytes(C, H, W, N, T, max_nodes, levels)) return MAGAT_ERR_UNSUPPORTED;
-  if (reinterpret_cast<uintptr_t>(workspace) % sizeof(u64)) return MAGAT_ERR_WORKSPACE;
+  const int rc = tree_entry_check({map, start, goal, paths, lengths, makespan, solved, status, flowtime, lower_bound, nodes, expanded, horizon_hit},
+                                  H, W, C, N, T, max_nodes, levels > 0 && w_milli >= 1000, levels <= ECBS_MAX_LEVELS && w_milli <= ECBS_MAX_W_MILLI,
+                                  WIDE_SIDE, WMAPF_MAX_T, ECBS_MAX_NODES, workspace, workspace_bytes,
+                                  magat_sim_mapf_ecbs_wide_workspace_bytes(C, H, W, N, T, max_nodes, levels));
+  if (rc != MAGAT_OK) return rc;
   hipStream_t st = static_cast<hipStream_t>(stream);
   magat_form_note(MAGAT_FORM_SIM_MAPF_ECBS);
   const int pid = magat_prof_begin(MAGAT_TAG_SIM_MAPF_ECBS, st);

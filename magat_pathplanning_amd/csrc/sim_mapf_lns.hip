@@ -59,18 +59,6 @@ __device__ void lns_stage(int* cells, const int* p, int len, int lane) {
   for (int t = lane; t < len; t += 64) cells[t] = p[2 * t] << 8 | p[2 * t + 1];
 }
 
-__device__ __forceinline__ int lns_wave_sum(int v) {
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ int lns_wave_max(int v) {
-  for (int off = 32; off >= 1; off >>= 1) {
-    const int o = __shfl_xor(v, off, 64);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-
 // how many agents have delay = length - d0 >= x (wave-uniform)
 __device__ int lns_count_ge(const int* len, const int* d0, int N, int x, int lane) {
   int cnt = 0;
@@ -283,8 +271,8 @@ __global__ __launch_bounds__(64) void mapf_lns_kernel(const uint8_t* __restrict_
     total += lb - 1;
     longest = lb > longest ? lb : longest;
   }
-  total = lns_wave_sum(total);
-  longest = lns_wave_max(longest);
+  total = wave_all_sum(total);
+  longest = wave_all_max(longest);
   if (lane == 0) {
     makespan[cs] = longest - 1;
     flow_after[cs] = total;

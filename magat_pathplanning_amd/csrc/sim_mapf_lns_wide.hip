@@ -64,18 +64,6 @@ struct wlns_staged {
   __device__ __forceinline__ int operator()(int t) const { return cells[t]; }
 };
 
-__device__ __forceinline__ int wlns_wave_sum(int v) {
-  for (int off = 32; off >= 1; off >>= 1) v += __shfl_xor(v, off, 64);
-  return v;
-}
-__device__ __forceinline__ int wlns_wave_max(int v) {
-  for (int off = 32; off >= 1; off >>= 1) {
-    const int o = __shfl_xor(v, off, 64);
-    v = o > v ? o : v;
-  }
-  return v;
-}
-
 // how many agents have delay = length - d0 >= x (the same for every thread; one round of the mail)
 __device__ int wlns_count_ge(wide_seat& s, const int* len, const int* d0, int N, int x, int tid, int nt) {
   int cnt = 0;
@@ -299,8 +287,8 @@ __global__ __launch_bounds__(WIDE_SIDE) void wmapf_lns_kernel(const uint8_t* __r
     total += lb - 1;
     longest = lb > longest ? lb : longest;
   }
-  wide_post(s, 0, wlns_wave_sum(total));
-  wide_post(s, 1, wlns_wave_max(longest));
+  wide_post(s, 0, wave_all_sum(total));
+  wide_post(s, 1, wave_all_max(longest));
   const int p = wide_sync(s);
   if (tid == 0) {
     makespan[cs] = wide_max(s, p, 1) - 1;

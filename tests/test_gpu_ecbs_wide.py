@@ -11,6 +11,7 @@ import torch
 import test_host_ecbs as he
 import test_host_ecbs_wide as hw
 from test_gpu_ecbs import EXTRA, form_count, given
+from test_gpu_ecbs import call as he_call
 from test_gpu_mapf import assert_equal_results
 
 pytestmark = pytest.mark.gpu
@@ -55,6 +56,42 @@ def test_a_narrow_shape_goes_to_the_narrow_kernel(gpu_device):
     narrow = ecbs_cases(md, sd, gd, w=1.5, horizon=k["T"], max_nodes=64, levels=4)
     for key in he.KEYS:
         assert torch.equal(got[key], narrow[key]), key
+
+
+# narrow shapes, all four K: the wide entry itself takes them (it refuses only above 256; mapf.py does the routing)
+BOTH_FORMS = (("pocket", 1500, 4, 64), ("hand", 1500, 4, 64), ("small", 1500, 4, 64), ("r8", 1500, 4, 64), ("r8", 1200, 2, 64),
+              ("r8", 1500, 1, 64), ("r8", 1500, 3, 8))
+
+
+@pytest.mark.parametrize("name,w_milli,levels,max_nodes", BOTH_FORMS)
+def test_the_forms_agree_where_both_apply(gpu_device, name, w_milli, levels, max_nodes):
+    """One walk, two forms: magat_sim_mapf_ecbs_wide called directly on a narrow shape, with a workspace of its own size, gives
+    what ecbs_cases gives and what the restatement gives, in every output."""
+    from magat_pathplanning_amd import _native as nat
+    k = he.case(name, w_milli, levels, max_nodes)
+    md, sd, gd = given(k, gpu_device)
+    narrow = he_call(k, md, sd, gd)
+    lib = nat.lib()
+    C, N = sd.shape[:2]
+    H, W = md.shape[-2:]
+    T = k["T"]
+    need = int(lib.magat_sim_mapf_ecbs_wide_workspace_bytes(C, H, W, N, T, max_nodes, levels))
+    assert need == hw.documented_bytes(C, H, W, N, T, max_nodes, levels)
+    ws = torch.empty(need, dtype=torch.uint8, device=gpu_device)
+    got = dict(paths=torch.full((C, N, T, 2), -7, dtype=torch.int32, device=gpu_device),
+               lengths=torch.full((C, N), -7, dtype=torch.int32, device=gpu_device),
+               solved=torch.full((C,), 9, dtype=torch.uint8, device=gpu_device))
+    got.update({key: torch.full((C,), -7, dtype=torch.int32, device=gpu_device) for key in ("makespan",) + EXTRA})
+    rc = lib.magat_sim_mapf_ecbs_wide(nat.ptr(md), int(md.dim() == 3), H, W, nat.ptr(sd), nat.ptr(gd), nat.ptr(got["paths"]),
+                                      nat.ptr(got["lengths"]), nat.ptr(got["makespan"]), nat.ptr(got["solved"]),
+                                      *[nat.ptr(got[key]) for key in EXTRA], nat.ptr(ws), need, C, N, T, max_nodes, w_milli, levels,
+                                      nat.current_stream(sd.device))
+    assert rc == 0
+    torch.cuda.synchronize()
+    assert set(he.KEYS) == set(got)
+    for key in he.KEYS:
+        assert torch.equal(got[key], narrow[key]), key
+    assert_equal_results(got, k["want"], he.KEYS, "%s at %r through the wide entry" % (name, (w_milli, levels, max_nodes)))
 
 
 def test_more_cases_than_compute_units(gpu_device):

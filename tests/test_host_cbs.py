@@ -289,9 +289,11 @@ def test_cbs_entries_are_declared_bound_and_built():
     assert "sim_mapf_cbs.hip" in build_native.SOURCES
     text = open(os.path.join(CSRC, "sim_mapf_cbs.hip")).read()
     assert "MAGAT_FORM_SIM_MAPF_CBS" in text and "MAGAT_TAG_SIM_MAPF_CBS" in text
-    for part in ("sim_mapf_parts.h", "sim_mapf_audit_parts.h", "row_board.h"):
+    for part in ("sim_mapf_parts.h", "sim_mapf_audit_parts.h", "sim_mapf_tree.h", "row_board.h"):
         assert '#include "%s"' % part in text and part in build_native.HEADERS
-    assert "mapf_search<true>" in text and "mapf_search<false>" in text and "audit_stage2(" in text
+    tree = open(os.path.join(CSRC, "sim_mapf_tree.h")).read()      # the walk, once for the three tree experts: it holds the conflict scan
+    assert "mapf_search<true>" in text and "mapf_search<false>" in text and "mapf_tree_search(" in text and "audit_stage2(" in tree
+    assert "audit_stage2(" not in text and "asm" not in tree and "printf" not in tree and "assert(" not in tree
     assert "asm" not in text and "printf" not in text and "assert(" not in text and "hipDeviceSynchronize" not in text
     assert re.search(r"^size_t magat_sim_mapf_cbs_workspace_bytes\(int C, int N, int T, int max_nodes\);", hdr, re.M)
     assert re.search(r"^int magat_sim_mapf_cbs\(", hdr, re.M)

@@ -193,14 +193,22 @@ def test_ecbs_entries_are_declared_bound_and_built():
     cbs = open(os.path.join(CSRC, "sim_mapf_cbs.hip")).read()
     parts = open(os.path.join(CSRC, "sim_mapf_cbs_parts.h")).read()
     assert "MAGAT_FORM_SIM_MAPF_ECBS" in text and "MAGAT_TAG_SIM_MAPF_ECBS" in text
-    for part in ("sim_mapf_parts.h", "sim_mapf_audit_parts.h", "sim_mapf_cbs_parts.h", "row_board.h"):
+    for part in ("sim_mapf_parts.h", "sim_mapf_audit_parts.h", "sim_mapf_cbs_parts.h", "sim_mapf_tree.h", "row_board.h"):
         assert '#include "%s"' % part in text and part in build_native.HEADERS
     assert '#include "sim_mapf_cbs_parts.h"' in cbs
-    for shared in ("cbs_wave_min", "cbs_wave_max", "cbs_mark", "cbs_mark_chain", "cbs_place"):      # one copy, in the shared header
-        assert re.search(r"\b%s\(" % shared, parts), shared
-        for body in (text, cbs):
+    board = open(os.path.join(CSRC, "row_board.h")).read()
+    tree = open(os.path.join(CSRC, "sim_mapf_tree.h")).read()
+    # one copy, in the shared header: the chain marks and the placing in the parts, the wave reductions with the row boards
+    for shared, home in (("wave_all_min", board), ("wave_all_max", board), ("wave_all_sum", board), ("wave_all_or", board), ("wave_all_min3", board),
+                         ("cbs_mark", parts), ("cbs_mark_chain", parts), ("cbs_place", parts)):
+        assert re.search(r"\b%s\(" % shared, home), shared
+        for body in (text, cbs, tree):
             assert not re.search(r"^__device__ [^\n]*\b%s\(" % shared, body, re.M), shared
-    assert "audit_stage2(" in text and "asm" not in text and "printf" not in text and "assert(" not in text
+    for body in (text, cbs, parts, tree):      # and no butterfly of their own
+        assert "__shfl_xor" not in body
+    # the walk, once: this file calls it and holds no conflict scan of its own
+    assert "mapf_tree_search(" in text and "audit_stage2(" in tree and "audit_stage2(" not in text
+    assert "asm" not in text and "printf" not in text and "assert(" not in text
     assert "hipDeviceSynchronize" not in text
     assert re.search(r"^size_t magat_sim_mapf_ecbs_workspace_bytes\(int C, int N, int T, int max_nodes, int levels\);", hdr, re.M)
     assert re.search(r"^int magat_sim_mapf_ecbs\(", hdr, re.M)

@@ -175,15 +175,20 @@ def test_wide_ecbs_entries_are_declared_bound_and_built():
     narrow = open(os.path.join(CSRC, "sim_mapf_ecbs.hip")).read()
     parts = open(os.path.join(CSRC, "sim_mapf_ecbs_parts.h")).read()
     assert "MAGAT_FORM_SIM_MAPF_ECBS" in text and "MAGAT_TAG_SIM_MAPF_ECBS" in text
-    for part in ("sim_mapf_wide_parts.h", "sim_mapf_audit_parts.h", "sim_mapf_cbs_parts.h", "sim_mapf_ecbs_parts.h", "row_board.h"):
+    for part in ("sim_mapf_wide_parts.h", "sim_mapf_audit_parts.h", "sim_mapf_cbs_parts.h", "sim_mapf_ecbs_parts.h", "sim_mapf_tree.h",
+                 "row_board.h"):
         assert '#include "%s"' % part in text and part in build_native.HEADERS
     assert '#include "sim_mapf_ecbs_parts.h"' in narrow
-    for shared in ("ecbs_node", "ecbs_count", "ecbs_wave_sum", "ECBS_MAX_NODES"):      # one copy, in the shared header
+    tree = open(os.path.join(CSRC, "sim_mapf_tree.h")).read()
+    board = open(os.path.join(CSRC, "row_board.h")).read()
+    assert re.search(r"\bwave_all_sum\(", board) and "ecbs_wave_sum" not in parts + text + narrow + tree      # the sum: with the row boards
+    assert "mapf_tree_search(" in text and "mapf_tree_search(" in narrow and "audit_stage2(" in tree      # the walk, once for both forms
+    for shared in ("ecbs_node", "ecbs_count", "ECBS_MAX_NODES"):      # one copy, in the shared header
         assert re.search(r"\b%s\b" % shared, parts), shared
         for body in (text, narrow):
             assert not re.search(r"^(struct|__device__ [^\n]*|template[^\n]*\n__device__ [^\n]*|constexpr int) ?\b%s\b[ ({=]" % shared, body,
                                  re.M), shared
-    assert "audit_stage2(" in text and "asm" not in text and "printf" not in text and "assert(" not in text
+    assert "audit_stage2(" not in text and "asm" not in text and "printf" not in text and "assert(" not in text
     assert "hipDeviceSynchronize" not in text
     assert re.search(r"^size_t magat_sim_mapf_ecbs_wide_workspace_bytes\(int C, int H, int W, int N, int T, int max_nodes, int levels\);",
                      hdr, re.M)
@@ -323,6 +328,20 @@ def test_kernel_compiled_for_the_host_equals_the_restatement(ecbs_wide_check, tm
     """The kernel with its workgroup emulated by threads and barriers, as in test_host_ecbs: it covers the algorithm, the indexing
     and the barriers - not the hardware."""
     k = he.tiled(case(name, *key), cases)
+    (tmp_path / "case.txt").write_text(he._case_text(k))
+    run = subprocess.run([ecbs_wide_check, str(tmp_path / "case.txt")], check=True, capture_output=True, text=True)
+    lines = run.stdout.strip().split("\n")
+    assert lines[0] == "0", name
+    for key_, line_ in zip(KEYS, lines[1:]):
+        got = np.array(line_.split(), dtype=np.int64).reshape(np.asarray(k["want"][key_]).shape)
+        np.testing.assert_array_equal(got, k["want"][key_], err_msg="%s: %s" % (name, key_))
+
+
+@pytest.mark.parametrize("name,key", [("pocket", (1500, 4, 64)), ("r8", (1500, 3, 8))])
+def test_the_forms_agree_where_both_apply(ecbs_wide_check, tmp_path, name, key):
+    """One walk, two forms: the wide kernel on a narrow shape (its entry refuses only above 256) gives the restatement's answer,
+    which is what the narrow kernel is held to (test_host_ecbs)."""
+    k = he.case(name, *key)
     (tmp_path / "case.txt").write_text(he._case_text(k))
     run = subprocess.run([ecbs_wide_check, str(tmp_path / "case.txt")], check=True, capture_output=True, text=True)
     lines = run.stdout.strip().split("\n")
