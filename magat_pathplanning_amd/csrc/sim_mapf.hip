@@ -17,6 +17,7 @@
 
 #include "magat_common.h"
 #include "row_board.h"      // u64, wave_shift, cells_up / cells_down, wave_any, has_bit
+#include "sim_group.h"      // load_free
 #include "sim_mapf_parts.h"   // MAPF_*, board_row, mapf_search, mapf_backtrace
 
 namespace {
@@ -32,13 +33,7 @@ __global__ __launch_bounds__(64) void mapf_plan_kernel(const uint8_t* __restrict
   const int cs = blockIdx.x, lane = threadIdx.x;
   u64* boards = workspace + (long long)cs * T * MAPF_BOARDS * MAPF_SIDE;
   for (int i = lane; i < T * MAPF_BOARDS * MAPF_SIDE; i += 64) boards[i] = 0ull;
-  // free cells: row r of the map read by the lanes over its columns, one ballot per row; lanes >= H and bits >= W stay zero
-  const uint8_t* mp = map + cs * map_stride;
-  u64 free = 0ull;
-  for (int r = 0; r < H; ++r) {
-    const u64 word = __builtin_amdgcn_ballot_w64(lane < W && mp[r * W + (lane < W ? lane : 0)] == 0);
-    if (lane == r) free = word;
-  }
+  const u64 free = load_free(map + cs * map_stride, H, W, lane);
   const long long a0 = (long long)cs * N;
   const int* ord = order ? order + a0 : nullptr;
   int* len = lengths + a0;

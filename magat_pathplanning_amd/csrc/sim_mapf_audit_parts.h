@@ -1,13 +1,16 @@
 // What the two forms of the schedule audit (sim_mapf_audit.hip, sim_mapf_audit_wide.hip) share: the packed keys of a fault, the
-// per-agent checks of stage 1 and the conflict search of stage 2.  The rule is in include/magat_hip.h and DESIGN 4.11, restated
-// cell by cell in tests/audit_restatement.py.  The forms differ in how a map is held (one wave with a word per row, or a
-// workgroup with up to four), so they bring: is_free(r, c) for a cell ON the map, and group_min(key) - the minimum over the
-// workgroup, the same value for every thread, behind a barrier of the whole workgroup.
+// per-agent checks of stage 1, the conflict search of stage 2, and audit_walk, the body of both kernels around them.  The rule is
+// in include/magat_hip.h and DESIGN 4.11, restated cell by cell in tests/audit_restatement.py.  The forms differ in how a map is
+// held (one wave with a word per row, or a workgroup with up to four), so the stages take: is_free(r, c) for a cell ON the map,
+// and group_min(key) - the minimum over the workgroup, the same value for every thread, behind a barrier of the whole workgroup
+// (sim_group.h; the tree walk of sim_mapf_tree.h runs stage 2 on its own form).
 // Every store is a per-lane (vector) store or an atomic from plain C++.
 #pragma once
 #include <cstdint>
 
 #include "magat_common.h"
+#include "sim_entry.h"      // sim_entry_check
+#include "sim_group.h"      // u64; the groups
 
 constexpr int AUDIT_MAX_N = 4096;             // agents per case: an agent index takes 12 bits of a key
 constexpr int AUDIT_NONE = 0x7fffffff;        // no fault; no owner of a cell
@@ -110,4 +113,82 @@ __device__ __forceinline__ void audit_write(int cs, int* __restrict__ status, in
   fault[4 * cs] = kind, fault[4 * cs + 1] = t, fault[4 * cs + 2] = a, fault[4 * cs + 3] = b;
   flowtime[cs] = st == 0 ? flow : -1;
   makespan[cs] = st == 0 ? longest : -1;
+}
+
+// ---- the walk: one case, from the free rows to the final write -----------------------------------------------------------------------
+// One workgroup per case runs audit_walk.  The kernel hands in a form, which brings what differs between the two: the group
+// (sim_group.h), flood(sr, sc, gr, gc) - the steps between two free cells, or -1, the same for every thread - and the two cell-owner
+// grids own0, own1 where the form keeps them (LDS, or the workspace).  Every branch around a barrier or a group_* call is uniform.
+struct audit_case {
+  const uint8_t* map;
+  int H, W;
+  const uint8_t* solved;      // of the batch, or null
+  const int *rows, *len, *st, *gl;
+  int* at;                    // the cell of every agent at two steps, 2 N ints
+  u64* free_rows;             // LDS, for publish_free
+  int N, T;
+};
+struct audit_out {
+  int *status, *fault, *dist, *flow_bound, *span_bound, *flowtime, *makespan;
+};
+
+template <class Form>
+__device__ __forceinline__ void audit_walk(Form& f, const audit_case& k, const audit_out& out, int cs) {
+  const int tid = f.tid, nt = f.nt, N = k.N, T = k.T, H = k.H, W = k.W;
+  const int *st = k.st, *gl = k.gl, *len = k.len;
+  f.load_free(k.map, H, W);
+  f.publish_free(k.free_rows);
+  for (int i = tid; i < H * W; i += nt) f.own0[i] = f.own1[i] = AUDIT_NONE;
+  __syncthreads();
+  const auto is_free = [&](int r, int c) { return f.is_free(r, c); };
+  // the bounds: they depend on map, start and goal alone
+  int bound = 0, longest = 0;
+  bool apart = false;
+  for (int a = 0; a < N; ++a) {
+    const int sr = __builtin_amdgcn_readfirstlane(st[2 * a]), sc = __builtin_amdgcn_readfirstlane(st[2 * a + 1]);
+    const int gr = __builtin_amdgcn_readfirstlane(gl[2 * a]), gc = __builtin_amdgcn_readfirstlane(gl[2 * a + 1]);
+    const bool s_in = sr >= 0 && sr < H && sc >= 0 && sc < W, g_in = gr >= 0 && gr < H && gc >= 0 && gc < W;
+    int d = -1;
+    if (s_in && g_in && is_free(sr, sc) && is_free(gr, gc)) d = f.flood(sr, sc, gr, gc);
+    if (tid == 0) out.dist[(long long)cs * N + a] = d;
+    apart |= d < 0;
+    bound += d;
+    longest = d > longest ? d : longest;
+  }
+  if (tid == 0) {
+    out.flow_bound[cs] = apart ? -1 : bound;
+    out.span_bound[cs] = apart ? -1 : longest;
+  }
+  if (k.solved && k.solved[cs] == 0) {
+    if (tid == 0) audit_write(cs, out.status, out.fault, out.flowtime, out.makespan, 1, 0, -1, -1, -1, 0, 0);
+    return;
+  }
+  const int key1 = f.group_min(audit_stage1(k.rows, len, st, gl, N, T, H, W, tid, nt, is_free));
+  if (key1 != AUDIT_NONE) {
+    if (tid == 0) {
+      audit_write(cs, out.status, out.fault, out.flowtime, out.makespan, 2, 0, -1, -1, -1, 0, 0);
+      audit_fault1(key1, len, out.fault + 4 * cs);
+    }
+    return;
+  }
+  int t2 = -1;
+  const int key2 = audit_stage2(k.rows, N, T, W, f.own0, f.own1, k.at, k.at + N, tid, nt, [&](int key) { return f.group_min(key); }, &t2);
+  int flow = 0, last = 0;
+  for (int base = 0; base < N; base += nt) {
+    const int b = base + tid, lb = b < N ? len[b] : 1;
+    flow += lb - 1;
+    last = lb - 1 > last ? lb - 1 : last;
+  }
+  f.group_sum_max(flow, last);
+  if (tid == 0) {
+    if (key2 == AUDIT_NONE) audit_write(cs, out.status, out.fault, out.flowtime, out.makespan, 0, 0, -1, -1, -1, flow, last);
+    else audit_write(cs, out.status, out.fault, out.flowtime, out.makespan, 2, 7 + (key2 & 1), t2, key2 >> 13, key2 >> 1 & 4095, 0, 0);
+  }
+}
+
+// what the two entries refuse alike, in the ladder's order (sim_entry.h); an entry brings its map side, horizon and bytes
+inline int audit_entry_check(std::initializer_list<const void*> pointers, int H, int W, int C, int N, int T, int side, int max_t,
+                             const void* workspace, size_t workspace_bytes, size_t need) {
+  return sim_entry_check(pointers, H > 0 && W > 0 && C > 0 && N > 0 && T > 0, H <= side && W <= side && T <= max_t && N <= AUDIT_MAX_N,
+                         workspace, workspace_bytes, need);
 }

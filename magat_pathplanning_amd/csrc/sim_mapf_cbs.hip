@@ -80,7 +80,7 @@ __global__ __launch_bounds__(64) void mapf_cbs_kernel(const uint8_t* __restrict_
                               reinterpret_cast<cbs_node*>(boards + lay.nodes), reinterpret_cast<int*>(boards + lay.rlen), nullptr, nullptr,
                               reinterpret_cast<int*>(boards + lay.at), cells, N, T, H, W, max_nodes, 0};
   for (int i = lane; i < T * MAPF_BOARDS * MAPF_SIDE; i += 64) boards[i] = 0ull;
-  cbs_form f{{lane, boards, 0ull}, R, reinterpret_cast<int*>(R), reinterpret_cast<int*>(R) + MAPF_SIDE * MAPF_SIDE, T, W, 0};
+  cbs_form f{{{lane}, boards}, R, reinterpret_cast<int*>(R), reinterpret_cast<int*>(R) + MAPF_SIDE * MAPF_SIDE, T, W, 0};
   f.load_free(map + cs * map_stride, H, W);
   mapf_tree_search(f, k, tree_out{makespan, solved, status, flowtime, lower_bound, nodes_out, expanded_out, horizon_hit}, cs);
 }

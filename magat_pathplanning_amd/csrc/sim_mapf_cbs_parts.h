@@ -1,12 +1,14 @@
 // What the tree walk (sim_mapf_tree.h) takes from below: the constraint bits of an agent's chain and a node's path laid into a row
 // of the schedule, for any form - and cbs_wave, what the two one-wavefront forms (sim_mapf_cbs.hip, sim_mapf_ecbs.hip: lane = map row,
-// one 64-bit word per row) bring alike: the butterfly reductions, the free board, the screening and a bit of the hard boards.
+// one 64-bit word per row) bring alike: the one-wave group (sim_group.h: the reductions, the free board), the screening and a bit of
+// the hard boards.
 // Every store is a per-lane (vector) store from plain C++.
 #pragma once
 #include <cstdint>
 
 #include "magat_common.h"
-#include "row_board.h"           // wave_any, wave_all_min / _max / _sum / _min3
+#include "row_board.h"           // wave_any
+#include "sim_group.h"           // wave_group
 #include "sim_mapf_parts.h"      // MAPF_BOARDS, MAPF_SIDE
 
 // one constraint bit, by the lane of its row
@@ -42,34 +44,8 @@ __device__ __forceinline__ void cbs_place(int* p, const uint16_t* src, int len, 
   }
 }
 
-struct cbs_wave {
-  static constexpr int nt = 64;
-  int tid;
+struct cbs_wave : wave_group {
   u64* hard;      // [t][V, A_up, A_left, A_down, A_right][row]: the constraints of the agent that is searched
-  u64 free;
-  __device__ __forceinline__ int group_min(int v) {
-    v = wave_all_min(v);
-    __syncthreads();
-    return v;
-  }
-  __device__ __forceinline__ int group_max(int v) {
-    v = wave_all_max(v);
-    __syncthreads();
-    return v;
-  }
-  __device__ __forceinline__ int group_sum(int v) {
-    v = wave_all_sum(v);
-    __syncthreads();
-    return v;
-  }
-  __device__ __forceinline__ void group_min3(int& a, int& b, int& c) { wave_all_min3(a, b, c); }
-  __device__ __forceinline__ void load_free(const uint8_t* mp, int H, int W) {
-    free = 0ull;
-    for (int r = 0; r < H; ++r) {
-      const u64 word = __builtin_amdgcn_ballot_w64(tid < W && mp[r * W + (tid < W ? tid : 0)] == 0);
-      if (tid == r) free = word;
-    }
-  }
   __device__ __forceinline__ bool screen(const int* st, const int* gl, int N, int H, int W) const {
     u64 starts = 0ull, goals = 0ull;
     bool ok = true;

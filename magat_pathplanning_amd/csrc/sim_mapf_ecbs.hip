@@ -243,7 +243,7 @@ __global__ __launch_bounds__(64) void mapf_ecbs_kernel(const uint8_t* __restrict
                                reinterpret_cast<ecbs_node*>(hard + lay.nodes), ints, ints + N, ints + 2 * N, ints + 3 * N, cells,
                                N, T, H, W, max_nodes, w_milli};
   for (long long i = lane; i < lay.planes; i += 64) hard[i] = 0ull;      // both sets of boards
-  ecbs_form<K> f{{lane, hard, 0ull}, hard + lay.soft, hard + lay.planes, own, own + ECBS_GRID, T, W, w_milli, 0, 0};
+  ecbs_form<K> f{{{lane}, hard}, hard + lay.soft, hard + lay.planes, own, own + ECBS_GRID, T, W, w_milli, 0, 0};
   f.load_free(map + cs * map_stride, H, W);
   mapf_tree_search(f, k, tree_out{makespan, solved, status, flowtime, lower_bound, nodes_out, expanded_out, horizon_hit}, cs);
 }

@@ -26,6 +26,7 @@
 
 #include "magat_common.h"
 #include "row_board.h"
+#include "sim_group.h"                  // wide_group: the walk's reductions, the free board
 #include "sim_mapf_audit_parts.h"      // AUDIT_MAX_N, audit_stage2 - the walk's conflict scan
 #include "sim_mapf_cbs_parts.h"        // (the walk's cbs_mark_chain, cbs_place)
 #include "sim_mapf_ecbs_parts.h"       // ECBS_*, ecbs_node
@@ -284,52 +285,17 @@ __device__ void wecbs_backtrace(const wecbs_set<NW>& hard, const wecbs_set<NW>& 
 }
 
 template <int NW, int K>
-struct wecbs_form {
+struct wecbs_form : wide_group<NW> {
   static constexpr bool FOCAL = true, BORROWS_GRIDS = false;
-  int tid, nt;      // nt = rows
-  wide_seat s;
   wecbs_set<NW> hard, soft;
   u64* planes;
   long long plane_words;
   int *own0, *own1;
-  wboard<NW> free;
   int T, W, w_milli, ka, ta;
-  __device__ __forceinline__ int group_min(int v) {
-    wide_post(s, 0, wave_all_min(v));
-    return wide_min(s, wide_sync(s), 0);
-  }
-  __device__ __forceinline__ int group_max(int v) {
-    wide_post(s, 0, wave_all_max(v));
-    return wide_max(s, wide_sync(s), 0);
-  }
-  __device__ __forceinline__ int group_sum(int v) {
-    wide_post(s, 0, wave_all_sum(v));
-    return wide_sum(s, wide_sync(s), 0);
-  }
-  __device__ __forceinline__ void group_min3(int& a, int& b, int& c) {      // the butterfly, then the waves' three ints through the mail
-    wave_all_min3(a, b, c);
-    wide_post(s, 0, a);
-    wide_post(s, 1, b);
-    wide_post(s, 2, c);
-    const int p = wide_sync(s);
-    for (int w = 0; w < s.nwaves; ++w) {
-      const int oa = s.mail->num[p][w][0], ob = s.mail->num[p][w][1], oc = s.mail->num[p][w][2];
-      if (oa < a || (oa == a && (ob < b || (ob == b && oc < c)))) a = oa, b = ob, c = oc;
-    }
-  }
-  // free cells: the rows of this wave, each read by the lanes over its columns, one ballot per word; rows >= H and bits >= W
-  // stay zero
-  __device__ __forceinline__ void load_free(const uint8_t* mp, int H, int W) {
-    free = wb_zero<NW>();
-    for (int r = 64 * s.wave; r < H && r < 64 * s.wave + 64; ++r) {
-#pragma unroll
-      for (int k = 0; k < NW; ++k) {
-        const int col = 64 * k + s.lane;
-        const u64 word = __builtin_amdgcn_ballot_w64(col < W && mp[r * W + (col < W ? col : 0)] == 0);
-        if (tid == r) free.w[k] = word;
-      }
-    }
-  }
+  using wide_group<NW>::tid;
+  using wide_group<NW>::nt;
+  using wide_group<NW>::s;
+  using wide_group<NW>::free;
   __device__ __forceinline__ bool screen(const int* st, const int* gl, int N, int H, int W) {      // one round per agent
     wboard<NW> starts = wb_zero<NW>(), goals = wb_zero<NW>();
     bool ok = true;
@@ -391,8 +357,8 @@ __global__ __launch_bounds__(WIDE_SIDE) void wmapf_ecbs_kernel(const uint8_t* __
                                reinterpret_cast<ecbs_node*>(mine + lay.nodes), ints, ints + N, ints + 2 * N, ints + 3 * N, cells,
                                N, T, H, W, max_nodes, w_milli};
   for (long long i = tid; i < lay.planes; i += nt) mine[i] = 0ull;      // both sets of boards
-  wecbs_form<NW, K> f{tid, nt, wide_seat{mails, tid & 63, tid >> 6, nt >> 6, 0}, wecbs_set<NW>{mine, nt}, wecbs_set<NW>{mine + lay.soft, nt},
-                      mine + lay.planes, (long long)T * nt * NW, own, own + H * W, wb_zero<NW>(), T, W, w_milli, 0, 0};
+  wecbs_form<NW, K> f{wide_group_of<NW>(mails, tid, nt), wecbs_set<NW>{mine, nt}, wecbs_set<NW>{mine + lay.soft, nt},
+                      mine + lay.planes, (long long)T * nt * NW, own, own + H * W, T, W, w_milli, 0, 0};
   f.load_free(map + cs * map_stride, H, W);
   mapf_tree_search(f, k, tree_out{makespan, solved, status, flowtime, lower_bound, nodes_out, expanded_out, horizon_hit}, cs);
 }

@@ -5,7 +5,8 @@
 // hands in a form, which brings what differs between the three:
 //   tid, nt, own0, own1     the workgroup (nt = 64: one wavefront) and the two cell-owner grids of the conflict scan, where the form
 //                           keeps them: dynamic LDS (CBS), static LDS (ECBS), the workspace (wide ECBS)
-//   group_min / _max / _sum a reduction over the workgroup BEHIND A BARRIER of the whole workgroup, the same value in every thread;
+//   group_min / _max / _sum (from the form's group, sim_group.h: wave_group or wide_group<NW>) a reduction over the workgroup
+//                           BEHIND A BARRIER of the whole workgroup, the same value in every thread;
 //   group_min3              the lexicographically smallest int triple.  One wave: the butterfly.  Wide: the LDS mail - every thread
 //                           goes through the same sequence of wide_sync, so the walk calls them under uniform conditions only
 //   screen                  every start and goal on a free cell of its own, before any cell indexes anything

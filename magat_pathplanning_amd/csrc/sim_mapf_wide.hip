@@ -16,6 +16,8 @@
 
 #include "magat_common.h"
 #include "row_board.h"
+#include "sim_entry.h"      // wide_launch
+#include "sim_group.h"                // load_free
 #include "sim_mapf_wide_parts.h"      // WMAPF_*, wide_rows / wide_words, wide_layers, wmapf_search, wmapf_backtrace
 
 namespace {
@@ -34,18 +36,7 @@ __global__ __launch_bounds__(WIDE_SIDE) void wmapf_plan_kernel(const uint8_t* __
   const wide_layers<NW> L{workspace + (long long)cs * T * layer_words, nt};
   for (int t = 0; t < T; ++t)      // the reservation boards; an R layer is written before it is read
     for (int i = tid; i < 5 * nt * NW; i += nt) L.base[t * layer_words + i] = 0ull;
-  // free cells: the rows of this wave, each read by the lanes over its columns, one ballot per word; rows >= H and bits >= W
-  // stay zero
-  const uint8_t* mp = map + cs * map_stride;
-  wboard<NW> free = wb_zero<NW>();
-  for (int r = 64 * s.wave; r < H && r < 64 * s.wave + 64; ++r) {
-#pragma unroll
-    for (int k = 0; k < NW; ++k) {
-      const int col = 64 * k + s.lane;
-      const u64 word = __builtin_amdgcn_ballot_w64(col < W && mp[r * W + (col < W ? col : 0)] == 0);
-      if (tid == r) free.w[k] = word;
-    }
-  }
+  const wboard<NW> free = load_free<NW>(map + cs * map_stride, H, W, s, tid);
   const long long a0 = (long long)cs * N;
   const int* ord = order ? order + a0 : nullptr;
   int* len = lengths + a0;
@@ -140,20 +131,10 @@ extern "C" int magat_sim_mapf_plan_wide(const uint8_t* map, int map_batched, int
   u64* ws = static_cast<u64*>(workspace);
   magat_form_note(MAGAT_FORM_SIM_MAPF);
   const int pid = magat_prof_begin(MAGAT_TAG_SIM_MAPF, st);
-  switch (wide_words(W)) {
-    case 1:
-      hipLaunchKernelGGL(wmapf_plan_kernel<1>, grid, block, 0, st, map, map_stride, H, W, start, goal, order, paths, lengths, makespan,
-                         solved, failed_agent, ws, N, T);
-      break;
-    case 2:
-      hipLaunchKernelGGL(wmapf_plan_kernel<2>, grid, block, 0, st, map, map_stride, H, W, start, goal, order, paths, lengths, makespan,
-                         solved, failed_agent, ws, N, T);
-      break;
-    default:
-      hipLaunchKernelGGL(wmapf_plan_kernel<4>, grid, block, 0, st, map, map_stride, H, W, start, goal, order, paths, lengths, makespan,
-                         solved, failed_agent, ws, N, T);
-      break;
-  }
+  wide_launch(wide_words(W), [&](auto nw) {
+    hipLaunchKernelGGL(wmapf_plan_kernel<decltype(nw)::value>, grid, block, 0, st, map, map_stride, H, W, start, goal, order, paths, lengths,
+                       makespan, solved, failed_agent, ws, N, T);
+  });
   magat_prof_end(pid, st);
   return magat_check_launch();
 }

@@ -172,6 +172,56 @@ def hand_case():
     return dict(map=m, start=start, goal=goal, T=T, before=before, after=after)
 
 
+NEWCOMER_FREE_PATH = [(1, 0), (1, 1), (1, 2), (1, 3), (1, 4)]
+
+
+def newcomer_case(H, N, s, p, q, T=12):
+    """Two agents join the neighbourhood in ONE step of the seed's free path.  H x 20, walled but for row 1 columns 0 .. 4 (a
+    corridor), the pockets (0, 1), (0, 2) and (2, 2), and the rows 4 .. H - 1, where the other N - 3 agents stand on their goals
+    (length 1, delay 0).  Agent s waits at (1, 0) until t = 2 and then walks the corridor to (1, 4): delay 2, the seed of iteration
+    0, its free path NEWCOMER_FREE_PATH.  Agent q comes the other way, (1, 3) (1, 2) (1, 1) (0, 1): between t = 1 and 2 it SWAPS
+    with the free path.  Agent p waits in (2, 2) and steps up, (2, 2) (2, 2) (1, 2) (0, 2): at t = 2 it STANDS ON the free path's
+    cell.  Nobody else is in the way at any t.  What comes of it depends on who is re-planned first: behind s and q, p finds a way
+    and the flowtime drops; behind s and p, q is shut in, and with p alone next to s nothing is gained."""
+    m = np.ones((H, 20), dtype=np.uint8)
+    m[1, 0:5] = 0
+    m[0, 1] = m[0, 2] = m[2, 2] = 0
+    m[4:, :] = 0
+    walks = {s: [(1, 0)] * 3 + NEWCOMER_FREE_PATH[1:], q: [(1, 3), (1, 2), (1, 1), (0, 1)], p: [(2, 2), (2, 2), (1, 2), (0, 2)]}
+    assert len(walks) == 3 and N - 3 <= (H - 4) * 20
+    field = iter((r, c) for r in range(4, H) for c in range(20))
+    cells = [walks[a] if a in walks else [next(field)] for a in range(N)]
+    lengths = np.array([len(w) for w in cells], dtype=np.int32)
+    return dict(map=m, T=T, cells=cells, start=np.array([w[0] for w in cells], dtype=np.int32)[None],
+                goal=np.array([w[-1] for w in cells], dtype=np.int32)[None],
+                res=dict(paths=padded(cells, T)[None], lengths=lengths[None], makespan=np.array([lengths.max() - 1], dtype=np.int32),
+                         solved=np.ones(1, dtype=np.uint8)))
+
+
+# arrangement -> (N, the seed, the smaller and the larger index of the two newcomers): in one wavefront; in two wavefronts of one
+# chunk of a workgroup of 128 threads (a map of 65 rows or more); in two chunks of 64 threads; in two chunks of 128 threads
+NEWCOMERS = {"one_wave": (6, 2, 1, 4), "two_waves": (72, 2, 10, 70), "two_chunks64": (70, 2, 3, 66), "two_chunks128": (140, 2, 5, 130)}
+
+
+def newcomer_named(name, H):
+    """"newcomers_<arrangement>_<qp | pq>_k<k>" -> (newcomer_case(...), s, p, q, k); qp: q has the smaller index."""
+    arrangement, order, k = name[len("newcomers_"):].rsplit("_", 2)
+    N, s, lo, hi = NEWCOMERS[arrangement]
+    p, q = (hi, lo) if order == "qp" else (lo, hi)
+    return newcomer_case(H, N, s, p, q), s, p, q, int(k[1:])
+
+
+def newcomer_names(arrangements):
+    return ["newcomers_%s_%s_k%d" % (a, order, k) for a in arrangements for order in ("qp", "pq") for k in (2, 3)]
+
+
+def joiners(free_cells, cells, t):
+    """The agents that stand on the free path's cell at t or swap with it between t - 1 and t, in index order."""
+    at = lambda b, u: cells[b][min(u, len(cells[b]) - 1)]      # noqa: E731
+    return [b for b in range(len(cells)) if at(b, t) == free_cells[t]
+            or (t >= 1 and at(b, t) == free_cells[t - 1] and at(b, t - 1) == free_cells[t])]
+
+
 def padded(cells, T):
     """Paths given as lists of cells -> (N,T,2) int32 padded with the last cell."""
     return np.asarray([p + [p[-1]] * (T - len(p)) for p in cells], dtype=np.int32)

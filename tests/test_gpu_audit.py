@@ -52,6 +52,32 @@ def test_audit_equals_restatement(gpu_device, name):
     assert_equal_results(got, want, ar.KEYS, name)
 
 
+@pytest.mark.parametrize("name", ha.NAMES_64)
+def test_wide_entry_on_the_64_forms_inputs(gpu_device, name):
+    """audit_schedules(..., wide=True) sends a shape inside 64 x 64 to the 64 form, so the wide kernel is reached here through its
+    entry, with a workspace of exactly the size it asks for: every output equals the 64 form's and the restatement's."""
+    from magat_pathplanning_amd import _native as nat
+    from magat_pathplanning_amd import audit_schedules
+    k = ha.case(name)
+    md, res = given(name, gpu_device)
+    narrow = audit_schedules(md, res)
+    C, N, T, _ = res["paths"].shape
+    H, W = md.shape[-2:]
+    lib = nat.lib()
+    out = {key: torch.full_like(narrow[key], -7) for key in ar.KEYS}
+    ws = torch.empty(lib.magat_sim_mapf_audit_wide_workspace_bytes(C, H, W, N, T), dtype=torch.uint8, device=gpu_device)
+    with torch.cuda.device(gpu_device):
+        rc = lib.magat_sim_mapf_audit_wide(nat.ptr(md), int(md.dim() == 3), H, W, nat.ptr(res.get("solved")), nat.ptr(res["paths"]),
+                                           nat.ptr(res["lengths"]), nat.ptr(res["start"]), nat.ptr(res["goal"]), nat.ptr(out["status"]),
+                                           nat.ptr(out["fault"]), nat.ptr(out["dist"]), nat.ptr(out["flowtime_bound"]),
+                                           nat.ptr(out["makespan_bound"]), nat.ptr(out["flowtime"]), nat.ptr(out["makespan"]), nat.ptr(ws),
+                                           ws.numel(), C, N, T, nat.current_stream(gpu_device))
+    nat.check(rc, "magat_sim_mapf_audit_wide")
+    for key in ar.KEYS:
+        assert torch.equal(out[key], narrow[key]), (name, key)
+    assert_equal_results(out, k["want"], ar.KEYS, name)
+
+
 def test_hand_cases_planned_on_the_device(gpu_device):
     """The five hand cases as one (5,5,7) batch with a map per case, planned on the device: the unsolved ones come back skipped
     and still carry dist."""

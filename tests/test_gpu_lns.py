@@ -87,7 +87,10 @@ def case(name):
         m, _, _, res, want = lr.solved_and_improved(name)
         return m, res, lr.BATCHES[name]["iterations"], lr.BATCHES[name]["k"], want
     it, k = 4, 3
-    if name == "edges":
+    if name.startswith("newcomers_"):           # two newcomers in one step of the seed's free path (lr.newcomer_case), 8 x 20
+        c, _, _, _, k = lr.newcomer_named(name, 8)
+        m, res, it = c["map"], c["res"], 1
+    elif name == "edges":
         m, res = edge_inputs()
         it, k = 2, 2
     elif name == "hand_k1":
@@ -137,8 +140,11 @@ def run(name, device):
     return got, want
 
 
+NEWCOMER_NAMES = lr.newcomer_names(("one_wave", "two_chunks64"))
+
+
 @pytest.mark.parametrize("name", ["10x10", "12x12", "edges", "hand_k1", "hand_k8_no_iterations", "hand_k8", "start_is_goal",
-                                  "corner64", "w33", "crowd70", "serpentine_T256", "c300", "map_per_case"])
+                                  "corner64", "w33", "crowd70", "serpentine_T256", "c300", "map_per_case"] + NEWCOMER_NAMES)
 def test_improve_equals_restatement(gpu_device, name):
     got, want = run(name, gpu_device)
     for key in KEYS:
@@ -164,6 +170,9 @@ def test_improve_equals_restatement(gpu_device, name):
         assert 0 < int((want["status"] == 1).sum()) < 300 and int(want["accepted"].sum()) >= 1
     if name in ("w33", "map_per_case"):
         assert int(want["accepted"].sum()) >= 1
+    if name in NEWCOMER_NAMES:
+        import test_host_lns as th
+        th.check_newcomers(name, 8, want)
 
 
 def test_solve_cases_with_improve_is_solve_cases_then_improve_schedules(gpu_device):

@@ -53,6 +53,40 @@ def test_wide_improve_equals_restatement(gpu_device, name):
     assert_equal_results(got, want, KEYS, name)
 
 
+def narrow_names():
+    import test_gpu_lns as tg
+    return ["10x10", "12x12", "edges", "hand_k1", "hand_k8_no_iterations", "hand_k8", "start_is_goal"] + tg.NEWCOMER_NAMES
+
+
+@pytest.mark.parametrize("name", narrow_names())
+def test_wide_entry_on_the_narrow_inputs(gpu_device, name):
+    """improve_schedules(..., wide=True) sends a shape inside 64 x 64 to the 64 form, so the wide kernel is reached here through its
+    entry, with a workspace of exactly the size it asks for: every output equals the 64 form's and the restatement's."""
+    import test_gpu_lns as tg
+    from magat_pathplanning_amd import _native as nat
+    from magat_pathplanning_amd import improve_schedules
+    m, res, it, k, want = tg.case(name)
+    md = dev(np.asarray(m, dtype=np.uint8), gpu_device)
+    given = {key: dev(res[key], gpu_device) for key in RES_KEYS}
+    narrow = improve_schedules(md, given, iterations=it, neighbourhood=k)
+    solved = given["solved"].to(torch.uint8).contiguous()
+    C, N, T, _ = given["paths"].shape
+    H, W = md.shape[-2:]
+    lib = nat.lib()
+    out = {key: given[key].to(torch.int32).clone() for key in ("paths", "lengths", "makespan")}
+    out.update({key: torch.full((C,), -7, dtype=torch.int32, device=gpu_device) for key in KEYS[3:]})
+    ws = torch.empty(lib.magat_sim_mapf_improve_wide_workspace_bytes(C, H, W, N, T), dtype=torch.uint8, device=gpu_device)
+    with torch.cuda.device(gpu_device):
+        rc = lib.magat_sim_mapf_improve_wide(nat.ptr(md), int(md.dim() == 3), H, W, nat.ptr(solved), nat.ptr(out["paths"]),
+                                             nat.ptr(out["lengths"]), nat.ptr(out["makespan"]), nat.ptr(out["flowtime_before"]),
+                                             nat.ptr(out["flowtime_after"]), nat.ptr(out["accepted"]), nat.ptr(out["status"]), nat.ptr(ws),
+                                             ws.numel(), C, N, T, it, k, nat.current_stream(gpu_device))
+    nat.check(rc, "magat_sim_mapf_improve_wide")
+    for key in KEYS:
+        assert torch.equal(out[key], narrow[key]), (name, key)
+    assert_equal_results(out, want, KEYS, name)
+
+
 def test_inside_the_old_limits_wide_gives_the_bits_of_the_64_form(gpu_device, tag_counts):
     from magat_pathplanning_amd import improve_schedules, solve_cases
     m, s, g = mr.random_batch(11, 16, 20, 20, 10, 0.1)

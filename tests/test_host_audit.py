@@ -407,6 +407,22 @@ def test_audit_entries_are_declared_bound_and_built():
     assert lib.magat_profile_read(tag, ctypes.byref(c), ctypes.byref(ms)) == 0
 
 
+def test_the_audit_body_has_one_home():
+    """audit_walk in sim_mapf_audit_parts.h is the body of both kernels: the stages are called from there alone, and the two kernel
+    files bring a form (the flood, the owner grids) on sim_group.h's workgroup and nothing of the rule."""
+    for name in sorted(os.listdir(CSRC)):
+        text = re.sub(r"//[^\n]*", "", open(os.path.join(CSRC, name)).read())
+        for helper in ("audit_stage1", "audit_walk", "audit_entry_check", "audit_write", "audit_fault1"):
+            defined = len(re.findall(r"\b(?:int|void) %s\(" % helper, text))
+            assert defined == (1 if name == "sim_mapf_audit_parts.h" else 0), (name, helper)
+        calls = len(re.findall(r"\baudit_stage1\(", text))
+        assert calls == (2 if name == "sim_mapf_audit_parts.h" else 0), (name, calls)      # its definition and ONE call
+    for src, group, flood in (("sim_mapf_audit.hip", "wave_group", "audit_flood"), ("sim_mapf_audit_wide.hip", "wide_group<NW>", "waudit_flood")):
+        text = open(os.path.join(CSRC, src)).read()
+        assert text.count("audit_walk(") == 1 and ": " + group in text and len(re.findall(r"\bint %s\(" % flood, text)) == 1, src
+        assert "__syncthreads" not in text and "audit_stage" not in text and "wave_all_" not in text, src
+
+
 def test_audit_workspace_formulas():
     from magat_pathplanning_amd import _native as nat
     lib = nat.lib()
@@ -506,6 +522,11 @@ def audit_check(tmp_path_factory):
 # (every thread rendezvous is a futex here, so the suite runs the small inputs; the others were run by hand - DESIGN 4.11)
 HOST_RUNS = [("hand", "64"), ("corrupted", "64"), ("corner64", "64"), ("other_component", "64"), ("open65", "wide"),
              ("open10x65", "wide"), ("open65x10", "wide"), ("open70x130", "wide")]
+
+
+# the 64 form's host inputs through the WIDE kernel's entry: audit_schedules(..., wide=True) sends a shape inside 64 x 64 to the
+# 64 form, so only here do the two kernels meet on one input - one body (audit_walk), two forms, one answer
+HOST_RUNS += [(name, "wide") for name, form in HOST_RUNS if form == "64"]
 
 
 @pytest.mark.parametrize("name,form", HOST_RUNS)

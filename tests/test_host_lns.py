@@ -99,6 +99,30 @@ def test_unsolved_and_refused_inputs_come_back_as_they_came():
         assert out["makespan"] == 77 and out["accepted"] == 0, what
 
 
+def check_newcomers(name, H, want):
+    """From the restatement alone: p and q join at the same step of the seed's free path, the smaller index first, and what that
+    order does to the schedule (want: the restatement's result on the case, one iteration).  The GPU files call this too."""
+    c, s, p, q, k = lr.newcomer_named(name, H)
+    cells, first, second = c["cells"], min(p, q), max(p, q)
+    assert mr.check_schedule(c["map"], c["start"][0], c["goal"][0], c["res"]["paths"][0], c["res"]["lengths"][0]) is None
+    empty = lr._Boards(H, 20, c["T"])
+    d0 = [len(empty.plan(c["map"] == 0, w[0], w[-1])) for w in cells]
+    delay = [len(w) - d for w, d in zip(cells, d0)]
+    assert delay[s] == 2 == max(delay) and delay.count(2) == 1                      # the seed of iteration 0
+    assert empty.plan(c["map"] == 0, cells[s][0], cells[s][-1]) == lr.NEWCOMER_FREE_PATH
+    others = [[b for b in lr.joiners(lr.NEWCOMER_FREE_PATH, cells, t) if b != s] for t in range(5)]
+    assert others == [[], [], [first, second], [], []]                              # both at t = 2, nobody at any other step
+    assert cells[p][2] == lr.NEWCOMER_FREE_PATH[2] and (cells[q][1], cells[q][2]) == (lr.NEWCOMER_FREE_PATH[2], lr.NEWCOMER_FREE_PATH[1])
+    assert lr.neighbourhood(s, lr.NEWCOMER_FREE_PATH, cells, k) == [s, first, second][:k]
+    L = want["lengths"][0]
+    if q < p:         # s, then q, then p: everybody finds a way
+        assert want["accepted"].tolist() == [1] and (want["flowtime_before"].tolist(), want["flowtime_after"].tolist()) == ([12], [11])
+        assert [int(L[s]), int(L[p]), int(L[q])] == ([6, 4, 4] if k == 2 else [5, 5, 4])
+    else:             # s, then p: nothing gained (k = 2), or q shut in behind them (k = 3)
+        assert want["accepted"].tolist() == [0] and (want["paths"] == c["res"]["paths"]).all()
+    assert want["status"].tolist() == [0]
+
+
 # ---- the host side of the entry ----------------------------------------------------------------------------------------------
 ENTRIES = ("magat_sim_mapf_improve_workspace_bytes", "magat_sim_mapf_improve")
 
@@ -136,6 +160,48 @@ def test_one_copy_of_the_search_helpers():
             assert defined == (1 if name == "sim_mapf_parts.h" else 0), (name, helper)
     for user in ("sim_mapf.hip", "sim_mapf_lns.hip"):
         assert '#include "sim_mapf_parts.h"' in open(os.path.join(csrc, user)).read()
+
+
+def test_the_walk_and_the_group_have_one_home():
+    """One body of the improver for both widths (sim_mapf_lns_walk.h), one workgroup per width (sim_group.h): the two kernel files
+    bring a form and nothing of the rule, and nobody spells a reduction, a free-map load or a path reservation out again."""
+    from magat_pathplanning_amd import build_native
+    csrc = os.path.join(ROOT, "magat_pathplanning_amd", "csrc")
+    assert all(h in build_native.HEADERS for h in ("sim_mapf_lns_walk.h", "sim_group.h", "sim_entry.h"))
+    homes = {"mapf_lns_walk": "sim_mapf_lns_walk.h", "lns_mark": "sim_mapf_lns_walk.h", "lns_count_ge": "sim_mapf_lns_walk.h",
+             "lns_entry_check": "sim_mapf_lns_walk.h", "load_free": "sim_group.h", "group_min": "sim_group.h", "group_max": "sim_group.h",
+             "group_sum": "sim_group.h", "group_or": "sim_group.h", "group_sum_waves": "sim_group.h", "group_min3": "sim_group.h", "group_count": "sim_group.h",
+             "publish_free": "sim_group.h", "group_sum_max": "sim_group.h", "sim_entry_check": "sim_entry.h"}
+    per_width = {"load_free": 4, "group_min": 2, "group_max": 2, "group_sum": 2, "group_or": 2, "group_min3": 2, "group_count": 2,
+                 "group_sum_waves": 2, "group_sum_max": 2, "publish_free": 2}      # load_free: the ballot load of each width and the member that calls it
+    once = {"bad |= la < 1 || la > T": "screening", "while (hi - lo > 1)": "the bisection", "const int fc = lds.fcells[t]": "the scan",
+            "if (done == m && new_sum < old_sum)": "accept / roll back"}
+    free_loads = []
+    seen = {key: [] for key in once}
+    for name in sorted(os.listdir(csrc)):
+        text = open(os.path.join(csrc, name)).read()
+        code = re.sub(r"//[^\n]*", "", text)
+        for helper, home in homes.items():
+            defined = len(re.findall(r"\b(?:int|void|bool|u64|wboard<NW>) %s\(" % helper, code))
+            assert defined == (per_width.get(helper, 1) if name == home else 0), (name, helper, defined)
+        assert text.count("void wide_launch(") == (1 if name == "sim_entry.h" else 0), name
+        free_loads += [name] * len(re.findall(r"ballot_w64\(\w+ < W && mp\[[^\]]*\] == 0\)", text))
+        for key in once:
+            seen[key] += [name] * text.count(key)
+        if name in ("sim_mapf_lns.hip", "sim_mapf_lns_wide.hip"):
+            assert "__builtin_amdgcn_ballot_w64" not in text and "wave_all_" not in text and "wide_post" not in text, name
+    assert free_loads == ["sim_group.h", "sim_group.h"]                # the free-map ballot load: once per width
+    assert all(where == ["sim_mapf_lns_walk.h"] for where in seen.values()), seen
+    for src, form in (("sim_mapf_lns.hip", "wave_group"), ("sim_mapf_lns_wide.hip", "wide_group<NW>")):
+        text = open(os.path.join(csrc, src)).read()
+        assert '#include "sim_mapf_lns_walk.h"' in text and text.count("mapf_lns_walk(") == 1 and ": " + form in text, src
+        assert "for (int it" not in text and "lns_mark" not in text and not re.search(r"\bgroup_(min|max|sum|or|count)", text), src
+    for user in ("sim_mapf_cbs_parts.h", "sim_mapf_ecbs_wide.hip", "sim_mapf.hip", "sim_mapf_wide.hip", "sim_mapf_audit.hip",
+                 "sim_mapf_audit_wide.hip"):
+        assert '#include "sim_group.h"' in open(os.path.join(csrc, user)).read(), user
+    for src in ("sim_mapf_wide.hip", "sim_mapf_lns_wide.hip", "sim_mapf_audit_wide.hip"):
+        text = open(os.path.join(csrc, src)).read()
+        assert text.count("wide_launch(") == 1 and "switch (wide_words" not in text, src
 
 
 def test_improve_argument_checks_answer_before_anything_touches_a_device():
@@ -192,8 +258,10 @@ def test_kernel_compiled_for_the_host_equals_the_restatement(tmp_path):
     exe = str(tmp_path / "lns_check")
     subprocess.run([cxx, "-std=c++17", "-O1", "-w", "-pthread", "-I", os.path.join(ROOT, "tools", "host_wave"), "-x", "c++",
                     os.path.join(ROOT, "tools", "host_wave", "mapf_lns_check.cpp"), "-o", exe], check=True)
-    for name in ("edges", "hand_k8", "corner64"):
+    for name in ("edges", "hand_k8", "corner64") + tuple(tg.NEWCOMER_NAMES):
         m, res, it, k, want = tg.case(name)
+        if name in tg.NEWCOMER_NAMES:
+            check_newcomers(name, 8, want)
         (tmp_path / "case.txt").write_text(_case_text(m, res, it, k))
         run = subprocess.run([exe, str(tmp_path / "case.txt")], check=True, capture_output=True, text=True)
         lines = run.stdout.strip().split("\n")

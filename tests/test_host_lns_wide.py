@@ -125,6 +125,9 @@ def case(name):
         h = hand_at(66, 66, 63, 62)
         m, s, g = h["map"], h["start"][None, 1:], h["goal"][None, 1:]
         res, it, k = mr.plan_batch(m, s, g, None, 8), 3, 4
+    elif name in NEWCOMER_NAMES:        # two newcomers in one step of the seed's free path (lr.newcomer_case), 66 x 20
+        c, _, _, _, k = lr.newcomer_named(name, 66)
+        m, s, g, res, it = c["map"], c["start"], c["goal"], c["res"], 1
     else:
         raise KeyError(name)
     return m, s, g, res, it, k, lr.improve_batch(m, res, it, k)
@@ -133,7 +136,8 @@ def case(name):
 HAND_NAMES = tuple(HANDS)
 EDGE_NAMES = ("edges", "edges_k8", "edges_no_iterations", "one_agent")
 BATCH_NAMES = tuple(CLUSTERS) + ("maps65",)
-ALL_NAMES = HAND_NAMES + ("long256", "serpentine_T1024") + BATCH_NAMES + ("agents70",) + EDGE_NAMES
+NEWCOMER_NAMES = tuple(lr.newcomer_names(("one_wave", "two_waves", "two_chunks128")))
+ALL_NAMES = HAND_NAMES + ("long256", "serpentine_T1024") + BATCH_NAMES + ("agents70",) + EDGE_NAMES + NEWCOMER_NAMES
 
 
 def check_what_the_case_is_there_for(name):
@@ -185,6 +189,9 @@ def check_what_the_case_is_there_for(name):
     elif name == "one_agent":
         assert want["status"].tolist() == [0] and want["accepted"].tolist() == [0] and (want["paths"] == res["paths"]).all()
         assert want["flowtime_before"].tolist() == want["flowtime_after"].tolist() == [2]
+    elif name in NEWCOMER_NAMES:
+        import test_host_lns as th
+        th.check_newcomers(name, 66, want)
 
 
 @pytest.mark.parametrize("name", ALL_NAMES)
@@ -314,12 +321,7 @@ def wide_check(tmp_path_factory):
     return exe
 
 
-@pytest.mark.parametrize("name", HAND_NAMES + ("long256",) + EDGE_NAMES + ("clusters65",))
-def test_wide_kernel_compiled_for_the_host_equals_the_restatement(wide_check, tmp_path, name):
-    """csrc/sim_mapf_lns_wide.hip with its workgroup emulated by threads and barriers - ballot, DPP shift, readfirstlane and
-    shuffle as exchanges inside a wavefront, __syncthreads across the workgroup: 1, 2 and 3 wavefronts, 1, 2 and 4 words.  It
-    covers the algorithm, the indexing and the barriers - not the hardware."""
-    m, _, _, res, it, k, want = case(name)
+def _run_and_compare(wide_check, tmp_path, name, m, res, it, k, want):
     (tmp_path / "case.txt").write_text(_case_text(m, res, it, k))
     run = subprocess.run([wide_check, str(tmp_path / "case.txt")], check=True, capture_output=True, text=True)
     lines = run.stdout.strip().split("\n")
@@ -327,3 +329,27 @@ def test_wide_kernel_compiled_for_the_host_equals_the_restatement(wide_check, tm
     for key, line in zip(KEYS, lines[1:]):
         got = np.array(line.split(), dtype=np.int64).reshape(np.asarray(want[key]).shape)
         np.testing.assert_array_equal(got, want[key], err_msg="%s: %s" % (name, key))
+
+
+def narrow_names():
+    import test_gpu_lns as tg
+    return ["edges", "hand_k1", "hand_k8_no_iterations", "hand_k8", "start_is_goal", "corner64"] + tg.NEWCOMER_NAMES
+
+
+@pytest.mark.parametrize("name", narrow_names())
+def test_wide_kernel_compiled_for_the_host_on_the_narrow_inputs(wide_check, tmp_path, name):
+    """improve_schedules(..., wide=True) sends a shape inside 64 x 64 to the 64 form, so the wide kernel never meets the narrow
+    one's inputs through it; here it does, through its entry: one wavefront, one word, and the results of the restatement - which
+    are what tests/test_host_lns.py asks of the narrow kernel on the same case texts."""
+    import test_gpu_lns as tg
+    m, res, it, k, want = tg.case(name)
+    _run_and_compare(wide_check, tmp_path, name, m, res, it, k, want)
+
+
+@pytest.mark.parametrize("name", HAND_NAMES + ("long256",) + EDGE_NAMES + ("clusters65",) + NEWCOMER_NAMES)
+def test_wide_kernel_compiled_for_the_host_equals_the_restatement(wide_check, tmp_path, name):
+    """csrc/sim_mapf_lns_wide.hip with its workgroup emulated by threads and barriers - ballot, DPP shift, readfirstlane and
+    shuffle as exchanges inside a wavefront, __syncthreads across the workgroup: 1, 2 and 3 wavefronts, 1, 2 and 4 words.  It
+    covers the algorithm, the indexing and the barriers - not the hardware."""
+    m, _, _, res, it, k, want = case(name)
+    _run_and_compare(wide_check, tmp_path, name, m, res, it, k, want)
