@@ -533,6 +533,27 @@ int magat_gso_csr_build(void* S, int s_is_f64, int scrub_nan, int gso_mode, int 
 int magat_gso_csr_build_phase(void* S, int s_is_f64, int scrub_nan, int gso_mode, int edge_rule, int* rowptr, int* colidx,
                               int* cscptr, int* cscsrc, int* cscpos, long long cap, long long* nnz_dev, void* workspace,
                               size_t workspace_bytes, int B, int N, int phase, void* stream);
+/* The same edge structure straight from agent positions (gso_edges.hip; additive behind ABI 9), for the layers that read the GSO
+ * through its edge test only - KeyQuery, GAT_modified, GAT_origin, GAT_Similarity: no (B,N,N) tensor and no eigenvalue, N <= 4096.
+ * pos [B][N][2] int32 (row, col); (i, j), i != j, is an edge when the reference's float64 sqrt(dr^2 + dc^2) < r holds, evaluated
+ * as the integer comparison magat_sim_gso uses (exact); r = radii[b] (device, float64) when radii is given, else comm_radius.
+ * edge_rule 0: no self-loops (|S| > 1e-9 of the simulator's GSO); 1: every (i, i) added (|float(S) + I| > 1e-9).  Outputs in
+ * magat_gso_csr_build's conventions, word for word: rowptr [B*(N+1)] absolute offsets, colidx ascending in j per row, cscptr /
+ * cscsrc / cscpos per in-edge in ascending source row: the source and its CSR position.  The graph is symmetric: cscptr equals
+ * rowptr and cscsrc equals colidx.  For N <= 1024 every array equals what magat_gso_csr_build makes of magat_sim_gso's tensor.
+ * cap, *nnz_dev: that entry's capacity contract (entries at positions >= cap are dropped, rowptr / cscptr stay true, *nnz_dev is
+ * the true total; a batch without an edge is legal).  Two launches, no host synchronisation, no atomics on device memory: the
+ * arrays are the same on every call.  Workspace: magat_gso_edges_workspace_bytes (the bit matrix, N*N/8 bytes per instance, a
+ * quarter of that for its word prefixes, and the row degrees; 0 = N > 4096 or a size <= 0), 256-byte aligned.
+ * Answers before anything is launched: NULL pointers MAGAT_ERR_NULL (radii may be NULL; colidx, cscsrc and cscpos only with
+ * cap == 0), then B, N <= 0, cap < 0, edge_rule outside 0 | 1, or no radii and comm_radius not > 0: MAGAT_ERR_BAD_SHAPE, then
+ * N > 4096: MAGAT_ERR_UNSUPPORTED, then the workspace: MAGAT_ERR_WORKSPACE.  Profiling tag 35 ("gso_edges", one span per call;
+ * 34 is unassigned), form counter 26 - numbered in the library, MAGAT_PROF_TAGS / MAGAT_FORMS below stay what ABI 9 was built
+ * against. */
+size_t magat_gso_edges_workspace_bytes(int B, int N);
+int magat_gso_edges_build(const int32_t* pos, const double* radii /* [B] or NULL */, double comm_radius, int edge_rule /* 0 | 1 */,
+                          int* rowptr, int* colidx, int* cscptr, int* cscsrc, int* cscpos, long long cap, long long* nnz_dev,
+                          void* workspace, size_t workspace_bytes, int B, int N, void* stream);
 /* magat_gat_forward_csr_{f32,bf16} with the CSC view from magat_gso_csr_build (no per-call transpose; workspace:
  * magat_gat_csc_workspace_bytes - the csr_* figure minus the transpose scratch, 3 * nnz ints) */
 size_t magat_gat_csc_workspace_bytes(int B, int N, long long nnz, int G, int F, int K, int P, int mode, int concat, int bf16);

@@ -20,12 +20,12 @@ _MODE_IDS = {"KeyQuery": MODE_KEYQUERY, "GAT_modified": MODE_GAT_MODIFIED, "GAT_
 TAGS = {0: "untagged", 1: "conv_first", 2: "layer1.conv1", 3: "layer1.conv2+ds", 4: "layer2.conv1",
         5: "layer2.conv2+ds", 6: "layer3.conv1", 7: "layer3.conv2+ds", 8: "head(avgpool+fc+linear)",
         9: "compressMLP", 10: "gat_maps_gemm", 11: "gat_graph", 12: "actionsMLP", 13: "head_mean",
-        14: "gat_pack", 15: "gso_prepare", 16: "gat_prepare", 17: "range_guard", 18: "layer1.conv2+layer2 (fused)", 19: "gat_layer (one launch)", 20: "gso_to_csr", 21: "gat_cast", 22: "layer3 (fused, pooled)", 23: "layer1.conv2+layer2+layer3 (fused, pooled)", 24: "conv_wgrad", 25: "gnn_dense", 26: "sim_guided", 27: "sim_expert", 28: "sim_mapf", 29: "sim_mapf_lns", 30: "sim_mapf_audit", 31: "sim_mapf_cbs", 32: "sim_mapf_ecbs", 33: "head_loss"}
+        14: "gat_pack", 15: "gso_prepare", 16: "gat_prepare", 17: "range_guard", 18: "layer1.conv2+layer2 (fused)", 19: "gat_layer (one launch)", 20: "gso_to_csr", 21: "gat_cast", 22: "layer3 (fused, pooled)", 23: "layer1.conv2+layer2+layer3 (fused, pooled)", 24: "conv_wgrad", 25: "gnn_dense", 26: "sim_guided", 27: "sim_expert", 28: "sim_mapf", 29: "sim_mapf_lns", 30: "sim_mapf_audit", 31: "sim_mapf_cbs", 32: "sim_mapf_ecbs", 33: "head_loss", 35: "gso_edges"}
 TAG_ACTIONS = 12
 # magat_form_count ids (include/magat_hip.h MAGAT_FORM_*)
 FORMS = {"head_longk": 0, "head_splitk": 1, "gat_pack": 2, "gat_persist": 3, "gat_hsplit": 4, "chain_persist": 5,
          "head_compress": 6, "guard_one": 7, "csr_fused": 8, "gat_mid": 9, "chain_lat": 10, "head_lat": 11, "guard_lat": 12, "stem_lat": 13, "actions_tail": 14, "gnn_dense": 15, "sim_guided": 16, "sim_expert": 17, "sim_mapf": 18, "sim_mapf_lns": 19, "sim_mapf_audit": 20, "sim_mapf_cbs": 21, "sim_mapf_ecbs": 22,
-         "chain_tile16": 23, "sim_replay": 24, "gat_cos_train": 25}
+         "chain_tile16": 23, "sim_replay": 24, "gat_cos_train": 25, "gso_edges": 26}
 TAG_GNN_DENSE = 25
 TAG_SIM_GUIDED = 26
 TAG_SIM_EXPERT = 27
@@ -35,6 +35,7 @@ TAG_SIM_MAPF_AUDIT = 30
 TAG_SIM_MAPF_CBS = 31
 TAG_SIM_MAPF_ECBS = 32
 TAG_HEAD_LOSS = 33
+TAG_GSO_EDGES = 35          # (34 is unassigned: csrc/magat_common.h)
 GUIDE_LOCAL, GUIDE_GLOBAL, GUIDE_SEMI = 1, 2, 3      # include/magat_hip.h MAGAT_GUIDE_*
 
 _lock = threading.Lock()
@@ -150,6 +151,8 @@ _SIGNATURES = {
     "magat_gso_csr_workspace_bytes": (_Z, [_I, _I]),
     "magat_gso_csr_build": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.c_longlong, _P, _P, _Z, _I, _I, _P]),
     "magat_gso_csr_build_phase": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.c_longlong, _P, _P, _Z, _I, _I, _I, _P]),
+    "magat_gso_edges_workspace_bytes": (_Z, [_I, _I]),
+    "magat_gso_edges_build": (_I, [_P, _P, ctypes.c_double, _I, _P, _P, _P, _P, _P, ctypes.c_longlong, _P, _P, _Z, _I, _I, _P]),
     "magat_gat_forward_csc_f32": (_I, [_P] * 6 + [ctypes.c_longlong, _P, _P, _P, _I, _P, _P, _Z] + [_I] * 8 + [_P]),
     "magat_gat_forward_csc_bf16": (_I, [_P] * 6 + [ctypes.c_longlong, _P, _P, _P, _I, _P, _P, _Z] + [_I] * 8 + [_P]),
     "magat_gat_forward_csc_bf16_f32out": (_I, [_P] * 6 + [ctypes.c_longlong, _P, _P, _P, _I, _P, _P, _Z] + [_I] * 8 + [_P]),

@@ -62,9 +62,22 @@ void magat_form_note(int id);      // which form a launch took (MAGAT_FORM_*; pr
 #define MAGAT_FORM_SIM_REPLAY 24     // magat_sim_replayed_states or its wide form launched (SemiLG from the schedule; tag MAGAT_TAG_SIM_GUIDED)
 #define MAGAT_FORM_GAT_COS_TRAIN 25  // magat_gat_train_forward_cos_f32 launched (GAT_Similarity's training forward; one count per call)
 #define MAGAT_FORMS_TABLE 26
+// (the two *_TABLE counts above are pinned by host tests as well, and so is "tag 34 is refused by magat_profile_read".)  Behind
+// them the edge structure from positions (gso_edges.hip): tag 35 - 34 stays unassigned - and form 26; the library's tables are
+// sized by the *_SIZED counts.
+#define MAGAT_TAG_GSO_EDGES 35      // agent positions -> CSR + CSC edge structure (magat_gso_edges_build; one span per call)
+#define MAGAT_PROF_TAGS_SIZED 36
+#define MAGAT_FORM_GSO_EDGES 26     // magat_gso_edges_build launched its two kernels (one count per call)
+#define MAGAT_FORMS_SIZED 27
 static_assert(MAGAT_PROF_TAGS_ALL >= MAGAT_PROF_TAGS && MAGAT_FORMS_ALL >= MAGAT_FORMS, "internal tag / form tables");
 static_assert(MAGAT_PROF_TAGS_TABLE > MAGAT_TAG_HEAD_LOSS && MAGAT_PROF_TAGS_TABLE >= MAGAT_PROF_TAGS_ALL &&
               MAGAT_FORMS_TABLE > MAGAT_FORM_GAT_COS_TRAIN && MAGAT_FORMS_TABLE >= MAGAT_FORMS_ALL, "internal tag / form tables");
+static_assert(MAGAT_PROF_TAGS_SIZED > MAGAT_TAG_GSO_EDGES && MAGAT_TAG_GSO_EDGES > MAGAT_PROF_TAGS_TABLE &&
+              MAGAT_FORMS_SIZED > MAGAT_FORM_GSO_EDGES && MAGAT_FORM_GSO_EDGES >= MAGAT_FORMS_TABLE, "internal tag / form tables");
+// a tag number the library books spans under (the numbers between the pinned table and the tags behind it are holes)
+static inline bool magat_prof_tag_known(int tag) {
+  return tag >= 0 && (tag < MAGAT_PROF_TAGS_TABLE || tag == MAGAT_TAG_GSO_EDGES);
+}
 
 // the move step with per-instance counters (sim_frontend.hip: sim_move_kernel), launched for the case pool's entries (sim_pool.hip)
 struct magat_sim_pool_slots {

@@ -17,8 +17,8 @@ struct Span {
 bool g_enabled = false;
 std::vector<Span> g_pool;   // created lazily, reused
 size_t g_used = 0;
-double g_total[MAGAT_PROF_TAGS_TABLE];
-long long g_count[MAGAT_PROF_TAGS_TABLE];
+double g_total[MAGAT_PROF_TAGS_SIZED];
+long long g_count[MAGAT_PROF_TAGS_SIZED];
 std::mutex g_mu;
 constexpr size_t kMaxSpans = 1 << 16;
 }  // namespace
@@ -69,7 +69,7 @@ extern "C" int magat_profile_collect(void) {
     float ms = 0.f;
     if (hipEventElapsedTime(&ms, g_pool[i].a, g_pool[i].b) == hipSuccess) {
       const int t = g_pool[i].tag;
-      if (t >= 0 && t < MAGAT_PROF_TAGS_TABLE) {
+      if (magat_prof_tag_known(t)) {
         g_total[t] += ms;
         g_count[t] += 1;
       }
@@ -80,7 +80,7 @@ extern "C" int magat_profile_collect(void) {
 }
 
 extern "C" int magat_profile_read(int tag, long long* count, double* total_ms) {
-  if (tag < 0 || tag >= MAGAT_PROF_TAGS_TABLE || !count || !total_ms) return MAGAT_ERR_BAD_SHAPE;
+  if (!magat_prof_tag_known(tag) || !count || !total_ms) return MAGAT_ERR_BAD_SHAPE;
   std::lock_guard<std::mutex> lk(g_mu);
   *count = g_count[tag];
   *total_ms = g_total[tag];
@@ -89,7 +89,7 @@ extern "C" int magat_profile_read(int tag, long long* count, double* total_ms) {
 
 extern "C" int magat_profile_reset(void) {
   std::lock_guard<std::mutex> lk(g_mu);
-  for (int i = 0; i < MAGAT_PROF_TAGS_TABLE; ++i) {
+  for (int i = 0; i < MAGAT_PROF_TAGS_SIZED; ++i) {
     g_total[i] = 0.0;
     g_count[i] = 0;
   }
@@ -194,15 +194,15 @@ extern "C" int magat_mfma_sustained_f16_ex(double* tflops, double* clock_mhz, do
 // ------------------------------------------------------------------------------------------------------------------------
 // Which FORM of a kernel a launch took (host-side counters, bumped where the launcher decides; tests assert on them next to the
 // per-tag launch counts: the forms below exist only at benchmark sizes and must not be swapped silently).
-namespace { std::atomic<long long> g_forms[MAGAT_FORMS_TABLE]; }      // relaxed counters: no lock on the launch path
+namespace { std::atomic<long long> g_forms[MAGAT_FORMS_SIZED]; }      // relaxed counters: no lock on the launch path
 void magat_form_note(int id) {
-  if (id >= 0 && id < MAGAT_FORMS_TABLE) g_forms[id].fetch_add(1, std::memory_order_relaxed);
+  if (id >= 0 && id < MAGAT_FORMS_SIZED) g_forms[id].fetch_add(1, std::memory_order_relaxed);
 }
 extern "C" long long magat_form_count(int id) {
-  if (id < 0 || id >= MAGAT_FORMS_TABLE) return -1;
+  if (id < 0 || id >= MAGAT_FORMS_SIZED) return -1;
   return g_forms[id].load(std::memory_order_relaxed);
 }
 extern "C" int magat_form_reset(void) {
-  for (int i = 0; i < MAGAT_FORMS_TABLE; ++i) g_forms[i].store(0, std::memory_order_relaxed);
+  for (int i = 0; i < MAGAT_FORMS_SIZED; ++i) g_forms[i].store(0, std::memory_order_relaxed);
   return MAGAT_OK;
 }

@@ -155,14 +155,17 @@ class CsrStructure:
     def supported(B, N):
         return nat.lib().magat_gso_csr_workspace_bytes(B, N) > 0 and B * N * N < CsrStructure._CAP_LIMIT
 
+    @staticmethod
+    def _workspace_bytes(B, N):
+        return nat.lib().magat_gso_csr_workspace_bytes(B, N)
+
     def _alloc(self, B, N, cap, dev):
-        lib = nat.lib()
         if self.rowptr is None or self.rowptr.numel() != B * (N + 1) or self.rowptr.device != dev:
             self.rowptr = torch.empty(B * (N + 1), dtype=torch.int32, device=dev)
             self.cscptr = torch.empty(B * (N + 1), dtype=torch.int32, device=dev)
             self.nnz_dev = torch.zeros(1, dtype=torch.int64, device=dev)
             self.nnz_host = torch.zeros(1, dtype=torch.int64).pin_memory()
-            self.ws = torch.empty(lib.magat_gso_csr_workspace_bytes(B, N), dtype=torch.uint8, device=dev)
+            self.ws = torch.empty(self._workspace_bytes(B, N), dtype=torch.uint8, device=dev)
             self.cap = 0
         if self.cap < cap or self.colidx is None or self.colidx.device != dev:
             self.colidx = torch.empty(cap, dtype=torch.int32, device=dev)
@@ -233,8 +236,7 @@ class CsrStructure:
             self.nnz = int(self.nnz_host[0])
             if self.nnz <= self.cap:
                 break
-            S3, rule, scrub, gmode = self.args
-            self.build(S3, rule, scrub, gmode, min_cap=self.nnz + self.nnz // 4)
+            self.build(*self.args, min_cap=self.nnz + self.nnz // 4)
         else:
             raise nat.MagatNativeError("CSR structure build did not converge (nnz %d, cap %d)" % (self.nnz, self.cap))
         torch.cuda.current_stream(dev).wait_event(self.event)
@@ -373,6 +375,29 @@ def gat_forward_rows(X, S, layer, out=None, want_attention=False, csr=None):
             nat.ptr(out), ldy, nat.ptr(aij), nat.ptr(sc.workspace), sc.workspace.numel(),
             B, N, G, F, K, P, mode, concat, None, stream), "magat_gat_forward_planned_f32")
     return out, aij
+
+
+def gat_forward_rows_structure(X, structure, layer, out=None):
+    """gat_forward_rows' CSR route on an edge structure that exists already - edges.EdgeStructure, made from agent positions
+    under layer.edge_rule: the rowptr / colidx / column-view arrays go to magat_gat_forward_csc_* as they are.  No GSO tensor,
+    no dense_gso_to_csr, no read-back beyond the structure's own edge count.  X (B,N,G) float32 | bfloat16 device rows.
+    Returns out (B*N, ld)."""
+    _require_device(X)
+    B, N, G = X.shape
+    if getattr(layer, "_similarity", False):
+        layer._check_forward(B, N)
+        if X.dtype == torch.bfloat16:
+            raise NotImplementedError("GAT_Similarity is built with float32 storage only (got bfloat16 rows)")
+    if structure.rowptr is None or structure.rowptr.numel() != B * (N + 1):
+        raise ValueError("the edge structure is not one of %d instances x %d agents" % (B, N))
+    X = X.contiguous()
+    if X.data_ptr() % 16:
+        X = X.clone()
+    if X.dtype not in (torch.float32, torch.bfloat16):
+        X = X.float()
+    nnz = structure.ready(X.device)
+    csc = (structure.cscptr, structure.csc[0], structure.csc[1])
+    return gat_forward_rows_csr(X, structure.rowptr, structure.colidx, nnz, layer, out=out, csc=csc)[0]
 
 
 def pack_torch(weight, weight_bias, mixer, taps, mode_name):

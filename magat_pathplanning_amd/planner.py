@@ -35,8 +35,10 @@ import torch.nn as nn
 
 from . import _native as nat
 from . import encoder as enc
+from .edges import GraphEdges
 from .graphml import (_MODES, _flat_bias, _gso3, CsrStructure, dense_route, GraphFilterBatchAttentional,
-                      GraphFilterBatchAttentional_Origin, GraphFilterBatchSimilarityAttentional, gat_forward_rows)
+                      GraphFilterBatchAttentional_Origin, GraphFilterBatchSimilarityAttentional, gat_forward_rows,
+                      gat_forward_rows_structure)
 from .resnet import ResNet, ResNetSlim
 
 # config.bottleneckMode -> what the reference file of that name feeds the action MLP (the GAT files ..._GAT_bottleneck*.py
@@ -237,6 +239,7 @@ class _PlannerBase(nn.Module):
         st = self.__dict__.copy()
         st["_rt"] = None
         st["S"] = None
+        st.pop("_edges", None)           # (DecentralPlannerGATNet: the GraphEdges of addGSO(edges) goes with S)
         st["_flat"] = None
         st["_dicts"] = st["_seen"] = None
         return st
@@ -668,7 +671,11 @@ class DecentralPlannerGATNet(_PlannerBase):
         self.apply(weights_init)
 
     def addGSO(self, S):
-        """…bottleneck.py:262-278: aliases the caller's tensor and scrubs it in place."""
+        """…bottleneck.py:262-278: aliases the caller's tensor and scrubs it in place.  S may also be a GraphEdges
+        (simulator.batched_edges, BatchedEpisode.edges, EpisodePool.edges): the graph as positions and radii, see _add_edges."""
+        if isinstance(S, GraphEdges):
+            return self._add_edges(S)
+        self._edges = None
         assert len(S.shape) == 3
         scrub = self.skip in ("only", "legacy")        # only these reference files zero NaNs
         gso_mode = _GSO_MODES.get(self.config.GSO_mode, 0)
@@ -689,6 +696,31 @@ class DecentralPlannerGATNet(_PlannerBase):
             self.S = S.unsqueeze(1)
             return
         self.S = _gso_prepare_host(S, scrub, gso_mode, self.config.device)
+
+    _edges = None          # the GraphEdges of the last addGSO(edges) while the forward takes the CSR kernels on its structure
+
+    def _wants_attention(self):
+        return self.GFL[0].return_attention or bool(getattr(self.config, "return_attentionGSO", False))
+
+    def _add_edges(self, edges):
+        """addGSO(edges): the layer reads the GSO through its edge test only, so the edge structure made from the positions
+        (csrc/gso_edges.hip) is all the CSR kernels need - eval / no_grad with bf16 storage or a graph beyond the LDS-resident
+        kernels, up to 4096 agents: no (B,N,N) tensor, no dense_gso_to_csr, no read-back but the structure's own edge count.
+        self.S is then the GraphEdges itself.  Where the layer takes the LDS-resident kernels, in training mode, with
+        return_attention, or under GSO_mode 'full_GSO', the 0 / 1 adjacency edges.dense() goes through the tensor path above
+        (those routes keep their limits).  The scrub and 'dist_GSO_one' have nothing to do on a 0 / 1 graph."""
+        layer = self.GFL[0]
+        csr_route = layer.storage_dtype == torch.bfloat16 or not dense_route(edges.N, layer)
+        if (self.training or not csr_route or self._wants_attention() or _GSO_MODES.get(self.config.GSO_mode, 0) == 2):
+            return self.addGSO(edges.dense())
+        self._rt.csr.key = None
+        self._edges = self.S = edges
+        edges.structure(layer.edge_rule)       # the build starts here, on the side stream: under the per-agent CNN
+
+    def _head_input(self, x, B, N):
+        if self._edges is not None:            # autograd was switched on behind addGSO(edges): the tensor path
+            self.addGSO(self._edges.dense())
+        return super()._head_input(x, B, N)
 
     def returnAttentionGSO(self):
         return self.GFL[0].returnAttentionGSO()
@@ -803,6 +835,8 @@ class DecentralPlannerGATNet(_PlannerBase):
         if not x.is_cuda:
             raise nat.MagatNativeError("inference runs on the HIP path only; config.device=%r is not a GPU "
                                        "(no CPU fallback)" % (self.config.device,))
+        if self._edges is not None:
+            return self._forward_edges(x, B, N)
         lib = nat.lib()
         dev = x.device
         M = B * N
@@ -879,6 +913,52 @@ class DecentralPlannerGATNet(_PlannerBase):
         return out
 
 
+    def _forward_edges(self, x, B, N):
+        """_forward_general with the graph layer on the edge structure of addGSO(edges): the encoder, the layer's CSR kernels
+        with the column view the structure brings (magat_gat_forward_csc_*), the action head."""
+        edges = self._edges
+        if edges.B != B or edges.N != N:
+            raise ValueError("%s: addGSO(edges) was given the graph of %d instances x %d agents, forward a batch of %d x %d"
+                             % (type(self).__name__, edges.B, edges.N, B, N))
+        if self._wants_attention():            # switched on behind addGSO(edges): the tensor path materialises it
+            self.addGSO(edges.dense())
+            return self._forward_hip(x, B, N)
+        dev = x.device
+        M = B * N
+        rt = self._refresh(dev)
+        rt.plan = None
+        x = x.contiguous().float()
+        G = self.numFeatures2Share
+        with torch.cuda.device(dev):
+            stream = nat.current_stream(dev)
+            feat, comp = self._run_encoder(rt, x, M, dev, stream)
+            layer = self.GFL[0]
+            structure = edges.structure(layer.edge_rule)
+            gat = self._buf("gat", (M, self.gat_width), dev)
+            gat_rows = gat
+            if layer.storage_dtype == torch.bfloat16:
+                # bf16 storage: _forward_general's choices where the structure brings its column view
+                comp16 = getattr(rt, "comp16", None)
+                if comp16 is None or comp16.shape[0] != M:
+                    comp16 = self._buf("comp16", (M, G), dev, torch.bfloat16)
+                    nat.check(nat.lib().magat_cast_rows(nat.ptr(comp), nat.ptr(comp16), 1, M, G, G, G, stream), "magat_cast_rows")
+                if rt.act[0].shape[0] <= 8 and nat.get_option("SKINNY") and self.gat_width % 8 == 0:
+                    gat_rows = self._buf("gat16", (M, self.gat_width), dev, torch.bfloat16)
+                    gat_forward_rows_structure(comp16.view(B, N, G), structure, layer, out=gat_rows)
+                else:
+                    gat_forward_rows_structure(comp16.view(B, N, G), structure, layer, out=gat)
+            else:
+                gat_forward_rows_structure(comp.view(B, N, G), structure, layer, out=gat)
+            layer.aij = None
+            return self._run_actions(rt, feat, comp, gat, gat_rows, M, dev, stream)
+
+
+def _refuse_edges(S, cls):
+    if isinstance(S, GraphEdges):
+        raise TypeError("%s multiplies by the GSO's values: addGSO takes the tensor of simulator.batched_gso, not the edges of "
+                        "batched_edges" % cls.__name__)
+
+
 class DecentralPlannerNet(_PlannerBase):
     """Drop-in for the reference's GNN-baseline model class `DecentralPlannerNet` (graphs/models/decentralplanner.py:14-398; the
     first command of scripts/train_DMap.sh:30, agents/decentralplannerlocal*.py): the same per-agent CNN encoder and
@@ -935,6 +1015,7 @@ class DecentralPlannerNet(_PlannerBase):
 
     def addGSO(self, S):
         """decentralplanner.py:336-353: aliases the caller's tensor, scrubs NaN in place, dist_GSO_one / full_GSO."""
+        _refuse_edges(S, type(self))
         assert len(S.shape) == 3
         gso_mode = _GSO_MODES.get(self.config.GSO_mode, 0)
         # (an EMPTY device GSO goes through the torch ops of the host preparation)
@@ -1024,6 +1105,7 @@ class DecentralPlannerBottleneckNet(DecentralPlannerNet):
     def addGSO(self, S):
         """decentralplanner_bottleneck*.py:262-278: aliases the caller's tensor; NaN scrubbed in place by
         decentralplanner_bottleneck.py (BottomNeck_only) alone; dist_GSO_one / full_GSO in every file."""
+        _refuse_edges(S, type(self))
         assert len(S.shape) == 3
         scrub = self.skip == "only"
         gso_mode = _GSO_MODES.get(self.config.GSO_mode, 0)

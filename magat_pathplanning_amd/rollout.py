@@ -16,6 +16,7 @@ import torch
 
 from . import _native as nat
 from . import _sim_host as sh
+from .edges import GraphEdges
 from .simulator import GUIDANCE_MODES, POLICIES, batched_fov_states, batched_gso, move_needs_wide, new_agent_view
 
 RADIUS_MAX_STEPS = 64           # batched_connect_radius' growth limit
@@ -89,6 +90,7 @@ class EpisodePool:
         self.comm_radius, self.symmetric_norm, self.FOV = float(comm_radius), bool(symmetric_norm), int(FOV)
         self.guidance, self.wide, self.seed = guidance, bool(wide), int(seed) & 0xFFFFFFFFFFFFFFFF
         self._guide_ws = sh._Workspace()
+        self._edges = None
         i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)      # noqa: E731
         self.pos, self.goal = i32(B, N, 2), i32(B, N, 2)
         self.map = torch.zeros(B, H, W, dtype=torch.uint8, device=dev) if batched else self.q_map
@@ -143,6 +145,13 @@ class EpisodePool:
     def gso(self, dtype=torch.float64):
         """getGSO for every slot, with the radius its case grew to at the refill."""
         return batched_gso(self.pos, self.radii, symmetric_norm=self.symmetric_norm, dtype=dtype)
+
+    def edges(self):
+        """gso()'s graph as a GraphEdges over the slots' own positions and radii, for DecentralPlannerGATNet.addGSO: one object
+        per pool, refreshed by every call (BatchedEpisode.edges).  No host synchronisation here."""
+        if self._edges is None:
+            self._edges = GraphEdges(self.pos, radii=self.radii)
+        return self._edges.refresh()
 
     def states(self):
         return batched_fov_states(self.map, self.pos, self.goal, self.FOV, self.guidance, self.agent_view, self.wide,
@@ -200,16 +209,21 @@ class EpisodePool:
                     goal=paths[:, :, -1].contiguous(), solved=self._rows[0].to(torch.uint8))
 
 
-def evaluate_cases(net, obstacle_map, start, goal, maxstep, slots, comm_radius, poll=16, **pool_kw):
+def evaluate_cases(net, obstacle_map, start, goal, maxstep, slots, comm_radius, poll=16, graph="gso", **pool_kw):
     """The validation / test run over a set of cases: every case rolled out in closed loop with `net` (addGSO + forward on the
-    pool's states) until it ends, `slots` at a time; finished() is asked every `poll` steps.  Returns EpisodePool.results()."""
+    pool's states) until it ends, `slots` at a time; finished() is asked every `poll` steps.  Returns EpisodePool.results().
+    graph: 'gso' hands the model the pool's GSO tensor; 'edges' its edge structure from the positions (EpisodePool.edges: the
+    attention models, up to 4096 agents)."""
+    if graph not in ("gso", "edges"):
+        raise ValueError("graph must be 'gso' or 'edges', got %r" % (graph,))
     pool = EpisodePool(obstacle_map, start, goal, maxstep, slots, comm_radius, **pool_kw)
+    the_graph = pool.edges if graph == "edges" else pool.gso
     poll = max(int(poll), 1)
     calls, bound = 0, pool.max_calls()
     with torch.no_grad():
         while True:
             for _ in range(poll):
-                net.addGSO(pool.gso())
+                net.addGSO(the_graph())
                 pool.step(logits=net(pool.states()))
             calls += poll
             if pool.finished():

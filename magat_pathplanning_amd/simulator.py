@@ -8,6 +8,8 @@ step, in numpy on the host right before the model call -
 - for B independent planning instances at once, on the GPU, so that a batched closed loop never leaves the device:
 
     S = batched_gso(pos, config.commR)                   # (B,N,N), what model.addGSO() takes
+    E = batched_edges(pos, config.commR)                 # the same graph as an edge structure (edges.py): what the attention
+                                                         # models' addGSO() takes as well - no (B,N,N) tensor, up to 4096 agents
     x = batched_fov_states(obstacle_map, pos, goal, 9)   # (B,N,3,11,11), what model.forward() takes
     x = batched_fov_states(obstacle_map, pos, goal, 9, guidance="GlobalG_SD")      # config.guidance: the A*-guided encodings
 
@@ -24,6 +26,7 @@ import torch
 from . import _native as nat
 from . import _sim_host as sh
 from ._sim_host import _Workspace, dev_i32 as _dev_i32      # noqa: F401  (the names other modules and tools import from here)
+from .edges import GraphEdges, batched_edges                # noqa: F401  (the graph as edges from positions: edges.py)
 
 
 def batched_connect_radius(pos, comm_radius, max_steps=64, return_steps=False):
@@ -279,6 +282,7 @@ class BatchedEpisode:
             self.agent_view = new_agent_view(B, N, self.map.shape[-2], self.map.shape[-1], self.FOV, dev)
         self.currentstep = 0
         self.radii = None
+        self._edges = None
         self.reach_goal = torch.zeros(B, N, dtype=torch.uint8, device=dev)
         self.first_move = torch.zeros(B, N, dtype=torch.int32, device=dev)
         self.end_step = torch.zeros(B, N, dtype=torch.int32, device=dev)
@@ -290,8 +294,7 @@ class BatchedEpisode:
         self.makespan = torch.full((B,), self.maxstep, dtype=torch.int32, device=dev)
         self.flowtime = torch.full((B,), self.maxstep * N, dtype=torch.int32, device=dev)
 
-    def gso(self, dtype=torch.float64):
-        """getGSO(step): at the first call the radius grows until each instance's graph is connected and is kept."""
+    def _grow_radii(self):
         if self.radii is None:
             self.radii, steps = batched_connect_radius(self.pos, self.comm_radius, return_steps=True)
             # once per episode (the reference grows the radius until the graph IS connected, new_simulator.py:759-768):
@@ -300,7 +303,20 @@ class BatchedEpisode:
                 bad = torch.nonzero(steps < 0).flatten().tolist()
                 raise nat.MagatNativeError("communication graph still disconnected after the radius growth limit in "
                                            "instances %s" % bad[:8])
+
+    def gso(self, dtype=torch.float64):
+        """getGSO(step): at the first call the radius grows until each instance's graph is connected and is kept."""
+        self._grow_radii()
         return batched_gso(self.pos, self.radii, symmetric_norm=self.symmetric_norm, dtype=dtype)
+
+    def edges(self):
+        """gso()'s graph as a GraphEdges over the episode's own positions and kept radii (the same growth and the same check at
+        the first call) - for DecentralPlannerGATNet.addGSO.  One object per episode, refreshed by every call: its structure is
+        built from the positions as they are when addGSO asks for it, and the forward orders the stream behind that build."""
+        self._grow_radii()
+        if self._edges is None:
+            self._edges = GraphEdges(self.pos, radii=self.radii)
+        return self._edges.refresh()
 
     def states(self):
         return batched_fov_states(self.map, self.pos, self.goal, self.FOV, self.guidance, self.agent_view, self.wide,

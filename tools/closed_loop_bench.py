@@ -1,7 +1,15 @@
 """Closed loop entirely on the device: per step  GSO construction -> FOV state tensors -> addGSO + forward -> action decode +
 collision shielding + position update, for B independent planning instances (what the reference does per instance on the
 host around a batch-1 forward: agents/decentralplannerlocal_OnlineExpert_GAT.py:880-905 -> utils/new_simulator.py).
-Reports agent-steps/s of the whole loop next to the forward alone."""
+Reports agent-steps/s of the whole loop next to the forward alone.
+
+    python tools/closed_loop_bench.py [B N size T]
+    python tools/closed_loop_bench.py B N size T --graph gso|edges|both [--storage bf16] [--rounds R]
+
+--graph times the step with the graph handed over as the GSO tensor (batched_gso) and / or as the edge structure from the
+positions (batched_edges, DESIGN 4.5: the only route above 2048 agents): the legs alternate inside this process, R rounds of T
+steps each on the same moving positions, and the median, the smallest and the largest round of each leg are printed - nothing else
+of the script runs then."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import numpy as np
@@ -10,7 +18,20 @@ from magat_pathplanning_amd import DecentralPlannerGATNet
 from magat_pathplanning_amd.simulator import batched_fov_states, batched_gso, batched_move
 from magat_pathplanning_amd.synthetic import make_config
 
-B, N, size, T = (int(a) for a in (sys.argv[1:5] + ["512", "100", "50", "20"][len(sys.argv) - 1:]))
+ARGV = sys.argv[1:]
+
+
+def flag(name, default):
+    if name not in ARGV:
+        return default
+    i = ARGV.index(name)
+    value = ARGV[i + 1]
+    del ARGV[i:i + 2]
+    return value
+
+
+GRAPH, STORAGE, ROUNDS = flag("--graph", None), flag("--storage", "fp32"), int(flag("--rounds", "5"))
+B, N, size, T = (int(a) for a in (ARGV[:4] + ["512", "100", "50", "20"][len(ARGV):]))
 dev = torch.device("cuda:0")
 rng = np.random.default_rng(3)
 m = (rng.random((size, size)) < 0.08).astype(np.uint8)
@@ -19,8 +40,59 @@ pos = np.stack([free[rng.permutation(len(free))[:N]] for _ in range(B)]).astype(
 goal = np.stack([free[rng.permutation(len(free))[:N]] for _ in range(B)]).astype(np.int32)
 dm, dpos, dgoal = torch.from_numpy(m).to(dev), torch.from_numpy(pos).to(dev).contiguous(), torch.from_numpy(goal).to(dev)
 cfg = make_config(num_agents=N, nGraphFilterTaps=3, nAttentionHeads=4, bottleneckMode="BottomNeck_skipConcat", device=str(dev))
+if STORAGE != "fp32":
+    cfg.gat_storage = STORAGE
 torch.manual_seed(0)
 net = DecentralPlannerGATNet(cfg).to(dev).eval()
+
+
+def graph_legs():
+    """--graph: the step with the GSO tensor against the step with the edge structure, alternating"""
+    from magat_pathplanning_amd.simulator import batched_edges
+    legs = [g for g in ("gso", "edges") if GRAPH in (g, "both")]
+    if not legs:
+        raise SystemExit("--graph takes gso, edges or both")
+    edges = batched_edges(dpos, 7.0)              # over dpos itself: refreshed behind every move, its arrays reused
+
+    def one(leg):
+        with torch.no_grad():
+            net.addGSO(edges.refresh() if leg == "edges" else batched_gso(dpos, 7.0))
+            logits = net(batched_fov_states(dm, dpos, dgoal, 9))
+        return batched_move(dm, dpos, logits=logits, goal=dgoal, wide=True)
+
+    def box_clock():
+        """the core clock this box holds under matrix load (the numbers move with it)"""
+        import ctypes
+        from magat_pathplanning_amd import _native as nat
+        cus = torch.cuda.get_device_properties(dev).multi_processor_count
+        scratch = torch.empty(256 * cus + 4 * cus, dtype=torch.float32, device=dev)
+        tf, mhz, per = ctypes.c_double(0), ctypes.c_double(0), ctypes.c_double(0)
+        nat.check(nat.lib().magat_mfma_sustained_f16_ex(ctypes.byref(tf), ctypes.byref(mhz), ctypes.byref(per), nat.ptr(scratch), 5,
+                                                        nat.current_stream(dev)), "magat_mfma_sustained_f16_ex")
+        return mhz.value
+
+    ms = {leg: [] for leg in legs}
+    for leg in legs:
+        for _ in range(3):
+            one(leg)
+    for _ in range(ROUNDS):
+        for leg in legs:
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            for _ in range(T):
+                one(leg)
+            torch.cuda.synchronize()
+            ms[leg].append((time.perf_counter() - t0) / T * 1e3)
+    for leg in legs:
+        v = sorted(ms[leg])
+        print("B %d N %d map %dx%d storage %s graph=%s: closed loop median %.3f ms/step (%.3f .. %.3f over %d rounds of %d steps) = "
+              "%.2f M agent-steps/s" % (B, N, size, size, STORAGE, leg, v[len(v) // 2], v[0], v[-1], ROUNDS, T, B * N / v[len(v) // 2] / 1e3))
+    print("sustained matrix clock of this box: %.0f MHz" % box_clock())
+
+
+if GRAPH is not None:
+    graph_legs()
+    sys.exit(0)
 
 
 NORMALIZE = True

@@ -12,7 +12,10 @@ initialised DecentralPlannerGATNet (K = 3, P = 4, skipConcat) every step and thr
 real one does.  The gain to expect is about max(maxstep) / mean(steps) where the episodes end by arrival.  Wall clock around the
 whole run with a device synchronisation at both ends, median of --repeats; one JSON line per shape.
 
-    python tools/rollout_bench.py [--forward] [--slots B] [--repeats K] [--poll P]"""
+    python tools/rollout_bench.py [--forward] [--slots B] [--repeats K] [--poll P] [--graph gso|edges]
+
+--graph edges hands the model the pool's / the episode's edge structure from the positions instead of the GSO tensor (DESIGN 4.5;
+it only matters with --forward: the stand-in policy never reads the graph)."""
 import argparse
 import json
 import os
@@ -70,6 +73,7 @@ def main():
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--poll", type=int, default=16)
     ap.add_argument("--forward", action="store_true", help="run a randomly initialised DecentralPlannerGATNet every step, for its cost")
+    ap.add_argument("--graph", choices=("gso", "edges"), default="gso", help="what addGSO is given: the GSO tensor or the edge structure")
     args = ap.parse_args()
     import torch
     from magat_pathplanning_amd import (BatchedEpisode, DecentralPlannerGATNet, evaluate_cases, generate_cases, reference_maxstep,
@@ -92,7 +96,8 @@ def main():
         kw = dict(action_select="exp_multinorm", seed=sh["seed"], guidance=GUIDANCE)
 
         def pool():
-            return evaluate_cases(net, cases["map"], cases["start"], cases["goal"], maxstep, B, COMM_RADIUS, poll=args.poll, **kw)
+            return evaluate_cases(net, cases["map"], cases["start"], cases["goal"], maxstep, B, COMM_RADIUS, poll=args.poll,
+                                  graph=args.graph, **kw)
 
         def fixed():
             reached = 0
@@ -104,7 +109,7 @@ def main():
                                         action_select="exp_multinorm", guidance=GUIDANCE)
                     ep.currentstep = 1
                     for _ in range(limit):
-                        net.addGSO(ep.gso())
+                        net.addGSO(ep.edges() if args.graph == "edges" else ep.gso())
                         ep.step(logits=net(ep.states()))
                     reached += int(ep.done.sum())
             return reached
@@ -112,7 +117,7 @@ def main():
         r, pool_s = timed(pool, args.repeats)
         reached, fixed_s = timed(fixed, args.repeats)
         steps = r["steps"].float()
-        print(json.dumps(dict(shape=sh["name"], forward=bool(args.forward), cases=C, agents=N, slots=B, maxstep_max=int(maxstep.max()),
+        print(json.dumps(dict(shape=sh["name"], forward=bool(args.forward), graph=args.graph, cases=C, agents=N, slots=B, maxstep_max=int(maxstep.max()),
                               maxstep_mean=float(maxstep.float().mean()), steps_mean=float(steps.mean()),
                               all_reach=float(r["all_reach"].float().mean()), expected_gain=float(maxstep.max()) / float(steps.mean()),
                               pool_s=pool_s, pool_cases_per_s=C / pool_s, fixed_s=fixed_s, fixed_cases_per_s=C / fixed_s,
