@@ -206,6 +206,9 @@ int magat_gnn_forward_csr_f32(const float* X, const int* rowptr, const int* coli
  * MAGAT_ERR_UNSUPPORTED before anything is launched (the caller then takes magat_gnn_forward_csr_f32). */
 int magat_gnn_forward_dense_f32(const float* X, int ldx, const void* S, int s_is_f64, const float* weight, const float* bias,
                                 float* Y, int ldy, int B, int N, int Nin, int G, int F, int K, int relu, void* stream);
+/* 1: a graph of N agents with these widths and tap count is one magat_gnn_forward_dense_f32 serves (the "Supported" line above,
+ * the test that entry itself makes first); 0: it answers MAGAT_ERR_UNSUPPORTED.  Additive behind ABI 9. */
+int magat_gnn_dense_supported(int N, int G, int F, int K);
 /* bf16-STORAGE variant (BASELINE config 5: "1000 agents, CSR, bf16"; SURVEY.md 8(b) `..._csr_{f32,bf16}`): X, the hoisted
  * maps Z, the hop intermediates and Y are bf16 in HBM (raw uint16 bit patterns, RNE), all arithmetic accumulates in
  * fp32 (bf16 MFMA for the maps GEMM with the RNE-bf16 plane of the packed weights; fp32 scores / softmax / gathers),
@@ -554,6 +557,26 @@ size_t magat_gso_edges_workspace_bytes(int B, int N);
 int magat_gso_edges_build(const int32_t* pos, const double* radii /* [B] or NULL */, double comm_radius, int edge_rule /* 0 | 1 */,
                           int* rowptr, int* colidx, int* cscptr, int* cscsrc, int* cscpos, long long cap, long long* nnz_dev,
                           void* workspace, size_t workspace_bytes, int B, int N, void* stream);
+/* The GSO's values on that structure (gso_edge_values.hip; additive behind ABI 9), for the layers that multiply by them -
+ * GraphFilterBatch through magat_gnn_forward_csr_f32 / magat_gnn_backward_csr_f32 - without a (B,N,N) tensor, N <= 4096.
+ * rowptr, colidx, nnz_dev, cap: what magat_gso_edges_build made under edge rule 0 (nnz_dev travels with the structure and must
+ * not be NULL; whether an instance lies inside cap is read from rowptr, which stays true beyond it).  lambda_out [B] float64: lambda_max of W, or of
+ * D^-1/2 W D^-1/2 under symmetric_norm, by magat_sim_gso's rule for more than 128 agents (Lanczos from the all-ones vector, Sturm
+ * multisection of the tridiagonal matrix, up to N steps; tests/gso_lanczos_restatement.py) - 0 for an instance without an edge and
+ * when normalize == 0.  vals [cap] float32: per CSR entry (i, j) the float32 of the float64 quotient 1 / div, or
+ * (inv[i] * inv[j]) / div under symmetric_norm with inv[i] = sqrt(1 / degree(i)); div = lambda_max when normalize != 0, else 1.
+ * Entries behind the edge count are not written.  Capacity contract: an instance whose edges do not all lie below cap is not
+ * walked (lambda_out 0, no values) - the caller re-builds the structure with a larger capacity and calls again.  One launch, one
+ * workgroup per instance, no host synchronisation, no atomics on device memory: the same result on every call.  Workspace:
+ * magat_gso_edge_values_workspace_bytes (the tridiagonal matrix of every instance, 16 max(N, 160) + 16 bytes each - used from 4093
+ * agents on, where it no longer fits the workgroup's 160 KB of LDS beside the three vectors; 0 = N > 4096
+ * or a size <= 0), 256-byte aligned.  Answers before anything is launched: NULL pointers MAGAT_ERR_NULL (colidx and vals only with
+ * cap == 0), then B, N <= 0 or cap < 0: MAGAT_ERR_BAD_SHAPE, then N > 4096: MAGAT_ERR_UNSUPPORTED, then the workspace:
+ * MAGAT_ERR_WORKSPACE.  Booked under magat_gso_edges_build's profiling tag and form counter (one span, one count per call). */
+size_t magat_gso_edge_values_workspace_bytes(int B, int N);
+int magat_gso_edge_values(const int* rowptr, const int* colidx, const long long* nnz_dev, long long cap, int symmetric_norm,
+                          int normalize, double* lambda_out, float* vals, void* workspace, size_t workspace_bytes, int B, int N,
+                          void* stream);
 /* magat_gat_forward_csr_{f32,bf16} with the CSC view from magat_gso_csr_build (no per-call transpose; workspace:
  * magat_gat_csc_workspace_bytes - the csr_* figure minus the transpose scratch, 3 * nnz ints) */
 size_t magat_gat_csc_workspace_bytes(int B, int N, long long nnz, int G, int F, int K, int P, int mode, int concat, int bf16);

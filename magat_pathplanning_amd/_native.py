@@ -140,6 +140,7 @@ _SIGNATURES = {
     "magat_gat_csr_workspace_bytes": (_Z, [_I, _I, ctypes.c_longlong] + [_I] * 6),
     "magat_gat_forward_csr_f32": (_I, [_P, _P, _P, ctypes.c_longlong, _P, _P, _P, _I, _P, _P, _Z] + [_I] * 8 + [_P]),
     "magat_gnn_forward_csr_f32": (_I, [_P, _P, _P, _P, ctypes.c_longlong, _P, _P, _P, _I, _P, _Z] + [_I] * 5 + [_P]),
+    "magat_gnn_dense_supported": (_I, [_I] * 4),
     "magat_gnn_forward_dense_f32": (_I, [_P, _I, _P, _I, _P, _P, _P, _I] + [_I] * 7 + [_P]),
     "magat_gat_csr_bf16_workspace_bytes": (_Z, [_I, _I, ctypes.c_longlong] + [_I] * 6),
     "magat_gat_csc_workspace_bytes": (_Z, [_I, _I, ctypes.c_longlong] + [_I] * 7),
@@ -153,6 +154,8 @@ _SIGNATURES = {
     "magat_gso_csr_build_phase": (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _P, _P, ctypes.c_longlong, _P, _P, _Z, _I, _I, _I, _P]),
     "magat_gso_edges_workspace_bytes": (_Z, [_I, _I]),
     "magat_gso_edges_build": (_I, [_P, _P, ctypes.c_double, _I, _P, _P, _P, _P, _P, ctypes.c_longlong, _P, _P, _Z, _I, _I, _P]),
+    "magat_gso_edge_values_workspace_bytes": (_Z, [_I, _I]),
+    "magat_gso_edge_values": (_I, [_P, _P, _P, ctypes.c_longlong, _I, _I, _P, _P, _P, _Z, _I, _I, _P]),
     "magat_gat_forward_csc_f32": (_I, [_P] * 6 + [ctypes.c_longlong, _P, _P, _P, _I, _P, _P, _Z] + [_I] * 8 + [_P]),
     "magat_gat_forward_csc_bf16": (_I, [_P] * 6 + [ctypes.c_longlong, _P, _P, _P, _I, _P, _P, _Z] + [_I] * 8 + [_P]),
     "magat_gat_forward_csc_bf16_f32out": (_I, [_P] * 6 + [ctypes.c_longlong, _P, _P, _P, _I, _P, _P, _Z] + [_I] * 8 + [_P]),

@@ -12,7 +12,7 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG, "csrc")
 LIB = os.path.join(PKG, "lib", "libmagat_hip.so")
 LIB_DEBUG = os.path.join(PKG, "lib", "libmagat_hip_debug.so")
-SOURCES = ["conv_gemm_f32.hip", "conv_gemm_bf16x6.hip", "block_fused.hip", "block_lat.hip", "gat_f32.hip", "gat_pack.hip", "gat_mfma.hip", "gat_small.hip", "gat_mid.hip", "gat_csr_f32.hip", "gat_train.hip", "gso_csr.hip", "gso_edges.hip", "gat_csr_fused.hip", "gnn_dense.hip",
+SOURCES = ["conv_gemm_f32.hip", "conv_gemm_bf16x6.hip", "block_fused.hip", "block_lat.hip", "gat_f32.hip", "gat_pack.hip", "gat_mfma.hip", "gat_small.hip", "gat_mid.hip", "gat_csr_f32.hip", "gat_train.hip", "gso_csr.hip", "gso_edges.hip", "gso_edge_values.hip", "gat_csr_fused.hip", "gnn_dense.hip",
            "encoder_f32.hip", "layer1_fused.hip", "stem8.hip", "conv_train.hip", "head_loss.hip", "sim_frontend.hip", "sim_guidance.hip", "sim_guidance_wide.hip", "sim_expert.hip", "sim_mapf.hip", "sim_cases.hip", "sim_mapf_wide.hip", "sim_mapf_lns.hip", "sim_mapf_lns_wide.hip", "sim_mapf_audit.hip", "sim_mapf_audit_wide.hip", "sim_mapf_cbs.hip", "sim_mapf_ecbs.hip", "sim_mapf_ecbs_wide.hip", "sim_cases_wide.hip", "sim_pool.hip", "profile.hip", "options.hip"]
 HEADERS = ["magat_common.h", "encoder_pack.h", "encoder_route.h", "f16x3.h", "gat_pack.h", "gat_route.h", "gat_csr_route.h", "gat_cos_parts.h", "gat_small_body.inc", "gat_mid_body.inc", "block_walk.h", "skinny_rows.h", "sim_connect.h", "sim_expert_pick.h", "row_board.h", "sim_group.h", "sim_entry.h", "sim_mapf_parts.h", "sim_mapf_wide_parts.h", "sim_mapf_audit_parts.h", "sim_mapf_cbs_parts.h", "sim_mapf_ecbs_parts.h", "sim_mapf_tree.h", "sim_mapf_lns_walk.h", "sim_guidance_parts.h", "cases_draw.h", os.path.join("..", "..", "include", "magat_hip.h")]
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-contract=off", "-Wno-unused-value", "-Wno-inline-asm"]

@@ -140,11 +140,15 @@ int launch_gnn_dense(const GnnDenseParams& p, int slot, hipStream_t st) {
 
 }  // namespace
 
+extern "C" int magat_gnn_dense_supported(int N, int G, int F, int K) {
+  const bool width_ok = (G == 16 || G == 32 || G == 64 || G == 128) && (F == 16 || F == 32 || F == 64 || F == 128);
+  return (N >= 1 && N <= 128 && K >= 1 && K <= 8 && width_ok) ? 1 : 0;
+}
+
 extern "C" int magat_gnn_forward_dense_f32(const float* X, int ldx, const void* S, int s_is_f64, const float* weight,
                                            const float* bias, float* Y, int ldy, int B, int N, int Nin, int G, int F, int K,
                                            int relu, void* stream) {
-  const bool width_ok = (G == 16 || G == 32 || G == 64 || G == 128) && (F == 16 || F == 32 || F == 64 || F == 128);
-  if (N < 1 || N > 128 || K < 1 || K > 8 || !width_ok) return MAGAT_ERR_UNSUPPORTED;
+  if (!magat_gnn_dense_supported(N, G, F, K)) return MAGAT_ERR_UNSUPPORTED;
   if (B < 1 || Nin < 1 || Nin > N || ldx < G || ldy < F) return MAGAT_ERR_BAD_SHAPE;
   if (!X || !S || !weight || !Y) return MAGAT_ERR_NULL;
   if (ldy % 4) return MAGAT_ERR_BAD_SHAPE;                               // (the header's alignment rules of every

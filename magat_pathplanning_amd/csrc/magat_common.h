@@ -184,7 +184,10 @@ enum MagatLdsSlot {
   MAGAT_LDS_GATS_COS_0,                         // gat_small.hip, cosine form (GAT_Similarity): 4 slots (width x taps)
   MAGAT_LDS_GATS_COS_END = MAGAT_LDS_GATS_COS_0 + 4,
   MAGAT_LDS_GATD_COS_0 = MAGAT_LDS_GATS_COS_END,  // gat_mid.hip, cosine form: 12 slots (width x taps x row tiles) + 2 of the 128-wide form
-  MAGAT_LDS_END = MAGAT_LDS_GATD_COS_0 + 14
+  MAGAT_LDS_GATD_COS_END = MAGAT_LDS_GATD_COS_0 + 14,
+  MAGAT_LDS_GSO_VALUES = MAGAT_LDS_GATD_COS_END,  // gso_edge_values.hip: the tridiagonal matrix in LDS (N <= 4092)
+  MAGAT_LDS_GSO_VALUES_WS,                        // ... and in the workspace (4093 .. 4096 agents)
+  MAGAT_LDS_END
 };
 static_assert(MAGAT_LDS_END <= MAGAT_LDS_SLOTS, "LDS attribute slots");
 

@@ -69,6 +69,11 @@ def _gso3(S, B, N, dev):
     return S3.to(dev, S3.dtype if S3.dtype in (torch.float32, torch.float64) else torch.float32).contiguous()
 
 
+def _is_edges(S):
+    """a GraphEdges (edges.py imports this module: the class is told by its attribute)"""
+    return hasattr(S, "valued") and hasattr(S, "structure")
+
+
 def _edge_rows(rowptr, B, N):
     """Row index (0 .. B*N-1) of every stored edge, in CSR order, from the absolute offsets rowptr [B*(N+1)]."""
     rp = rowptr.view(B, N + 1).long()
@@ -653,6 +658,8 @@ class _DropsDeviceState:
     def __getstate__(self):
         st = self.__dict__.copy()
         st.update(_scratch=None, aij=None, _edge_views=None)
+        if _is_edges(st.get("S")):          # (a GraphEdges holds streams and events: the copy asks for addGSO again)
+            st["S"] = None
         return st
 
     def __setstate__(self, st):
@@ -996,13 +1003,29 @@ class GraphFilterBatch(_DropsDeviceState, nn.Module):
             if self.bias is not None:
                 self.bias.uniform_(-stdv, stdv)
 
+    unit_values = False     # addGSO(edges): every edge weighs 1 (the planners' GSO_mode 'dist_GSO_one') instead of the GSO's values
+
     def addGSO(self, S):
+        """S (B,E,N,N), or the graph as a GraphEdges made with values=True (edges.py): the HIP routes then read the structure's
+        arrays and the values magat_gso_edge_values leaves on them - no (B,N,N) tensor, up to 4096 agents."""
+        if _is_edges(S):
+            if not S.valued:
+                raise TypeError("GraphFilterBatch multiplies by the GSO's values: addGSO takes the tensor of simulator.batched_gso, "
+                                "or the edges of batched_edges(..., values=True)")
+            self.N = S.N
+            self.S = S
+            return
         assert len(S.shape) == 4 and S.shape[1] == self.E and S.shape[2] == S.shape[3]     # graphML.py:5661-5668
         self.N = S.shape[2]
         self.S = S
 
     def forward(self, x):
         Nin = x.shape[2]
+        if _is_edges(self.S) and (x.shape[0] != self.S.B or Nin != self.S.N or not x.is_cuda):
+            if not x.is_cuda:
+                _require_device(x, "graph layer on an edge structure")
+            raise ValueError("GraphFilterBatch: addGSO(edges) was given the graph of %d instances x %d agents, forward a batch of "
+                             "%d x %d" % (self.S.B, self.S.N, x.shape[0], Nin))
         x, needs_grad = _intake(self, x)
         N = self.N
         if needs_grad and not x.is_cuda:
@@ -1024,8 +1047,12 @@ class GraphFilterBatch(_DropsDeviceState, nn.Module):
         return y
 
     def _csr(self, dev, B):
-        """CSR arrays of float(S) (every non-zero entry, values kept) for the HIP kernels."""
+        """CSR arrays of float(S) (every non-zero entry, values kept) for the HIP kernels.  A GraphEdges brings them as they
+        are: the structure's rowptr and colidx, the values launched behind its build, its own edge-count read."""
         N = self.N
+        if _is_edges(self.S):
+            st, vals, _ = self.S.values(normalize=not self.unit_values)
+            return st.rowptr, st.colidx, vals, st.exact_nnz()
         S3 = _gso3(self.S, B, N, dev)
         rowptr, colidx, nnz = dense_gso_to_csr(S3, self_loops=self.edge_rule)
         vals = S3.reshape(B * N, N)[_edge_rows(rowptr, B, N), colidx[:nnz].long()].float().contiguous() if nnz else \

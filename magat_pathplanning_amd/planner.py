@@ -954,9 +954,9 @@ class DecentralPlannerGATNet(_PlannerBase):
 
 
 def _refuse_edges(S, cls):
-    if isinstance(S, GraphEdges):
-        raise TypeError("%s multiplies by the GSO's values: addGSO takes the tensor of simulator.batched_gso, not the edges of "
-                        "batched_edges" % cls.__name__)
+    if isinstance(S, GraphEdges) and not S.valued:
+        raise TypeError("%s multiplies by the GSO's values: addGSO takes the tensor of simulator.batched_gso, or the edges of "
+                        "batched_edges(..., values=True), not the plain edges of batched_edges" % cls.__name__)
 
 
 class DecentralPlannerNet(_PlannerBase):
@@ -1016,6 +1016,8 @@ class DecentralPlannerNet(_PlannerBase):
     def addGSO(self, S):
         """decentralplanner.py:336-353: aliases the caller's tensor, scrubs NaN in place, dist_GSO_one / full_GSO."""
         _refuse_edges(S, type(self))
+        if isinstance(S, GraphEdges):
+            return self._add_valued_edges(S)
         assert len(S.shape) == 3
         gso_mode = _GSO_MODES.get(self.config.GSO_mode, 0)
         # (an EMPTY device GSO goes through the torch ops of the host preparation)
@@ -1025,10 +1027,30 @@ class DecentralPlannerNet(_PlannerBase):
         else:
             self.S = _gso_prepare_host(S, True, gso_mode, self.config.device)
 
+    def _add_valued_edges(self, edges):
+        """addGSO(edges), edges made with values=True: GraphFilterBatch's CSR kernels read the structure's arrays and the values
+        magat_gso_edge_values leaves on them (csrc/gso_edge_values.hip) - inference and training, up to 4096 agents, no (B,N,N)
+        tensor.  self.S is then the GraphEdges itself.  'dist_GSO_one': every edge weighs 1, no eigenvalue.  'full_GSO' is the
+        all-ones TENSOR: edges.gso() through the tensor path, with batched_gso's limit.  The NaN scrub has nothing to do."""
+        gso_mode = _GSO_MODES.get(self.config.GSO_mode, 0)
+        if gso_mode == 2 or self._edges_take_tensor(edges):
+            return self.addGSO(edges.gso())
+        self.GFL[0].unit_values = gso_mode == 1
+        self.S = edges
+        edges.structure(0)                     # the build starts here, on the side stream: under the per-agent CNN
+
+    def _edges_take_tensor(self, edges):
+        return False
+
     def returnAttentionGSO(self):
         raise AttributeError("DecentralPlannerNet has no attention (GraphFilterBatch)")
 
     def _check_gso_shape(self, B, N):
+        if isinstance(self.S, GraphEdges):
+            if self.S.B != B or self.S.N != N:
+                raise ValueError("%s: addGSO(edges) was given the graph of %d instances x %d agents, forward a batch of %d x %d"
+                                 % (type(self).__name__, self.S.B, self.S.N, B, N))
+            return
         if self.S.shape[0] != B or self.S.shape[-1] < N:
             raise RuntimeError("%s: GSO of shape %s does not match a batch of %d instances x %d agents"
                                % (type(self).__name__, tuple(self.S.shape), B, N))
@@ -1036,7 +1058,7 @@ class DecentralPlannerNet(_PlannerBase):
     def _csr_rows(self, layer, comp, B, N, M):
         """GraphFilterBatch on the CSR kernels (the layer holds the GSO already) + the ReLU behind it: (M, gat_width) rows."""
         xg = comp.view(B, N, self.numFeatures2Share).permute(0, 2, 1)
-        if self.S.shape[-1] == N:
+        if isinstance(self.S, GraphEdges) or self.S.shape[-1] == N:
             # rows in, rows out ((B, F, N) is a view of the (M, F) result)
             y = layer._forward_hip(xg)[0]
         else:
@@ -1106,6 +1128,8 @@ class DecentralPlannerBottleneckNet(DecentralPlannerNet):
         """decentralplanner_bottleneck*.py:262-278: aliases the caller's tensor; NaN scrubbed in place by
         decentralplanner_bottleneck.py (BottomNeck_only) alone; dist_GSO_one / full_GSO in every file."""
         _refuse_edges(S, type(self))
+        if isinstance(S, GraphEdges):
+            return self._add_valued_edges(S)
         assert len(S.shape) == 3
         scrub = self.skip == "only"
         gso_mode = _GSO_MODES.get(self.config.GSO_mode, 0)
@@ -1115,6 +1139,13 @@ class DecentralPlannerBottleneckNet(DecentralPlannerNet):
             self.S = S.unsqueeze(1)
         else:
             self.S = _gso_prepare_host(S, scrub, gso_mode, self.config.device)
+
+    def _edges_take_tensor(self, edges):
+        """the one-launch dense kernel reads a GSO tensor: graphs it serves in inference (N <= 128) take edges.gso()"""
+        layer = self.GFL[0]
+        if self.training:
+            return False
+        return bool(nat.lib().magat_gnn_dense_supported(edges.N, self.numFeatures2Share, layer.F, layer.K))
 
     def forward(self, inputTensor):
         # the refusal fires before anything else of forward(), as an override: _PlannerBase.forward, which every step of the
@@ -1141,8 +1172,12 @@ class DecentralPlannerBottleneckNet(DecentralPlannerNet):
             stream = nat.current_stream(dev)
             feat, comp = self._run_encoder(rt, x, M, dev, stream)
             S = self.S
-            Ns = S.shape[-1]
             self._check_gso_shape(B, N)
+            if isinstance(S, GraphEdges):      # beyond the dense kernel: GraphFilterBatch's CSR route on the structure's arrays
+                layer.addGSO(S)
+                rows = self._csr_rows(layer, comp, B, N, M)
+                return self._run_actions(rt, feat, comp, rows, rows, M, dev, stream)
+            Ns = S.shape[-1]
             rows = self._buf("gat", (M, self.gat_width), dev)
             S3 = _gso3(S, B, Ns, dev)
             w = layer.weight.detach().to(dev, torch.float32).contiguous()

@@ -90,7 +90,7 @@ class EpisodePool:
         self.comm_radius, self.symmetric_norm, self.FOV = float(comm_radius), bool(symmetric_norm), int(FOV)
         self.guidance, self.wide, self.seed = guidance, bool(wide), int(seed) & 0xFFFFFFFFFFFFFFFF
         self._guide_ws = sh._Workspace()
-        self._edges = None
+        self._edges = self._valued_edges = None
         i32 = lambda *s: torch.zeros(*s, dtype=torch.int32, device=dev)      # noqa: E731
         self.pos, self.goal = i32(B, N, 2), i32(B, N, 2)
         self.map = torch.zeros(B, H, W, dtype=torch.uint8, device=dev) if batched else self.q_map
@@ -146,9 +146,14 @@ class EpisodePool:
         """getGSO for every slot, with the radius its case grew to at the refill."""
         return batched_gso(self.pos, self.radii, symmetric_norm=self.symmetric_norm, dtype=dtype)
 
-    def edges(self):
+    def edges(self, values=False):
         """gso()'s graph as a GraphEdges over the slots' own positions and radii, for DecentralPlannerGATNet.addGSO: one object
-        per pool, refreshed by every call (BatchedEpisode.edges).  No host synchronisation here."""
+        per pool, refreshed by every call (BatchedEpisode.edges).  No host synchronisation here.  values=True: with gso()'s
+        values under the pool's symmetric_norm, for the GNN planners' addGSO."""
+        if values:
+            if self._valued_edges is None:
+                self._valued_edges = GraphEdges(self.pos, radii=self.radii, values=True, symmetric_norm=self.symmetric_norm)
+            return self._valued_edges.refresh()
         if self._edges is None:
             self._edges = GraphEdges(self.pos, radii=self.radii)
         return self._edges.refresh()
@@ -213,11 +218,12 @@ def evaluate_cases(net, obstacle_map, start, goal, maxstep, slots, comm_radius, 
     """The validation / test run over a set of cases: every case rolled out in closed loop with `net` (addGSO + forward on the
     pool's states) until it ends, `slots` at a time; finished() is asked every `poll` steps.  Returns EpisodePool.results().
     graph: 'gso' hands the model the pool's GSO tensor; 'edges' its edge structure from the positions (EpisodePool.edges: the
-    attention models, up to 4096 agents)."""
-    if graph not in ("gso", "edges"):
-        raise ValueError("graph must be 'gso' or 'edges', got %r" % (graph,))
+    attention models, up to 4096 agents); 'valued_edges' that structure with the GSO's values on it (EpisodePool.edges(values=True):
+    the GNN planners, up to 4096 agents)."""
+    if graph not in ("gso", "edges", "valued_edges"):
+        raise ValueError("graph must be 'gso', 'edges' or 'valued_edges', got %r" % (graph,))
     pool = EpisodePool(obstacle_map, start, goal, maxstep, slots, comm_radius, **pool_kw)
-    the_graph = pool.edges if graph == "edges" else pool.gso
+    the_graph = {"gso": pool.gso, "edges": pool.edges, "valued_edges": lambda: pool.edges(values=True)}[graph]
     poll = max(int(poll), 1)
     calls, bound = 0, pool.max_calls()
     with torch.no_grad():

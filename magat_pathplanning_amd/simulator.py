@@ -282,7 +282,7 @@ class BatchedEpisode:
             self.agent_view = new_agent_view(B, N, self.map.shape[-2], self.map.shape[-1], self.FOV, dev)
         self.currentstep = 0
         self.radii = None
-        self._edges = None
+        self._edges = self._valued_edges = None
         self.reach_goal = torch.zeros(B, N, dtype=torch.uint8, device=dev)
         self.first_move = torch.zeros(B, N, dtype=torch.int32, device=dev)
         self.end_step = torch.zeros(B, N, dtype=torch.int32, device=dev)
@@ -309,11 +309,17 @@ class BatchedEpisode:
         self._grow_radii()
         return batched_gso(self.pos, self.radii, symmetric_norm=self.symmetric_norm, dtype=dtype)
 
-    def edges(self):
+    def edges(self, values=False):
         """gso()'s graph as a GraphEdges over the episode's own positions and kept radii (the same growth and the same check at
         the first call) - for DecentralPlannerGATNet.addGSO.  One object per episode, refreshed by every call: its structure is
-        built from the positions as they are when addGSO asks for it, and the forward orders the stream behind that build."""
+        built from the positions as they are when addGSO asks for it, and the forward orders the stream behind that build.
+        values=True: the graph with gso()'s values under the episode's symmetric_norm (GraphEdges.values) - for the GNN planners'
+        addGSO; an object of its own, refreshed in the same way."""
         self._grow_radii()
+        if values:
+            if self._valued_edges is None:
+                self._valued_edges = GraphEdges(self.pos, radii=self.radii, values=True, symmetric_norm=self.symmetric_norm)
+            return self._valued_edges.refresh()
         if self._edges is None:
             self._edges = GraphEdges(self.pos, radii=self.radii)
         return self._edges.refresh()
